@@ -6,7 +6,9 @@ encode this rank's 12,000 cells (n ~ U{6..26} objects x 256 points each, SURVEY.
 all-gather of the cell embeddings) -> encode this rank's 1,000 query texts -> float64 similarity + top-10.
 Weak scaling: every rank holds 12k cells + 1k queries, so the database is 12k x N cells.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times --steps steps, writes
+the last step's result if --dump-outputs DIR is given, and prints the line.  Everything else the benchmark measures or checks
+runs behind the timed region only with --full, which adds among others:
   roofline      the dominant kernel (the SA3 edge kernel, csrc/sa3.hip): algorithmic FLOPs / hipEvent-measured launch time,
                 against the nominal 2.5 PFLOP/s dense f16 MFMA peak (the f16x3 path issues 3 f16 MFMA FLOPs per algorithmic FLOP;
                 --precision fp32: against the 157.3 TFLOP/s fp32 MFMA peak)
@@ -487,6 +489,32 @@ def needs_self_launch(n_gpus, force=False, environ=None):
     return (n_gpus > 1 or force) and not under_launcher
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, idx, score, world, rank):
+    """--dump-outputs: the last timed step's result as the caller of distributed.sharded_retrieval receives it - top-k cell rows
+    (int64, written as float64: exact below 2**53) and their float64 scores - every rank's query block in rank order, i.e. the
+    whole query set.  Above DUMP_MAX_BYTES a fixed, seeded sample of query rows is written, with the rows in query_rows.npy."""
+    import torch.distributed as dist
+    arrays = {"topk_indices": idx.cpu().numpy().astype(np.float64), "topk_scores": score.cpu().numpy().astype(np.float64)}
+    if world > 1:
+        parts = [None] * world
+        dist.all_gather_object(parts, arrays)
+        arrays = {k: np.concatenate([p[k] for p in parts]) for k in arrays}
+    if rank != 0:
+        return
+    n = arrays["topk_indices"].shape[0]
+    row_bytes = sum(a[:1].nbytes for a in arrays.values())
+    if n * row_bytes > DUMP_MAX_BYTES:
+        rows = np.sort(np.random.default_rng(SEED).choice(n, DUMP_MAX_BYTES // (row_bytes + 8), replace=False))
+        arrays = {k: a[rows] for k, a in arrays.items()}
+        arrays["query_rows"] = rows.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
 def pipeline_rates(model, torch, n_cells=2048, n_poses=1024, top_k=(1, 5, 10), pad=16):
     """BASELINE configs[4]'s shape on one GPU, end to end from RAW Python scenes: `pipeline.evaluate` (evaluation/pipeline.py:
     282-342: every cell of the database through the dataloader chain + the coarse model, every query through the text branch,
@@ -548,6 +576,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also run every report-only measurement and check (per-kernel times and roofline, "
+                         "single-stream and fp32 passes, trained weights, phase rates, drop-in, pipeline, extras, CPU baseline, "
+                         "--oracle-cells); the --no-* switches below select among them.  Without it a run only times the step")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the last timed step's result (top-k rows and scores of every query) as DIR/<name>.npy")
     ap.add_argument("--cells", type=int, default=None,
                     help="cells per GPU.  Default: 12,000 at --gpus 1 (BASELINE configs[1]), 12,500 at --gpus N > 1 - so that the "
                          "driver's `--gpus 8` runs configs[2] exactly: a 100,000-cell database + 10,000 queries")
@@ -594,7 +628,7 @@ def main():
                          "it is not already running under a launcher; test hook)")
     ap.add_argument("--no-pipeline", action="store_true", help="skip the end-to-end evaluate() measurement from raw scenes")
     ap.add_argument("--oracle-cells", type=int, default=0,
-                    help="also encode this many cells of the workload (all 12,000 = the whole database) with the CPU oracle carrying the "
+                    help="with --full: also encode this many cells of the workload (all 12,000 = the whole database) with the CPU oracle carrying the "
                          "benchmarked weights, in parallel worker processes, and report per arithmetic path the cells beyond 1e-4, the kNN "
                          "graph differences and the largest error over ALL those cells (`oracle_full`; --oracle-out also writes it to a file). "
                          "~1-2 minutes of host time for 12,000 cells on the GPU box's 256 threads")
@@ -735,7 +769,7 @@ def main():
     from text2pos_amd.modules import tokenize
     tok, lens = tokenize(S.make_texts(SEED, q_lo, q_hi), model.language_encoder.known_words)
     d_tok, d_len = torch.from_numpy(tok).to(dev), torch.from_numpy(lens).to(dev)
-    h_pinned = [torch.from_numpy(a).pin_memory() for a in (xyz, rgb, center, mean_rgb)] if rank == 0 else None
+    h_pinned = [torch.from_numpy(a).pin_memory() for a in (xyz, rgb, center, mean_rgb)] if rank == 0 and args.full else None
     del xyz, rgb
 
     side = ops.concurrent_stream(dev)      # the text branch is independent of the cell branch: its (latency-bound)
@@ -795,16 +829,18 @@ def main():
     barrier()
     log("timed region")
     gather_events.clear()
-    single = args.cell_streams == 1 or (args.cell_streams == 0 and n_cells_total // world < 2048)   # (then the timed region itself is profiled)
-    ops.profile_enable(single)
+    single = args.cell_streams == 1 or (args.cell_streams == 0 and n_cells_total // world < 2048)   # (then --full profiles the timed region itself)
+    ops.profile_enable(single and args.full)
     t0 = time.perf_counter()
     for _ in range(args.steps):
         idx, score = step()
     barrier()
     elapsed = time.perf_counter() - t0
     ops.profile_enable(False)
-    prof, prof_steps = (ops.profile_report(), args.steps) if single else ({}, 0)
+    prof, prof_steps = (ops.profile_report(), args.steps) if single and args.full else ({}, 0)
     log(f"{args.steps} steps in {elapsed:.3f}s")
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, idx, score, world, rank)
     guard_code = model.overflow_detected() if args.precision == "f16x3" else 0
     if guard_code and not os.environ.get("T2P_ABLATION_RUN"):   # (ablation builds of the library compute garbage on purpose)
         raise SystemExit(f"fp16-range guard fired during the timed region (code {guard_code:#x}): the f16x3 numbers are invalid")
@@ -839,7 +875,7 @@ def main():
     # ---- per-kernel times: the same step with the whole cell encoder on ONE stream (an event pair around a launch then times
     # that kernel alone), hipEvents on the launch stream.  A multi-stream timed region cannot supply them.
     single_stream = None
-    if not single:
+    if args.full and not single:
         saved_streams, args.cell_streams = args.cell_streams, 1
         try:
             step()
@@ -869,7 +905,7 @@ def main():
 
     # ---- one pass of the same step on the exact fp32 MFMA path (outside the headline timing), and the precision evidence
     fp32_info = None
-    if args.precision == "f16x3" and not args.no_fp32_pass:
+    if args.full and args.precision == "f16x3" and not args.no_fp32_pass:
         light = ("obj_emb", "knn_idx")
         with torch.no_grad():
             x3_cells, x3_tr = model.encode_objects_packed(d_xyz, d_rgb, d_center, d_mean, cell_ptr, d_ptr,
@@ -935,7 +971,7 @@ def main():
     trained_info = None
     # (N = 1 only, like every other report-only block: a scaling run's line must not depend on a training run; `--weights trained` makes
     # the trained checkpoint the benchmarked model at any N)
-    if args.weights == "random" and not args.no_trained and args.precision == "f16x3" and args.cell_variant == "ragged" and world == 1:
+    if args.full and args.weights == "random" and not args.no_trained and args.precision == "f16x3" and args.cell_variant == "ragged" and world == 1:
         try:
             import train_checkpoint as TC
             tmodel, tinfo = TC.trained_model(None, device=dev, log=log)
@@ -997,116 +1033,133 @@ def main():
             trained_info = {"error": f"{type(e).__name__}: {e}"}
             log(f"trained-weights block failed: {trained_info['error']}")
 
-    # per-phase rates (outside the timed region; SURVEY 8(d) sub-metrics): each phase alone, events on torch's stream
-    def timed(fn, reps):
-        """median wall time of `reps` synchronised calls (after one untimed call)"""
-        r = fn()
-        torch.cuda.synchronize()
-        ts = []
-        for _ in range(reps):
-            t = time.perf_counter()
-            r = fn()
-            torch.cuda.synchronize()
-            ts.append(time.perf_counter() - t)
-        return float(np.median(ts)), r
-    with torch.no_grad():
-        t_cells, cells_ = timed(lambda: model.encode_objects_packed(d_xyz, d_rgb, d_center, d_mean, cell_ptr, d_ptr,
-                                                                    chunk_objects=args.chunk_objects), 3)
-        t_text, q_ = timed(lambda: model.language_encoder.encode_tokens(d_tok, d_len, normalize=True), 11)
-        t_topk, _ = timed(lambda: ops.sim_topk(q_, cells_, TOPK), 11)
-    phase_rates = {"cells_per_s": (c_hi - c_lo) / t_cells, "objects_per_s": n_obj / t_cells,
-                   "queries_per_s": (q_hi - q_lo) / t_text, "retrieval_qps": (q_hi - q_lo) / t_topk,
-                   "note": "this rank, each phase alone (encode cells / encode text / sim + top-k over this rank's cells): median of 3 / "
-                           "11 / 11 synchronised calls"}
-    # roofline fractions of the two other phases (SURVEY 8(d)): text = 2,097,152 FLOP per token minus the input projection
-    # (a [V][4D] gate table here) = 2 dirs x 2 x 256 x 1024 per token on the fp32 matrix path; retrieval = 2 Nq Nc D on
-    # the fp64 matrix path (78.6 TFLOP/s dense)
-    n_tok = int(d_len.sum().item())
-    text_flops = 2.0 * 2 * 256 * 1024 * n_tok
-    sim_flops = 2.0 * (q_hi - q_lo) * cells_.shape[0] * 256
-    phase_rates["roofline"] = {
-        # (a call's latency is max_len sequential time steps whatever the batch: 1,000 queries occupy 64 of the 256 CUs)
-        "text": {"bound": ("mfma (f16x3: 3 f16 MFMA FLOPs per algorithmic FLOP)" if args.precision == "f16x3" else "mfma (fp32)")
-                 + " / latency of the recurrence", "achieved_tflops": text_flops / t_text / 1e12,
-                 "peak_tflops": F16_MFMA_PEAK_TFLOPS if args.precision == "f16x3" else FP32_MFMA_PEAK_TFLOPS,
-                 "frac": text_flops / t_text / 1e12 / (F16_MFMA_PEAK_TFLOPS if args.precision == "f16x3" else FP32_MFMA_PEAK_TFLOPS),
-                 "tokens": n_tok},
-        "retrieval": {"bound": "mfma (fp64)", "achieved_tflops": sim_flops / t_topk / 1e12, "peak_tflops": 78.6,
-                      "frac": sim_flops / t_topk / 1e12 / 78.6}}
-    if rank == 0:  # PCIe-inclusive cell rate: pinned host arrays -> HBM -> embeddings (never `value`)
-        def with_h2d():  # copies of block b+1 under the kernels of block b (CellRetrievalNetwork.encode_objects_packed_host)
-            return model.encode_objects_packed_host(*h_pinned, cell_ptr)
-        with torch.no_grad():
-            t_h2d, _ = timed(with_h2d, 3)
-        phase_rates["cells_per_s_incl_h2d"] = (c_hi - c_lo) / t_h2d
-        phase_rates["h2d_bytes"] = int(sum(t.numel() * 4 for t in h_pinned))
-
     # sanity on the result of the last step (not timed): sorted scores, valid indices
     assert os.environ.get("T2P_ABLATION_RUN") or (bool((score[:, :-1] >= score[:, 1:]).all()) and bool((idx >= 0).all()) and bool((idx < n_cells_total).all()))
 
+    if args.full:
+        # per-phase rates (outside the timed region; SURVEY 8(d) sub-metrics): each phase alone, events on torch's stream
+        def timed(fn, reps):
+            """median wall time of `reps` synchronised calls (after one untimed call)"""
+            r = fn()
+            torch.cuda.synchronize()
+            ts = []
+            for _ in range(reps):
+                t = time.perf_counter()
+                r = fn()
+                torch.cuda.synchronize()
+                ts.append(time.perf_counter() - t)
+            return float(np.median(ts)), r
+        with torch.no_grad():
+            t_cells, cells_ = timed(lambda: model.encode_objects_packed(d_xyz, d_rgb, d_center, d_mean, cell_ptr, d_ptr,
+                                                                        chunk_objects=args.chunk_objects), 3)
+            t_text, q_ = timed(lambda: model.language_encoder.encode_tokens(d_tok, d_len, normalize=True), 11)
+            t_topk, _ = timed(lambda: ops.sim_topk(q_, cells_, TOPK), 11)
+        phase_rates = {"cells_per_s": (c_hi - c_lo) / t_cells, "objects_per_s": n_obj / t_cells,
+                       "queries_per_s": (q_hi - q_lo) / t_text, "retrieval_qps": (q_hi - q_lo) / t_topk,
+                       "note": "this rank, each phase alone (encode cells / encode text / sim + top-k over this rank's cells): median of 3 / "
+                               "11 / 11 synchronised calls"}
+        # roofline fractions of the two other phases (SURVEY 8(d)): text = 2,097,152 FLOP per token minus the input projection
+        # (a [V][4D] gate table here) = 2 dirs x 2 x 256 x 1024 per token on the fp32 matrix path; retrieval = 2 Nq Nc D on
+        # the fp64 matrix path (78.6 TFLOP/s dense)
+        n_tok = int(d_len.sum().item())
+        text_flops = 2.0 * 2 * 256 * 1024 * n_tok
+        sim_flops = 2.0 * (q_hi - q_lo) * cells_.shape[0] * 256
+        phase_rates["roofline"] = {
+            # (a call's latency is max_len sequential time steps whatever the batch: 1,000 queries occupy 64 of the 256 CUs)
+            "text": {"bound": ("mfma (f16x3: 3 f16 MFMA FLOPs per algorithmic FLOP)" if args.precision == "f16x3" else "mfma (fp32)")
+                     + " / latency of the recurrence", "achieved_tflops": text_flops / t_text / 1e12,
+                     "peak_tflops": F16_MFMA_PEAK_TFLOPS if args.precision == "f16x3" else FP32_MFMA_PEAK_TFLOPS,
+                     "frac": text_flops / t_text / 1e12 / (F16_MFMA_PEAK_TFLOPS if args.precision == "f16x3" else FP32_MFMA_PEAK_TFLOPS),
+                     "tokens": n_tok},
+            "retrieval": {"bound": "mfma (fp64)", "achieved_tflops": sim_flops / t_topk / 1e12, "peak_tflops": 78.6,
+                          "frac": sim_flops / t_topk / 1e12 / 78.6}}
+        if rank == 0:  # PCIe-inclusive cell rate: pinned host arrays -> HBM -> embeddings (never `value`)
+            def with_h2d():  # copies of block b+1 under the kernels of block b (CellRetrievalNetwork.encode_objects_packed_host)
+                return model.encode_objects_packed_host(*h_pinned, cell_ptr)
+            with torch.no_grad():
+                t_h2d, _ = timed(with_h2d, 3)
+            phase_rates["cells_per_s_incl_h2d"] = (c_hi - c_lo) / t_h2d
+            phase_rates["h2d_bytes"] = int(sum(t.numel() * 4 for t in h_pinned))
+
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3
-        # algorithmic work of the dominant kernel: 2*256*256 FLOP per SA3 edge row (ball-query edges + self loops)
-        with torch.no_grad():
-            e_lvl, e1_dedup = edge_rows(ops, torch, d_xyz, d_rgb)
-        e3 = e_lvl[2]
-        launches, total_ms = prof.get(DOMINANT, (0, 0.0))
-        flops_per_step = 2.0 * 256 * 256 * e3
-        achieved = (flops_per_step * prof_steps) / (total_ms * 1e-3) / 1e12 if total_ms > 0 else None
-        peak = F16_MFMA_PEAK_TFLOPS if args.precision == "f16x3" else FP32_MFMA_PEAK_TFLOPS
-        phases = {k: round(v[1] / prof_steps, 3) for k, v in sorted(prof.items(), key=lambda kv: -kv[1][1])}
-        # SURVEY 8(d): FPS / ball query are scan-type (latency / issue bound); their compulsory read is the object's xyz + rgb
-        # (6,168 B): report the HBM rate that corresponds to, as overhead against the encoder's MFMA bound
-        sg_launches, sg_ms = prof.get("sample_group", (0, 0.0))
-        if sg_ms > 0:
-            gbps = 6168.0 * n_obj * prof_steps / (sg_ms * 1e-3) / 1e9
-            phase_rates["roofline"]["sample_group"] = {"bound": "latency / issue (scan)", "achieved_gbps": gbps, "peak_gbps": 8000.0,
-                                                       "frac": gbps / 8000.0, "ms_per_step": sg_ms / prof_steps}
-        # HBM traffic and MFMA-busy fraction of the dominant kernel from the committed counter passes (separate rocprofv3 --pmc runs
-        # of this command: bench.py cannot host rocprofv3 itself): newest profiles/*_evidence.json, which carries the content hashes
-        # of the kernel sources it was taken on - a figure whose kernel source has changed since is refused, not quoted
-        traffic, traffic_source, mfma_busy, step_bytes = None, None, None, None
-        try:
-            ev_file, ev_doc = committed_evidence()
-            if ev_doc and args.precision == "f16x3" and args.cells == CELLS_PER_GPU and args.cell_variant == "ragged":
-                stale = stale_sources(ev_doc, ("csrc/sa3.hip", "csrc/t2p_common.h"))
-                if stale:
-                    traffic_source = (f"REFUSED: profiles/{ev_file} was taken on other sources ({', '.join(stale)} changed since): "
-                                      "re-run profiles/collect.sh")
-                else:
-                    row = ev_doc["kernels"].get(DOMINANT_SYMBOL, {})
-                    traffic = row.get("hbm_bytes_per_launch")
-                    mfma_busy = {"frac_of_kernel_cycles": row.get("mfma_busy"), "frac_at_2400mhz": row.get("mfma_busy_at_2400mhz"),
-                                 "shader_clock_ghz": row.get("shader_clock_ghz"),
-                                 "counter": "SQ_VALU_MFMA_BUSY_CYCLES / (1,024 SIMDs x the kernel's busy cycles from the GRBM_GUI_ACTIVE pass)"}
-                    traffic_source = (f"profiles/{ev_file} (tag {ev_doc.get('tag')}; separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE / SQ / GRBM "
-                                      f"passes of this command on sources with csrc/sa3.hip sha256 {ev_doc['source_sha256_16'].get('csrc/sa3.hip')}: "
-                                      "same as this tree's; not measured in this run)")
-                    if not stale_sources(ev_doc, None):      # whole-step bytes need every kernel source unchanged
-                        step_bytes = ev_doc.get("whole_run", {}).get("hbm_bytes_per_step")
-        except Exception as e:
-            traffic_source = f"no usable evidence file ({type(e).__name__}: {e})"
-        # the other SA levels and the whole step, same convention (algorithmic FLOPs executed / hipEvent time)
-        sizes_np = np.diff(cell_ptr).astype(np.int64)
-        knn_edges = int((sizes_np * np.minimum(sizes_np, 8)).sum())
-        sa1_per_edge = args.precision == "f16x3"     # (sa_points.hip runs level 1: both layers per edge)
-        ex = executed_flops(e_lvl, e1_dedup if not (args.tuning & 1) else e_lvl[0], n_obj, c_hi - c_lo, knn_edges, sa1_per_edge)
-        sa_levels = {}
-        for name, rows_l, hc in (("ws_edge_sa_k32_n64", e1_dedup if not (args.tuning & 1) else e_lvl[0],
-                                  32 * 64 + (6 * 32 if sa1_per_edge else 0)),
-                                 ("ws_edge_sa_k128_n128", e_lvl[1], 128 * 128), ("ws_edge_sa_k256_n256", e_lvl[2], 256 * 256)):
-            ln, ms = prof.get(name, (0, 0.0))
-            tf = 2.0 * hc * rows_l * prof_steps / (ms * 1e-3) / 1e12 if ms > 0 else None
-            sa_levels[name] = {"edge_rows_per_step": rows_l, "ms_per_step": ms / prof_steps, "achieved_tflops": tf,
-                               "frac_of_peak": tf / peak if tf else None,
-                               "frac_of_f16x3_ceiling": (3.0 * tf / peak if tf else None) if args.precision == "f16x3" else None}
-        compulsory = float(COMPULSORY_BYTES_PER_OBJECT) * n_obj
-        whole_step = {"hbm_bytes_per_step": step_bytes, "compulsory_bytes_per_step": compulsory,
-                      "hbm_bytes_over_compulsory": (step_bytes / compulsory) if step_bytes else None,
-                      "executed_flop_per_step": ex, "achieved_tflops": ex["total"] / (ms_per_step * 1e-3) / 1e12,
-                      "frac_of_peak": ex["total"] / (ms_per_step * 1e-3) / 1e12 / peak,
-                      "note": "algorithmic FLOPs this plan executes (layer 1 of the SA MLPs per point at levels 2 / 3, per edge at level 1; "
-                              "SA1 rows after t2p_dedup_rows) over the whole timed step, text branch and ranking excluded"}
+        full_out = {}
+        if args.full:
+            # algorithmic work of the dominant kernel: 2*256*256 FLOP per SA3 edge row (ball-query edges + self loops)
+            with torch.no_grad():
+                e_lvl, e1_dedup = edge_rows(ops, torch, d_xyz, d_rgb)
+            e3 = e_lvl[2]
+            launches, total_ms = prof.get(DOMINANT, (0, 0.0))
+            flops_per_step = 2.0 * 256 * 256 * e3
+            achieved = (flops_per_step * prof_steps) / (total_ms * 1e-3) / 1e12 if total_ms > 0 else None
+            peak = F16_MFMA_PEAK_TFLOPS if args.precision == "f16x3" else FP32_MFMA_PEAK_TFLOPS
+            phases = {k: round(v[1] / prof_steps, 3) for k, v in sorted(prof.items(), key=lambda kv: -kv[1][1])}
+            # SURVEY 8(d): FPS / ball query are scan-type (latency / issue bound); their compulsory read is the object's xyz + rgb
+            # (6,168 B): report the HBM rate that corresponds to, as overhead against the encoder's MFMA bound
+            sg_launches, sg_ms = prof.get("sample_group", (0, 0.0))
+            if sg_ms > 0:
+                gbps = 6168.0 * n_obj * prof_steps / (sg_ms * 1e-3) / 1e9
+                phase_rates["roofline"]["sample_group"] = {"bound": "latency / issue (scan)", "achieved_gbps": gbps, "peak_gbps": 8000.0,
+                                                           "frac": gbps / 8000.0, "ms_per_step": sg_ms / prof_steps}
+            # HBM traffic and MFMA-busy fraction of the dominant kernel from the committed counter passes (separate rocprofv3 --pmc runs
+            # of this command: bench.py cannot host rocprofv3 itself): newest profiles/*_evidence.json, which carries the content hashes
+            # of the kernel sources it was taken on - a figure whose kernel source has changed since is refused, not quoted
+            traffic, traffic_source, mfma_busy, step_bytes = None, None, None, None
+            try:
+                ev_file, ev_doc = committed_evidence()
+                if ev_doc and args.precision == "f16x3" and args.cells == CELLS_PER_GPU and args.cell_variant == "ragged":
+                    stale = stale_sources(ev_doc, ("csrc/sa3.hip", "csrc/t2p_common.h"))
+                    if stale:
+                        traffic_source = (f"REFUSED: profiles/{ev_file} was taken on other sources ({', '.join(stale)} changed since): "
+                                          "re-run profiles/collect.sh")
+                    else:
+                        row = ev_doc["kernels"].get(DOMINANT_SYMBOL, {})
+                        traffic = row.get("hbm_bytes_per_launch")
+                        mfma_busy = {"frac_of_kernel_cycles": row.get("mfma_busy"), "frac_at_2400mhz": row.get("mfma_busy_at_2400mhz"),
+                                     "shader_clock_ghz": row.get("shader_clock_ghz"),
+                                     "counter": "SQ_VALU_MFMA_BUSY_CYCLES / (1,024 SIMDs x the kernel's busy cycles from the GRBM_GUI_ACTIVE pass)"}
+                        traffic_source = (f"profiles/{ev_file} (tag {ev_doc.get('tag')}; separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE / SQ / GRBM "
+                                          f"passes of this command on sources with csrc/sa3.hip sha256 {ev_doc['source_sha256_16'].get('csrc/sa3.hip')}: "
+                                          "same as this tree's; not measured in this run)")
+                        if not stale_sources(ev_doc, None):      # whole-step bytes need every kernel source unchanged
+                            step_bytes = ev_doc.get("whole_run", {}).get("hbm_bytes_per_step")
+            except Exception as e:
+                traffic_source = f"no usable evidence file ({type(e).__name__}: {e})"
+            # the other SA levels and the whole step, same convention (algorithmic FLOPs executed / hipEvent time)
+            sizes_np = np.diff(cell_ptr).astype(np.int64)
+            knn_edges = int((sizes_np * np.minimum(sizes_np, 8)).sum())
+            sa1_per_edge = args.precision == "f16x3"     # (sa_points.hip runs level 1: both layers per edge)
+            ex = executed_flops(e_lvl, e1_dedup if not (args.tuning & 1) else e_lvl[0], n_obj, c_hi - c_lo, knn_edges, sa1_per_edge)
+            sa_levels = {}
+            for name, rows_l, hc in (("ws_edge_sa_k32_n64", e1_dedup if not (args.tuning & 1) else e_lvl[0],
+                                      32 * 64 + (6 * 32 if sa1_per_edge else 0)),
+                                     ("ws_edge_sa_k128_n128", e_lvl[1], 128 * 128), ("ws_edge_sa_k256_n256", e_lvl[2], 256 * 256)):
+                ln, ms = prof.get(name, (0, 0.0))
+                tf = 2.0 * hc * rows_l * prof_steps / (ms * 1e-3) / 1e12 if ms > 0 else None
+                sa_levels[name] = {"edge_rows_per_step": rows_l, "ms_per_step": ms / prof_steps, "achieved_tflops": tf,
+                                   "frac_of_peak": tf / peak if tf else None,
+                                   "frac_of_f16x3_ceiling": (3.0 * tf / peak if tf else None) if args.precision == "f16x3" else None}
+            compulsory = float(COMPULSORY_BYTES_PER_OBJECT) * n_obj
+            whole_step = {"hbm_bytes_per_step": step_bytes, "compulsory_bytes_per_step": compulsory,
+                          "hbm_bytes_over_compulsory": (step_bytes / compulsory) if step_bytes else None,
+                          "executed_flop_per_step": ex, "achieved_tflops": ex["total"] / (ms_per_step * 1e-3) / 1e12,
+                          "frac_of_peak": ex["total"] / (ms_per_step * 1e-3) / 1e12 / peak,
+                          "note": "algorithmic FLOPs this plan executes (layer 1 of the SA MLPs per point at levels 2 / 3, per edge at level 1; "
+                                  "SA1 rows after t2p_dedup_rows) over the whole timed step, text branch and ranking excluded"}
+            full_out = {"kernel_ms_per_step": phases, "phase_rates": phase_rates,
+                "roofline": {"bound": "mfma", "kernel": "t2p::" + DOMINANT_SYMBOL, "kernel_file": "text2pos-cvpr2022_amd/csrc/sa3.hip",
+                             "profile_scope": DOMINANT, "achieved": achieved, "peak": peak,
+                             "unit": "TFLOP/s", "frac": (achieved / peak) if achieved else None,
+                             "traffic": traffic, "traffic_source": traffic_source, "mfma_busy": mfma_busy, "launches": launches, "avg_launch_ms": (total_ms / launches) if launches else None,
+                             "measured_in": ("the timed region (single stream)" if single_stream is None else
+                                             f"a single-stream pass of the same step right behind the timed region ({prof_steps} steps; hipEvents on "
+                                             "the launch stream): in the multi-stream timed region an event pair around one launch also spans "
+                                             "the other stream's kernels"),
+                             "algorithmic_flop_per_step": flops_per_step, "sa3_edge_rows_per_step": e3,
+                             "sa_levels": sa_levels, "whole_step": whole_step,
+                             "note": ("algorithmic FLOPs = 2*256*256 per SA3 edge row; the f16x3 path executes 3 f16 MFMA FLOPs per "
+                                      "algorithmic FLOP, so its ceiling on this metric is peak/3 = 833 TFLOP/s"
+                                      if args.precision == "f16x3" else "exact fp32 MFMA path")}}
         out = {
             "metric": "cells+queries encoded/sec and top-k retrieval QPS, 256-pt cells, 12k-cell DB",
             "value": (n_cells_total + n_q_total) / (elapsed / args.steps),
@@ -1127,26 +1180,13 @@ def main():
                                    ("calibrated by one train-mode pass over 64 cells (deviation from SURVEY 8(d), which randomises "
                                     "them: random statistics collapse every embedding onto one direction; --bn random restores it)"
                                     if args.bn == "calibrated" else "random (SURVEY 8(d))") +
-                                   "; the same step on a TRAINED checkpoint: `trained_weights`") if weights_info is None else
+                                   ("; the same step on a TRAINED checkpoint: `trained_weights`" if trained_info else "")) if weights_info is None else
                                   {"kind": "trained checkpoint (train_checkpoint.py)" if args.weights == "trained" else "checkpoint file",
                                    "file": None if args.weights == "trained" else os.path.basename(args.weights), **weights_info}),
                        "cell_streams": ("product default: 2 parts of the cell batch on 2 HIP streams" if args.cell_streams == 0 and not single
                                         else (args.cell_streams or 1)),
                        "parallelism": f"cells+queries sharded x{world}, 1 all-gather" if world > 1 else "single GPU"},
-            "kernel_ms_per_step": phases, "phase_rates": phase_rates,
-            "roofline": {"bound": "mfma", "kernel": "t2p::" + DOMINANT_SYMBOL, "kernel_file": "text2pos-cvpr2022_amd/csrc/sa3.hip",
-                         "profile_scope": DOMINANT, "achieved": achieved, "peak": peak,
-                         "unit": "TFLOP/s", "frac": (achieved / peak) if achieved else None,
-                         "traffic": traffic, "traffic_source": traffic_source, "mfma_busy": mfma_busy, "launches": launches, "avg_launch_ms": (total_ms / launches) if launches else None,
-                         "measured_in": ("the timed region (single stream)" if single_stream is None else
-                                         f"a single-stream pass of the same step right behind the timed region ({prof_steps} steps; hipEvents on "
-                                         "the launch stream): in the multi-stream timed region an event pair around one launch also spans "
-                                         "the other stream's kernels"),
-                         "algorithmic_flop_per_step": flops_per_step, "sa3_edge_rows_per_step": e3,
-                         "sa_levels": sa_levels, "whole_step": whole_step,
-                         "note": ("algorithmic FLOPs = 2*256*256 per SA3 edge row; the f16x3 path executes 3 f16 MFMA FLOPs per "
-                                  "algorithmic FLOP, so its ceiling on this metric is peak/3 = 833 TFLOP/s"
-                                  if args.precision == "f16x3" else "exact fp32 MFMA path")},
+            **full_out,
             "host_generation_s": round(gen_s, 2),
             # rank 0's first queries (global queries 0..15) and the GLOBAL cell rows they retrieved: the same lists at any N with
             # the same total database and query set (the synthetic data is a function of the global index)
@@ -1165,13 +1205,13 @@ def main():
             out["exchange"] = exchange
         if trained_info:
             out["trained_weights"] = trained_info
-        if not args.no_dropin and world == 1 and args.cell_variant == "ragged":
+        if args.full and not args.no_dropin and world == 1 and args.cell_variant == "ragged":
             log("drop-in caller shape: encode_objects(objects, object_points) at batch 64 / 512")
             out["dropin"] = dropin_rates(model, S, torch)
-        if not args.no_pipeline and world == 1 and args.cell_variant == "ragged":
+        if args.full and not args.no_pipeline and world == 1 and args.cell_variant == "ragged":
             log("pipeline: evaluate() end to end from raw Object3d scenes (configs[4] shape, 2,048 cells / 1,024 poses)")
             out["pipeline"] = pipeline_rates(model, torch)
-        if not args.no_extras and world == 1 and args.cell_variant == "ragged":
+        if args.full and not args.no_extras and world == 1 and args.cell_variant == "ragged":
             # report-only measurements, all outside the timed region: on-box peaks, SURVEY 8(d)'s two other cell shapes
             # (the cost is per object, so objects/s is the comparable figure), the fine stage (BASELINE configs[3])
             log("extras: on-box peaks")
@@ -1211,7 +1251,7 @@ def main():
             fine = bench_fine.run(queries=args.fine_queries, topk=10, steps=3, warmup=1, precision=args.precision)
             out["fine_stage"] = {k: fine[k] for k in ("metric", "value", "unit", "ms_per_step", "config", "queries_per_s",
                                                       "matcher_kernels_ms_per_step")}
-        if not args.no_cpu_baseline and world == 1:  # the CPU baseline is timed on rank 0 at N = 1 only
+        if args.full and not args.no_cpu_baseline and world == 1:  # the CPU baseline is timed on rank 0 at N = 1 only
             big_host = (os.cpu_count() or 1) >= 32
             n_cells_cpu = args.cpu_cells or (256 if big_host else 16)
             log("cpu baseline")
@@ -1227,7 +1267,7 @@ def main():
                     "timed region) against both arithmetic paths of the HIP library: cells further than north_star's 1e-4 from the "
                     "oracle (each one a DynamicEdgeConv near-tie that fell the other way; tests/test_gpu_headline.py proves the ties) "
                     "and the largest difference over all other cells"))
-        if args.oracle_cells and world == 1 and fp32_info and args.cell_variant == "ragged":   # (its own switch: independent of the CPU baseline leg)
+        if args.full and args.oracle_cells and world == 1 and fp32_info and args.cell_variant == "ragged":   # (its own switch: independent of the CPU baseline leg)
             n_or = min(args.oracle_cells, c_hi - c_lo)
             log(f"oracle_full: {n_or} cells through the CPU oracle in parallel worker processes")
             of = oracle_full_check(SEED, n_cells_total, n_or, {k: v.detach().cpu() for k, v in model.state_dict().items()},

@@ -1,7 +1,8 @@
 # How far the fp32 oracle's training-mode gradients are from its own float64 evaluation (the conditioning behind the gradient bars of
 # tests/test_gpu_parity.py::test_cell_branch_training_step_matches_autograd): python profiles/oracle_grad_conditioning.py <seed> [alt|nc|f1|sl] [cells]
-import sys, torch, numpy as np, copy
-sys.path.insert(0, '/root/repo'); sys.path.insert(0, '/root/repo/tests/golden')
+import os, sys, torch, numpy as np, copy
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'tests', 'golden'))
 import weights as W
 from text2pos_amd import synthetic as S
 from oracle import model as OM

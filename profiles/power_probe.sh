@@ -1,8 +1,8 @@
 #!/bin/bash
 # Is the chip power-limited under this path's kernels?  Samples rocm-smi (socket power, sclk) every 0.25 s while
 #   (1) nothing runs, (2) bench.py's step loops, (3) the bare f16 MFMA loop of microbench/mix2 (random operands) runs.
-# usage (GPU box, repo root): bash profiles/power_probe.sh <outdir>
-out=${1:-gpurun_out/power}; mkdir -p $out; cd /root/repo; export TMPDIR=/tmp
+# usage (MI355X machine): bash profiles/power_probe.sh <outdir, relative to the repository root>
+cd "$(dirname "$0")/.."; out=${1:-prof_out/power}; mkdir -p $out; export TMPDIR=/tmp
 sample() {  # $1 = tag, $2 = seconds
   for i in $(seq 1 $(( $2 * 4 ))); do
     echo "== $(date +%s.%N)"; /opt/rocm/bin/rocm-smi -P -c 2>/dev/null | grep -E "Power|sclk|mclk|fclk"; sleep 0.25

@@ -3,8 +3,8 @@ kernel on a pair of them behind a common start event: side by side the pair take
     python profiles/tools/probe_stream_queues.py            (GPU_MAX_HW_QUEUES=8 python ... for the 8-queue runtime setting)
 Measured on MI355X / ROCm 7.2 (round 6): the default stream shares with the 7th used stream, stream 1 with stream 6; no pair
 shares with GPU_MAX_HW_QUEUES=8.  ops.concurrent_stream is the product-side use of the same measurement."""
-import sys, time
-sys.path.insert(0, "/root/repo")
+import os, sys, time
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import torch
 import text2pos_amd
 from text2pos_amd import ops

@@ -1,6 +1,7 @@
 # Timing + torch.profiler table of one coarse training step on the HIP path (docs/notebook.md 4.8): python profiles/train_step_time.py [batch]
-import sys, time, torch, numpy as np
-sys.path.insert(0, '/root/repo'); sys.path.insert(0, '/root/repo/tests/golden')
+import os, sys, time, torch, numpy as np
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'tests', 'golden'))
 import weights as W
 import text2pos_amd as t2p
 from text2pos_amd import synthetic as S

@@ -128,7 +128,7 @@ typedef struct t2p_cell_weights {
     const float* color_embedding;
     /* fp16-range guard (cfg->overflow_flag): bound of GA layer 1's output from its input's magnitude,
      * |gh| <= ga_w1_l1 * max(|F_3|, 1) + ga_b1_absmax with ga_w1_l1 = max over output columns of sum_k |ga_w1[k][col]|
-     * and ga_b1_absmax = max |ga_b1| (that kernel's epilogue is too tight for a running maximum of its own). */
+     * and ga_b1_absmax = max |ga_b1| (the high side; the kernel's exact maximum of what it stores also serves the low side). */
     float ga_w1_l1;
     float ga_b1_absmax;
     /* the same kind of bound for the layer-1 tables that depend on the inputs only: sa_wp_l1[l] = max over columns of
@@ -174,10 +174,12 @@ typedef struct t2p_cell_config {
      * (round to nearest: a magnitude past 65504 would become inf).  When non-NULL, this DEVICE word receives a
      * sticky OR of a non-zero code whenever a conversion site of the call may have left fp16's range (bits 0-2: SA level
      * 1-3 edge inputs, judged by max|A_l| + max|B_l|; bit 3: SA output rows split by the dense table kernels; bit 4: GA
-     * hidden planes, judged by a norm bound; bit 5: rows of the LDS-tiled GEMMs; bit 6: a NaN among the input points / colours -
-     * the float-max aggregation of the f16x3 kernels would drop it where the reference's scatter-max propagates it; bit 7: LOW side - the
-     * largest hidden activation or the largest output of an SA level is below 2^-7, where the fp16 pieces keep an absolute 2^-25
-     * instead of a relative 2^-22 and a later BatchNorm that rescales would expose the loss).  The tests are conservative: they may
+     * hidden planes, judged by a norm bound and by their exact maximum; bit 5: rows of the LDS-tiled GEMMs and the kNN edge
+     * rows; bit 6: a NaN among the input points / colours - the float-max aggregation of the f16x3 kernels would drop it where
+     * the reference's scatter-max propagates it; bit 7: LOW side - the largest hidden activation or the largest output of an
+     * SA level, the largest GA hidden activation, PointNet2 feature (features0 / 1 / 2, each on its own) or kNN edge row is
+     * below 2^-7, where the fp16 pieces keep an absolute 2^-25 instead of a relative 2^-22 and a later BatchNorm that rescales
+     * would expose the loss).  The tests are conservative: they may
      * fire for a checkpoint that would just have fitted, never the other way round.  The caller clears it, reads it after the stream has drained, and must
      * not trust the call's output when it is set (the Python host raises or re-runs with precision = 0).  NULL: no check. */
     int32_t* overflow_flag;

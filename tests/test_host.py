@@ -938,26 +938,11 @@ def test_bench_oracle_full_check_machinery(oracle_model):
     assert g.tolist() == [[0, 1], [1, -1], [2, 3], [3, 2]]
 
 
-def test_sa_rows_inline_asm_mfmas_keep_their_distance_from_valu_writes():
-    """k_sa_rows issues its MFMAs as inline asm (their weight operands live in AGPRs), which hipcc's hazard recogniser does not see as
-    MFMAs: gfx950 needs two wait states between a VALU write of a VGPR and an MFMA that reads it as A / B operand, and only the
-    source's structure provides them.  Compile the file for gfx950 and check the generated code: no VALU instruction writes a register
-    that an MFMA reads within the next two issue slots (an s_nop in between counts for its wait states)."""
+def _mfma_hazards(ops):
+    """(number of MFMAs, [(wait states, VALU instruction, MFMA)]) of one function's instruction list: a VALU instruction that
+    writes a VGPR which an MFMA reads as A / B operand within the next two issue slots (an s_nop in between counts for its wait
+    states)."""
     import re
-    import subprocess
-    import tempfile
-    src = os.path.join(ROOT, "text2pos-cvpr2022_amd", "csrc", "sa_rows.hip")
-    hipcc = "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("no hipcc")
-    with tempfile.TemporaryDirectory() as d:
-        out = os.path.join(d, "sa_rows.s")
-        subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "--cuda-device-only", "-S", src, "-o", out],
-                       check=True, capture_output=True)
-        text = open(out).read().split("\n")
-    st = [i for i, l in enumerate(text) if re.match(r"^_Z\w+:", l) and "k_sa_rows" in l][0]
-    fe = next(i for i in range(st, len(text)) if text[i].startswith(".Lfunc_end"))
-    ops = [l.strip() for l in text[st + 1: fe] if l.strip() and not l.strip().startswith((";", ".")) and not l.strip().endswith(":")]
 
     def regs(tok):
         tok = tok.strip()
@@ -985,8 +970,55 @@ def test_sa_rows_inline_asm_mfmas_keep_their_distance_from_valu_writes():
                 close.append((states, p, o))
                 break
             states += 1
-    assert n_mfma == 96, n_mfma
-    assert not close, close[:3]
+    return n_mfma, close
+
+
+def test_mfmas_keep_their_distance_from_valu_writes():
+    """gfx950 needs two wait states between a VALU write of a VGPR and an MFMA that reads it as A / B operand.  hipcc pads the
+    MFMAs it schedules itself, but not those issued as inline asm (k_sa_rows keeps its weight operands in AGPRs and issues its
+    MFMAs that way: only the source's structure provides the distance there), and a compiler change could break either.  Compile
+    every source of csrc/ for gfx950 with the library's flags and check the generated code of every function that issues MFMAs:
+    no VALU instruction writes a register that an MFMA reads within the next two issue slots.  k_sa_rows issues exactly 96."""
+    import glob
+    import importlib
+    import re
+    import subprocess
+    import tempfile
+    from concurrent.futures import ThreadPoolExecutor
+    hipcc = "/opt/rocm/bin/hipcc"
+    if not os.path.exists(hipcc):
+        pytest.skip("no hipcc")
+    builder = importlib.import_module("text2pos-cvpr2022_amd.build")
+    flags = [f for f in builder.FLAGS if f != "-fPIC"]
+    srcs = sorted(glob.glob(os.path.join(ROOT, "text2pos-cvpr2022_amd", "csrc", "*.hip")))
+    assert len(srcs) >= 17
+
+    with tempfile.TemporaryDirectory() as d:
+        def isa(src):
+            out = os.path.join(d, os.path.basename(src) + ".s")
+            subprocess.run([hipcc, *flags, "--cuda-device-only", "-S", src, "-o", out], check=True, capture_output=True)
+            return os.path.basename(src), open(out).read().split("\n")
+        with ThreadPoolExecutor(max_workers=min(16, len(srcs))) as ex:
+            texts = list(ex.map(isa, srcs))
+    per_fn = {}
+    for name, text in texts:
+        for st, line in enumerate(text):
+            m = re.match(r"^([A-Za-z_]\w*):", line)
+            if not m or m.group(1).startswith(".L"):
+                continue
+            fe = next((i for i in range(st, len(text)) if text[i].startswith(".Lfunc_end")), None)
+            if fe is None:
+                continue
+            ops = [l.strip() for l in text[st + 1: fe] if l.strip() and not l.strip().startswith((";", ".")) and not l.strip().endswith(":")]
+            n_mfma, close = _mfma_hazards(ops)
+            if n_mfma:
+                per_fn[(name, m.group(1))] = (n_mfma, close)
+    sa_rows = [v[0] for (f, fn), v in per_fn.items() if "k_sa_rows" in fn]
+    assert sa_rows == [96], sa_rows
+    assert len(per_fn) >= 40, sorted(per_fn)          # (about 45 kernel instantiations issue MFMAs)
+    bad = {k: v[1][:3] for k, v in per_fn.items() if v[1]}
+    assert not bad, bad
+    print(f"{len(per_fn)} functions, {sum(v[0] for v in per_fn.values())} MFMAs checked")
 
 
 def test_concurrent_stream_selection_on_a_model_of_the_hardware_queues(monkeypatch):

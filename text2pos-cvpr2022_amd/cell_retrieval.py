@@ -134,9 +134,10 @@ class CellRetrievalNetwork(PicklableModule):
                                     class_idx=class_idx, color_idx=color_idx, tuning=self.tuning,
                                     overflow_flag=self._overflow_word() if (precision or self.precision) == "f16x3" else None)
 
-    _GUARD_BITS = ("bits 0-2 = SA level 1-3 edge inputs, 3 = SA output rows, 4 = GA hidden planes, 5 = GEMM rows past fp16's "
-                   "largest value; 6 = NaN among the input points / colours; 7 = a level's activations too SMALL for the fp16 "
-                   "pieces (largest magnitude below 2^-7: their low parts would underflow)")
+    _GUARD_BITS = ("bits 0-2 = SA level 1-3 edge inputs, 3 = SA output rows, 4 = GA hidden planes, 5 = GEMM rows (PointNet2 "
+                   "features, kNN edge rows) past fp16's largest value; 6 = NaN among the input points / colours; 7 = a stage's "
+                   "activations too SMALL for the fp16 pieces (SA levels, GA hidden planes, PointNet2 features, kNN edge rows: "
+                   "largest magnitude below 2^-7, their low parts would underflow)")
 
     def _with_guard(self, run):
         """run() -> result of an encode on the CURRENT precision.  On the f16x3 path the sticky guard word is read after the

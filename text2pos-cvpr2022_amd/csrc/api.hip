@@ -384,6 +384,7 @@ int encode_chunk(const float* xyz, const float* rgb, const float* center, const 
         if (cfg.precision == 1) {
             p.out_hi = gh_hi;
             p.out_lo = gh_lo;
+            p.amax_out = gslot(G_GA_H);
         }
         p.ldo = 512;
         p.relu = 1;
@@ -408,8 +409,8 @@ int encode_chunk(const float* xyz, const float* rgb, const float* center, const 
     }
     // ---- PointNet2 heads + ObjectEncoder ------------------------------------------------------------------------
     if (cfg.precision == 1 && W.lin1_x3 && W.lin2_x3) {
-        T2P_TRY(launch_gemm_x3(ws.f0, 1024, W.lin1_x3, W.lin1_scale, W.lin1_b, ws.f1, 512, 0, n, 1024, 512, 1, st, nullptr, 0, gslot(G_GEMM_IN)));
-        T2P_TRY(launch_gemm_x3(ws.f1, 512, W.lin2_x3, W.lin2_scale, W.lin2_b, ws.f2, 256, 0, n, 512, 256, 1, st, nullptr, 0, gslot(G_GEMM_IN)));
+        T2P_TRY(launch_gemm_x3(ws.f0, 1024, W.lin1_x3, W.lin1_scale, W.lin1_b, ws.f1, 512, 0, n, 1024, 512, 1, st, nullptr, 0, gslot(G_PN_F0)));
+        T2P_TRY(launch_gemm_x3(ws.f1, 512, W.lin2_x3, W.lin2_scale, W.lin2_b, ws.f2, 256, 0, n, 512, 256, 1, st, nullptr, 0, gslot(G_PN_F1)));
     } else {
         T2P_TRY(launch_gemm(ws.f0, 1024, W.lin1_w, W.lin1_b, ws.f1, 512, 0, n, 1024, 512, 1, st));
         T2P_TRY(launch_gemm(ws.f1, 512, W.lin2_w, W.lin2_b, ws.f2, 256, 0, n, 512, 256, 1, st));
@@ -426,7 +427,8 @@ int encode_chunk(const float* xyz, const float* rgb, const float* center, const 
         const int kin = cfg.pointnet_features == 0 ? 1024 : (cfg.pointnet_features == 1 ? 512 : 256);
         // mlp_pointnet into P (scratch), then F.normalize into the concat slot
         if (cfg.precision == 1 && W.pn_x3)
-            T2P_TRY(launch_gemm_x3(fin, kin, W.pn_x3, W.pn_scale, W.pn_b, ws.P, D, 0, n, kin, D, 1, st, nullptr, 0, gslot(G_GEMM_IN)));
+            T2P_TRY(launch_gemm_x3(fin, kin, W.pn_x3, W.pn_scale, W.pn_b, ws.P, D, 0, n, kin, D, 1, st, nullptr, 0,
+                                          gslot(G_PN_F0 + cfg.pointnet_features)));
         else
             T2P_TRY(launch_gemm(fin, kin, W.pn_w, W.pn_b, ws.P, D, 0, n, kin, D, 1, st));
         T2P_TRY(launch_rownorm(ws.P, D, n, D, ws.cat, ldcat, slot * D, st));
@@ -473,7 +475,7 @@ int encode_chunk(const float* xyz, const float* rgb, const float* center, const 
         p.Bc = ws.P;
         p.W = W.g_w2;
         p.W_x3 = cfg.precision == 1 ? W.g_w2_x3 : nullptr;   // f16x3 image of layer 2 (absent: fp32 MFMA)
-        p.amax_out = gslot(G_GEMM_IN);                                      // (here: the rows this kernel splits itself)
+        p.amax_out = gslot(G_EDGE);                                         // (here: the rows this kernel splits itself)
         p.ldw = D;
         p.bias = W.g_b2;
         p.out = ws.x1;

@@ -498,7 +498,9 @@ __global__ void k_cell_index(const int32_t* __restrict__ cell_ptr, int n_cells, 
 // fp16-range verdict of one chunk (t2p_common.h GuardSlot): bit 0..2 = SA level l may have staged relu(A_j - B_i) past
 // fp16's largest finite value, bit 3 = an SA output row (split by the next dense kernel) did, bit 4 = the GA hidden planes
 // may have (bound ||W1||_1 max(F_3, 1) + max|b1|), bit 5 = a row of the LDS-tiled GEMMs did, bit 6 = NaN in the input points / colours,
-// bit 7 = an SA level's hidden activations or outputs are all below kGuardTiny (too small for the fp16 pieces)
+// bit 7 = a stage's activations are all below kGuardTiny (too small for the fp16 pieces): an SA level's hidden activations or
+// outputs, GA layer 1's output, the PointNet2 features f0 / f1 / f2 or the kNN edge rows (slots G_GA_H .. G_EDGE; bit 5 is
+// their high side, bit 4 GA layer 1's)
 __global__ void k_guard_check(const uint32_t* __restrict__ guard, int32_t* flag, GuardBounds gb) {
     if (threadIdx.x != 0) return;
     const float lim = 65504.f;
@@ -521,6 +523,12 @@ __global__ void k_guard_check(const uint32_t* __restrict__ guard, int32_t* flag,
     }
     if (!(fmaxf(__uint_as_float(guard[G_F3]), 1.f) * gb.ga1_l1 + gb.ga1_bmax < lim)) code |= 16;
     if (!(__uint_as_float(guard[G_GEMM_IN]) < lim)) code |= 32;
+    // exact maxima of the stages behind the SA levels (0 = the stage did not run: nothing to judge)
+    for (int i = G_GA_H; i <= G_EDGE; i++) {
+        const float m = __uint_as_float(guard[i]);
+        if (!(m < lim)) code |= i == G_GA_H ? 16 : 32;
+        if (m > 0.f && m < kGuardTiny) code |= 128;
+    }
     if (code != 0) atomicOr(flag, code);
 }
 

@@ -99,7 +99,11 @@ enum GuardSlot {
     G_F1 = 6, G_F2 = 7, G_F3 = 8,  // SA outputs F_l = the rows the dense weight-stationary kernels split on the fly; exact
                                    // maxima, reported by the SA kernels (their xyz tail is bounded by 1).  GA layer 1's
                                    // output (handed on as fp16 planes) is bounded by ||W||_1 max(F_3, 1) + max|b|
-    G_GEMM_IN = 9,    // rows split on the fly by the LDS-tiled f16x3 GEMM (f0, f1, cat, emb)
+    G_GEMM_IN = 9,    // unit-norm rows split on the fly by the LDS-tiled f16x3 GEMM (cat, emb): high side only
+    // exact maxima of the stages that are split on the fly downstream of the SA levels, one slot each (a warm stage must not
+    // hide a cold one): GA layer 1's output (the fp16 planes GA2 reads), the PointNet2 features f0 / f1 / f2 as the LDS-tiled
+    // f16x3 GEMMs split them (lin1, lin2, mlp_pointnet), and the kNN edge rows relu(P_i + Q_j) of DynamicEdgeConv
+    G_GA_H = 10, G_PN_F0 = 11, G_PN_F1 = 12, G_PN_F2 = 13, G_EDGE = 14,
     G_SLOTS = 16
 };
 struct GuardBounds {   // host-side norms of the folded weights (packing.py), passed by value to k_guard_check
@@ -109,23 +113,17 @@ struct GuardBounds {   // host-side norms of the folded weights (packing.py), pa
     float ga1_l1;       // GA layer 1: max over columns of sum_k |W[k][c]|
     float ga1_bmax;
 };
-// Magnitudes below kGuardFloor are never published (no atomic traffic in the normal case: activations of a trained,
-// batch-normalised network are O(1..100)); k_guard_check counts an unpublished word as kGuardFloor.
+// High side of SA levels 2 and 3: k_guard_check counts the point table's maximum as at least kGuardFloor (a margin far above
+// the activations of a trained, batch-normalised network, O(1..100)).
 constexpr float kGuardFloor = 16384.f;
 // Low side: fp16 pieces hi = fp16(v), lo = fp16(v - hi) carry an ABSOLUTE error of ~2^-25 (fp16's subnormal spacing) once
 // |v| < 2^-3; harmless while a layer's largest activations are O(1), but a layer whose LARGEST magnitude is below 2^-7 keeps
-// fewer than ~18 bits of its own scale (and below 2^-14 the hi piece itself goes subnormal).  k_guard_check sets bit 7 then.
+// fewer than ~18 bits of its own scale (and below 2^-14 the hi piece itself goes subnormal).  k_guard_check sets bit 7 then,
+// for every stage with an exact maximum (SA outputs, the layer-1 tables of SA levels 2 and 3, and slots G_GA_H .. G_EDGE).
 constexpr float kGuardTiny = 0.0078125f;
 #ifdef __HIPCC__
 // m >= 0 (a magnitude; NaN compares false everywhere and is caught by the table producers' own inputs); at most one
-// atomic per wavefront, and only when some lane saw a magnitude at or above the floor
-__device__ __forceinline__ void guard_publish(uint32_t* slot, float m) {
-    if (slot == nullptr) return;
-    if (!__any(m >= kGuardFloor)) return;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-    if ((threadIdx.x & 63) == 0) atomicMax(slot, __float_as_uint(m));
-}
+// atomic per wavefront, and only when some lane saw a magnitude above the floor
 __device__ __forceinline__ void guard_publish_above(uint32_t* slot, float m, float floor_) {
     if (slot == nullptr) return;
     if (!__any(m > floor_)) return;

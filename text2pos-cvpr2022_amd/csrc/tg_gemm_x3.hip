@@ -145,7 +145,8 @@ __global__ __launch_bounds__(256, 2) void k_gemm_x3(const float* __restrict__ A,
         __syncthreads();
     }
 
-    if (blockIdx.y == 0) guard_publish(amax_in, gmax);  // every column block stages the same rows
+    // every column block stages the same rows; exact maximum (high and low side of the guard), once per wave
+    if (blockIdx.y == 0) guard_publish_exact(amax_in, gmax);
 #pragma unroll
     for (int j = 0; j < MI; j++) {
         const int col = n0 + wc * (TS / 2) + j * 32 + l31;

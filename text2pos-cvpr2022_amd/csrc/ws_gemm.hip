@@ -126,8 +126,8 @@ __global__ __launch_bounds__((WN > 4 || W8) ? 512 : 256, (WN > 4 || W8) ? 2 : 1)
     for (int nt = 0; nt < C::NTW; nt++) bias[nt] = p.bias ? p.bias[ncol0 + nt * 32 + l31] : 0.f;
 
     // fp16-range guard (f16x3 only, t2p_common.h): the rows these kernels split while staging are SA outputs, whose
-    // magnitude the SA kernels report; here only the magnitude of the layer-1 point tables (A_2, A_3) is published, per
-    // batch, by the epilogue (guard_publish: one ballot, no atomic below the floor)
+    // magnitude the SA kernels report; here the exact largest magnitude of what the epilogue stores (the layer-1 point tables
+    // A_2, A_3 and GA layer 1's split output) and of the kNN edge rows split while staging is published, once per wave
     const int k_live = p.k_live > 0 ? p.k_live : K;   // pad columns of SA output rows are never written: do not read them
     f32x4 sa[C::ITERS];                  // staged source rows (in flight behind the MFMA block)
     f32x4 sb[C::EDGE ? C::ITERS : 1];    // staged destination terms (kNN edge mode)
@@ -188,7 +188,7 @@ __global__ __launch_bounds__((WN > 4 || W8) ? 512 : 256, (WN > 4 || W8) ? 2 : 1)
                 *(f32x4*)(hidh + buf * 2 * C::PLANE + pl * C::PLANE + prow * C::LDHH + c8 * 8) = sa[it];
             } else if constexpr (X3) {
                 _Float16* dsth = hidh + buf * 2 * C::PLANE;
-                if constexpr (C::EDGE)   // fp16-range guard: the kNN edge rows relu(P_i + Q_j) are split here and nowhere reported
+                if constexpr (C::EDGE)   // fp16-range guard: the kNN edge rows relu(P_i + Q_j) are split here
                     gmax_edge = fmaxf(fmaxf(gmax_edge, fmaxf(v[0], v[1])), fmaxf(v[2], v[3]));
                 const fp16x2 h01 = cvt_pk_f16(v[0], v[1]), h23 = cvt_pk_f16(v[2], v[3]);
                 const fp16x2 l01 = cvt_pk_f16((v[0] - (float)h01[0]) * 2048.f, (v[1] - (float)h01[1]) * 2048.f);
@@ -325,10 +325,8 @@ __global__ __launch_bounds__((WN > 4 || W8) ? 512 : 256, (WN > 4 || W8) ? 2 : 1)
                             const int r = trow0 + 4 * h + rr;
                             float v = acc[rt][nt][e];
                             if (p.relu) v = fmaxf(v, 0.f);
-                            // (rows past M hold the bias only).  Not for the split-output form (GA layer 1): that kernel sits
-                            // at the register limit with a store-bound epilogue (a running maximum cost 14 %); its output
-                            // is bounded from its input's magnitude instead (k_guard_check)
-                            if constexpr (X3 && SPLIT_IO != 2) gmax_out = fmaxf(gmax_out, fabsf(v));
+                            // (rows past M hold the bias only)
+                            if constexpr (X3) gmax_out = fmaxf(gmax_out, fabsf(v));
                             if constexpr (SPLIT_IO == 2) {  // hand the activations on already split into fp16 hi / lo
                                 const fp16x2 hv = cvt_pk_f16(v, 0.f);
                                 const fp16x2 lv = cvt_pk_f16((v - (float)hv[0]) * 2048.f, 0.f);
@@ -360,12 +358,12 @@ __global__ __launch_bounds__((WN > 4 || W8) ? 512 : 256, (WN > 4 || W8) ? 2 : 1)
             };
             if (n_rows == C::TR) epilogue(std::true_type{});
             else epilogue(std::false_type{});
-            if constexpr (X3 && MODE == WS_DENSE_STORE && SPLIT_IO != 2) gmax_all = fmaxf(gmax_all, gmax_out);
+            if constexpr (X3 && MODE == WS_DENSE_STORE) gmax_all = fmaxf(gmax_all, gmax_out);
             if (gn < p.n_groups) stage_write((i + 1) & 1);
             __syncthreads();
         }
         // the table's exact largest magnitude, once per wave (high AND low side of the guard)
-        if constexpr (X3 && MODE == WS_DENSE_STORE && SPLIT_IO != 2) guard_publish_exact(p.amax_out, gmax_all);
+        if constexpr (X3 && MODE == WS_DENSE_STORE) guard_publish_exact(p.amax_out, gmax_all);
     } else {
         // ---- kNN edge stream: a group = 32 destination objects, rows = their valid neighbours ----------------------
         for (int64_t g = stream; g < p.n_groups; g += n_streams) {
@@ -472,7 +470,7 @@ __global__ __launch_bounds__((WN > 4 || W8) ? 512 : 256, (WN > 4 || W8) ? 2 : 1)
             }
             __syncthreads();
         }
-        if constexpr (X3) guard_publish(p.amax_out, gmax_edge);
+        if constexpr (X3) guard_publish_exact(p.amax_out, gmax_edge);
     }
 }
 

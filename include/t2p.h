@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define T2P_ABI_VERSION 27
+#define T2P_ABI_VERSION 28
 #define T2P_DEFAULT_CHUNK_OBJECTS 65000 /* t2p_cell_config.chunk_objects == 0 */
 #define T2P_MAX_CHUNK_OBJECTS 65535     /* 32-bit table offsets / 16-bit local indices: chunk_objects and the largest single
                                            cell may not exceed it (T2P_E_ARG otherwise).  The caller-provided workspace holds
@@ -143,7 +143,8 @@ typedef struct t2p_cell_weights {
 } t2p_cell_weights;
 
 typedef struct t2p_cell_config {
-    int32_t n_pts;             /* points per object after T.FixedPoints (training/args.py:53); 256 */
+    int32_t n_pts;             /* points per object after T.FixedPoints (args.pointnet_numpoints, training/args.py:53): 8 to 256
+                                  (default 256); outside that range T2P_E_UNSUPPORTED */
     int32_t embed_dim;         /* D; 256 */
     int32_t pointnet_features; /* 0 | 1 | 2 (training/args.py:58) */
     int32_t use_class;         /* "class" / "color" / "position" in args.use_features (training/args.py:21) */

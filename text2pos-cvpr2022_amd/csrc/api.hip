@@ -125,6 +125,7 @@ struct Bump {
 // Level geometry for n_pts points: dense/centroid counts, feature widths, hidden widths.
 struct Geo {
     int nd[3], nc[3];
+    int gp;   // GA max group: SA level 3 writes gp rows per object (the next power of two >= nc[2]; rows past nc[2] repeat the last)
     static constexpr int H[3] = {32, 128, 256};
     static constexpr int C[3] = {64, 128, 256};
     static constexpr int LD[3] = {96, 160, 288};  // SA output row = [C | xyz 0 | 28 pad columns: zero at level 3, never written at levels 1-2 (their readers mask them: k_live)]: K % 32 == 0 for the next GEMM
@@ -134,6 +135,13 @@ struct Geo {
             nc[l] = (nd[l] + 1) / 2;
             if (l < 2) nd[l + 1] = nc[l];
         }
+        gp = 1;
+        while (gp < nc[2]) gp *= 2;
+    }
+    // f16x3: the specialised SA kernels (LDS centroid table) are built for the level shapes of 256 points per object
+    bool specialised(int l) const {
+        static constexpr int ND[3] = {256, 128, 64}, NC[3] = {128, 64, 32};
+        return nd[l] == ND[l] && nc[l] == NC[l];
     }
 };
 constexpr int Geo::H[3];
@@ -147,6 +155,9 @@ struct CellWs {
     int32_t *knn, *seg_ptr, *first, *prefix[3], *bounds[3];
     uint32_t* guard;  // [G_SLOTS] fp16-range guard words of the chunk (t2p_common.h)
 };
+
+// rows of GA layer 1's output: n objects x gp rows, rounded up to the 32-row tiles GA layer 2 reads
+int64_t gh_rows(int64_t n, const Geo& g) { return (n * g.gp + 31) / 32 * 32; }
 
 // Carve the per-chunk workspace (n objects, nb cells).  With base == nullptr this only measures.
 size_t carve(Bump& b, int64_t n, int64_t nb, const t2p_cell_config& cfg, CellWs* ws) {
@@ -164,9 +175,9 @@ size_t carve(Bump& b, int64_t n, int64_t nb, const t2p_cell_config& cfg, CellWs*
         w.gt.n_rows[l] = b.take<uint16_t>(n);
         w.A[l] = b.take<float>(n * g.nd[l] * Geo::H[l]);
         w.B[l] = b.take<float>(n * g.nc[l] * Geo::H[l]);
-        w.F[l] = b.take<float>(n * g.nc[l] * Geo::LD[l]);
+        w.F[l] = b.take<float>(n * (l == 2 ? g.gp : g.nc[l]) * Geo::LD[l]);
     }
-    w.gh = b.take<float>(n * g.nc[2] * 512);
+    w.gh = b.take<float>(gh_rows(n, g) * 512);
     w.f0 = b.take<float>(n * 1024);
     w.f1 = b.take<float>(n * 512);
     w.f2 = b.take<float>(n * 256);
@@ -197,8 +208,8 @@ int default_chunk(const t2p_cell_config& cfg) { return cfg.chunk_objects > 0 ? c
 
 int check_cfg(const t2p_cell_config* cfg) {
     T2P_CHECK_ARG(cfg != nullptr, "encode_cells: cfg is NULL");
-    if (cfg->n_pts != 256) {
-        set_error("encode_cells: n_pts=%d not built (256; the GA max-pool tile assumes 32 points per object)", cfg->n_pts);
+    if (cfg->n_pts < 8 || cfg->n_pts > 256) {
+        set_error("encode_cells: n_pts=%d not built (8 <= n_pts <= 256 points per object)", cfg->n_pts);
         return T2P_E_UNSUPPORTED;
     }
     if (cfg->objects_only) {
@@ -259,12 +270,13 @@ int encode_chunk(const float* xyz, const float* rgb, const float* center, const 
     gbounds.a1_bmax = W.sa_b1_absmax;
     gbounds.ga1_l1 = W.ga_w1_l1;
     gbounds.ga1_bmax = W.ga_b1_absmax;
-    // f16x3: the SA kernels build their centroid tables B_i = W1p pos_i in LDS (sa_points.hip, sa_rows.hip, sa3.hip); the HBM
-    // tables B_l are then neither written nor read.  The fp32 kernels (ws_sa.hip) gather all three from HBM.
-    const bool lds_btab = cfg.precision == 1;
-    const bool lds_btab0 = lds_btab;
+    // f16x3: the SA kernels of the level shapes of 256 points build their centroid tables B_i = W1p pos_i in LDS (sa_points.hip,
+    // sa_rows.hip, sa3.hip); the HBM tables B_l are then neither written nor read.  The fp32 kernels (ws_sa.hip) and the f16x3
+    // kernel of the other shapes (sa_x3.hip) gather theirs from HBM.
+    bool lds_btab[3];
+    for (int l = 0; l < 3; l++) lds_btab[l] = cfg.precision == 1 && g.specialised(l);
     // level 0 runs on sa_points.hip, which computes layer 1 per edge from the points themselves: no point table A_1 either
-    const bool sa1_points = lds_btab0 && cfg.n_pts == 256;
+    const bool sa1_points = lds_btab[0];
     T2P_TRY(launch_cell_index(cell_ptr_dev, (int)nb, o_lo, ws.seg_ptr, ws.first, st, guard));
     // models/object_encoder.py:86: the PointNet++ only runs when the "class" feature does not come from class_embedding
     const bool run_pointnet = cfg.use_class && !cfg.class_embed;
@@ -279,13 +291,14 @@ int encode_chunk(const float* xyz, const float* rgb, const float* center, const 
         // [xyz | 0] tail of the F_l rows) for every level, and the K = 6 point table A_1 of level 0
         for (int l = 0; l < 3; l++) {
             const int cf = l == 0 ? 3 : Geo::C[l - 1];
-            gt.B[l] = (l > 0 ? lds_btab : lds_btab0) ? nullptr : ws.B[l];
+            gt.B[l] = lds_btab[l] ? nullptr : ws.B[l];
             gt.wp[l] = W.sa_w1[l] + (size_t)cf * Geo::H[l];
             gt.H[l] = Geo::H[l];
             gt.tail[l] = ws.F[l];
             gt.ld_tail[l] = Geo::LD[l];
             gt.tail_col0[l] = Geo::C[l];
         }
+        gt.tail_rows[2] = g.gp;
         gt.A1 = sa1_points ? nullptr : ws.A[0];
         gt.w1 = W.sa_w1[0];
         gt.b1 = W.sa_b1[0];
@@ -305,7 +318,9 @@ int encode_chunk(const float* xyz, const float* rgb, const float* center, const 
             bp[l].prefix_ws = ws.prefix[l];
             bp[l].bounds_ws = ws.bounds[l];
             bp[l].W_x3 = cfg.precision == 1 ? W.sa_w2_x3[l] : nullptr;
-            bp[l].wp = (l > 0 ? lds_btab : lds_btab0) ? W.sa_w1[l] : nullptr;   // (non-null = LDS centroid table: selects the launch shape)
+            bp[l].wp = lds_btab[l] ? W.sa_w1[l] : nullptr;   // (non-null = LDS centroid table: selects the launch shape)
+            bp[l].n_dense = g.nd[l];
+            bp[l].n_cent = g.nc[l];
         }
         bp[0].w1 = sa1_points ? W.sa_w1[0] : nullptr;
         T2P_TRY(launch_sa_balance_levels(bp, Geo::H, Geo::C, st));
@@ -339,7 +354,7 @@ int encode_chunk(const float* xyz, const float* rgb, const float* center, const 
         SaParams p{};
         p.A = ws.A[l];
         p.Bc = ws.B[l];
-        p.wp = (l > 0 ? lds_btab : lds_btab0) ? W.sa_w1[l] + (size_t)cf * Geo::H[l] : nullptr;
+        p.wp = lds_btab[l] ? W.sa_w1[l] + (size_t)cf * Geo::H[l] : nullptr;
         p.W = W.sa_w2[l];
         p.W_x3 = cfg.precision == 1 ? W.sa_w2_x3[l] : nullptr;
         p.bias = cfg.precision == 1 ? W.sa_b2_x3[l] : W.sa_b2[l];
@@ -365,9 +380,10 @@ int encode_chunk(const float* xyz, const float* rgb, const float* center, const 
         p.bounds_ws = ws.bounds[l];
         p.balanced = 1;
         p.amax_out = gslot(G_F1 + l);
+        if (l == 2) p.out_rows = g.gp;
         T2P_TRY(launch_ws_sa(H, C, p, st));
     }
-    // ---- global abstraction: [x | pos] -> 512 -> 1024, max over the object's 32 points ------------------------
+    // ---- global abstraction: [x | pos] -> 512 -> 1024, max over the object's nc[2] points (gp rows, the padding repeats one) ---
     {
         WsParams p{};
         p.A = ws.F[2];
@@ -380,7 +396,7 @@ int encode_chunk(const float* xyz, const float* rgb, const float* center, const 
         // f16x3: GA1 hands its ReLU output to GA2 already split into fp16 hi / lo planes (same bytes as fp32), so the
         // eight column-slice workgroups of GA2 stage it with plain 16-byte copies instead of re-splitting it 8 times
         _Float16* gh_hi = (_Float16*)ws.gh;
-        _Float16* gh_lo = gh_hi + (size_t)n * g.nc[2] * 512;
+        _Float16* gh_lo = gh_hi + (size_t)gh_rows(n, g) * 512;
         if (cfg.precision == 1) {
             p.out_hi = gh_hi;
             p.out_lo = gh_lo;
@@ -388,7 +404,7 @@ int encode_chunk(const float* xyz, const float* rgb, const float* center, const 
         }
         p.ldo = 512;
         p.relu = 1;
-        p.M = n * g.nc[2];
+        p.M = n * g.gp;
         T2P_TRY(launch_ws(WS_DENSE_STORE, Geo::LD[2] - (cfg.precision == 1 ? 16 : 0), 512, p, st));
         WsParams q{};
         q.A = ws.gh;
@@ -404,7 +420,8 @@ int encode_chunk(const float* xyz, const float* rgb, const float* center, const 
         q.out = ws.f0;
         q.ldo = 1024;
         q.relu = 1;
-        q.M = n * g.nc[2];
+        q.M = n * g.gp;
+        q.group_rows = g.gp;
         T2P_TRY(launch_ws(WS_DENSE_GROUPMAX, 512, 1024, q, st));
     }
     // ---- PointNet2 heads + ObjectEncoder ------------------------------------------------------------------------
@@ -505,9 +522,15 @@ int encode_chunk(const float* xyz, const float* rgb, const float* center, const 
             T2P_TRY(copy_trace(tr->cnt[l] ? tr->cnt[l] + trace_obj0 * g.nc[l] : nullptr, ws.gt.cnt[l],
                                (size_t)n * g.nc[l], st));
             if (tr->sa_out[l] && n > 0) {   // [features | xyz 0] of every row; the pad columns behind are left as the caller set them
-                hipError_t e = hipMemcpy2DAsync(tr->sa_out[l] + trace_obj0 * g.nc[l] * Geo::LD[l], Geo::LD[l] * sizeof(float), ws.F[l],
-                                                Geo::LD[l] * sizeof(float), (Geo::C[l] + 4) * sizeof(float), (size_t)n * g.nc[l],
-                                                hipMemcpyDeviceToDevice, st);
+                const int rows = l == 2 ? g.gp : g.nc[l];   // (level 3: the gp - nc[2] padding rows of an object stay behind)
+                const size_t ld = Geo::LD[l] * sizeof(float);
+                hipError_t e = hipSuccess;
+                if (rows == g.nc[l])
+                    e = hipMemcpy2DAsync(tr->sa_out[l] + trace_obj0 * g.nc[l] * Geo::LD[l], ld, ws.F[l], ld, (Geo::C[l] + 4) * sizeof(float),
+                                         (size_t)n * g.nc[l], hipMemcpyDeviceToDevice, st);
+                for (int c = 0; rows != g.nc[l] && c < g.nc[l] && e == hipSuccess; c++)   // centroid c of every object
+                    e = hipMemcpy2DAsync(tr->sa_out[l] + (trace_obj0 * g.nc[l] + c) * Geo::LD[l], g.nc[l] * ld, ws.F[l] + (size_t)c * Geo::LD[l],
+                                         rows * ld, (Geo::C[l] + 4) * sizeof(float), (size_t)n, hipMemcpyDeviceToDevice, st);
                 if (e != hipSuccess) {
                     set_error("encode_cells: trace copy failed: %s", hipGetErrorString(e));
                     return (int)e;

@@ -1,4 +1,5 @@
-// GlobalAbstraction layer 2 + global max pool (512 -> 1024, max over each object's 32 points), f16x3 path.
+// GlobalAbstraction layer 2 + global max pool (512 -> 1024, max over each object's 32 points - or over groups of 1 .. 16 rows when
+// the objects have fewer than 256 points), f16x3 path.
 // (reference: GlobalAbstractionLayer.forward, models/pointcloud/pointnet2.py:45-49)
 //
 // The generic weight-stationary kernel (ws_gemm.hip) needs 256 registers per lane for the hi/lo weight image of a
@@ -31,6 +32,8 @@ constexpr int XCH_FLOATS = 4 * 16 * 64;  // exchange area: 4 column blocks x 16 
 constexpr size_t kLds = (size_t)2 * TILE_HALVES * 2 + (size_t)XCH_FLOATS * 4;
 constexpr int CHUNKS = (2 * 32 * (K / 8)) / NT;  // 16-byte chunks staged per thread and tile (= 8)
 
+// GP: rows per max group (1, 2, 4, 8, 16, 32): a 32-row tile holds 32 / GP objects (fewer than 32 points per object at SA level 3)
+template <int GP>
 __global__ __launch_bounds__(NT, 2) void k_ga2(WsParams p, int n_slices) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     _Float16* tile = (_Float16*)lds;                  // [2][hi plane | lo plane]
@@ -146,7 +149,7 @@ __global__ __launch_bounds__(NT, 2) void k_ga2(WsParams p, int n_slices) {
                 for (int v = 0; v < 4; v++) x[(4 * b + v) * 64] = acc[b][v];
         }
         __syncthreads();
-        if (!sender) {
+        if (!sender && GP == 32) {
             // partner's partial + bias, ReLU (= starting the max at 0), max over the 32 rows of the object: per column block
             // over its two row blocks x four rows in this lane, then over the four lane quarters
 #pragma unroll
@@ -160,17 +163,37 @@ __global__ __launch_bounds__(NT, 2) void k_ga2(WsParams p, int n_slices) {
                 m = fmaxf(m, __shfl_xor(m, 32, 64));
                 if (q16 == 0) p.out[g * (int64_t)p.ldo + ncol0 + 16 * cb + i16] = m;
             }
+        } else if (!sender) {
+            // groups of GP rows: row 16 rb + 4 q16 + v of the tile belongs to object 32 / GP * g + (16 rb + 4 q16 + v) / GP.  The lane's
+            // four rows v reduce in registers (GP >= 4: one group; GP = 2: two; GP = 1: four), the lane quarters by shuffles (GP = 8:
+            // pairs of quarters, GP = 16: all four); the rows of a tile past the last object are never stored
+            constexpr int VG = GP < 4 ? GP : 4;   // rows of one group inside the lane
+            const int64_t n_obj = p.M / GP;
+#pragma unroll
+            for (int cb = 0; cb < 2; cb++)
+#pragma unroll
+                for (int rb = 0; rb < 2; rb++)
+#pragma unroll
+                    for (int v0 = 0; v0 < 4; v0 += VG) {
+                        float m = 0.f;
+#pragma unroll
+                        for (int v = v0; v < v0 + VG; v++)
+                            m = fmaxf(m, (acc[2 * rb + cb][v] + x[(4 * (2 * rb + cb) + v) * 64]) + bias2[cb]);
+                        if constexpr (GP >= 8) m = fmaxf(m, __shfl_xor(m, 16, 64));
+                        if constexpr (GP >= 16) m = fmaxf(m, __shfl_xor(m, 32, 64));
+                        const int row = 16 * rb + 4 * q16 + v0;
+                        const int64_t obj = g * (32 / GP) + row / GP;
+                        if (row % GP == 0 && obj < n_obj) p.out[obj * (int64_t)p.ldo + ncol0 + 16 * cb + i16] = m;
+                    }
         }
     }
 }
 
-}  // namespace
-
-// out[M/32][ldo] (columns [0, 1024)) = max over each 32-row group of relu(A W + b); A as fp16 hi / lo planes [M][lda]
-int launch_ga2(const WsParams& p_in, hipStream_t st) {
-    T2P_TRY(reserve_lds((const void*)k_ga2, kLds, "ga2"));
+template <int GP>
+int launch_ga2_gp(const WsParams& p_in, hipStream_t st) {
+    T2P_TRY(reserve_lds((const void*)k_ga2<GP>, kLds, "ga2"));
     WsParams p = p_in;
-    p.n_groups = p.M / 32;
+    p.n_groups = (p.M + 31) / 32;   // 32-row tiles (GP < 32: the planes hold whole tiles, rows past M are read, not stored)
     if (p.n_groups <= 0) return 0;
     const int n_slices = 1024 / NW;
     int64_t streams = matrix_wgs() / n_slices;
@@ -178,9 +201,26 @@ int launch_ga2(const WsParams& p_in, hipStream_t st) {
     if (streams > p.n_groups) streams = p.n_groups;
     if (streams >= 8) streams -= streams % 8;
     ProfScope ps_("ws_groupmax_k512_n1024", st);
-    T2P_REPEAT(ps_) hipLaunchKernelGGL(k_ga2, dim3((unsigned)(streams * n_slices)), dim3(NT), kLds, st, p, n_slices);
+    T2P_REPEAT(ps_) hipLaunchKernelGGL(k_ga2<GP>, dim3((unsigned)(streams * n_slices)), dim3(NT), kLds, st, p, n_slices);
     T2P_CHECK_LAUNCH("ga2");
     return 0;
+}
+
+}  // namespace
+
+// out[M/GP][ldo] (columns [0, 1024)) = max over each GP-row group of relu(A W + b), GP = p.group_rows (0 = 32); A as fp16 hi / lo
+// planes [rows][lda] with rows = M rounded up to a multiple of 32
+int launch_ga2(const WsParams& p, hipStream_t st) {
+    switch (p.group_rows > 0 ? p.group_rows : 32) {
+        case 32: return launch_ga2_gp<32>(p, st);
+        case 16: return launch_ga2_gp<16>(p, st);
+        case 8: return launch_ga2_gp<8>(p, st);
+        case 4: return launch_ga2_gp<4>(p, st);
+        case 2: return launch_ga2_gp<2>(p, st);
+        case 1: return launch_ga2_gp<1>(p, st);
+    }
+    set_error("ga2: group_rows=%d (1, 2, 4, 8, 16 or 32)", p.group_rows);
+    return T2P_E_UNSUPPORTED;
 }
 
 }  // namespace t2p

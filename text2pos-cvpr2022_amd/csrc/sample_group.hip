@@ -280,8 +280,15 @@ __device__ void level_fast(const float* px, const float* py, const float* pz, in
 // 16-byte stores.  Same arithmetic order as the stand-alone kernel.
 __device__ __attribute__((noinline)) void emit_centroid_table(const float* qx, const float* qy, const float* qz, int n_c,
                                                     const float* __restrict__ wp, int H, float* __restrict__ out,
-                                                    float* __restrict__ tail, int ld_tail, int tail_col0, int tail_quads) {
+                                                    float* __restrict__ tail, int ld_tail, int tail_col0, int tail_quads,
+                                                    int tail_rows) {
     const int lane = threadIdx.x;
+    if (tail != nullptr) {   // padding rows n_c .. tail_rows - 1 (GA max groups): copies of the last centroid's tail
+        const int hq = lane % tail_quads;
+        for (int c = n_c + lane / tail_quads; c < tail_rows; c += 64 / tail_quads)
+            *(f32x4*)(tail + (size_t)c * ld_tail + tail_col0 + hq * 4) =
+                hq == 0 ? f32x4{qx[n_c - 1], qy[n_c - 1], qz[n_c - 1], 0.f} : f32x4{0.f, 0.f, 0.f, 0.f};
+    }
     if (out == nullptr) {   // tails only: tail_quads (1 or 8) lanes per row
         if (tail == nullptr) return;
         const int hq = lane % tail_quads;
@@ -421,10 +428,11 @@ __global__ __launch_bounds__(64, T2P_SG_WAVES) void k_sample_group(const float* 
             if (gt.B[l] != nullptr || gt.tail[l] != nullptr) {
                 const float* wpl = gt.wp[l];
                 asm volatile("" : "+s"(wpl));
+                const int t_rows = gt.tail_rows[l] > n_c ? gt.tail_rows[l] : n_c;
                 emit_centroid_table(pin[l + 1][0], pin[l + 1][1], pin[l + 1][2], n_c, wpl, gt.H[l],
                                     gt.B[l] ? gt.B[l] + o * (int64_t)n_c * gt.H[l] : nullptr,
-                                    gt.tail[l] ? gt.tail[l] + o * (int64_t)n_c * gt.ld_tail[l] : nullptr, gt.ld_tail[l],
-                                    gt.tail_col0[l], l == 2 ? 8 : 1);
+                                    gt.tail[l] ? gt.tail[l] + o * (int64_t)t_rows * gt.ld_tail[l] : nullptr, gt.ld_tail[l],
+                                    gt.tail_col0[l], l == 2 ? 8 : 1, t_rows);
             }
             uint8_t* g_sel = gt.fps_idx[l] + o * (int64_t)n_c;
             for (int i = lane; i < n_c; i += 64) g_sel[i] = sel_lds[i];

@@ -203,6 +203,7 @@ struct GroupTables {
     int H[3];
     float* tail[3];         // SA output rows F_l: the [xyz | 0] quad at column tail_col0[l]; the 28 pad columns behind it are never written, their readers mask them (WsParams::k_live) (row stride ld_tail[l])
     int ld_tail[3], tail_col0[3];
+    int tail_rows[3];       // rows per object of the tail table (0 = n_cent); rows past n_cent repeat centroid n_cent - 1
     float* A1;              // SA1 point table A_1[o*n_pts + j][H1] = W1 [rgb_j | xyz_j] + b1
     const float* w1;        // [6][H1]
     const float* b1;
@@ -298,6 +299,7 @@ struct WsParams {
     int64_t n_dst;
     int mean;               // 0 = max aggregation, 1 = mean (needs knn_k == 8)
     int knn_group;          // destinations per group: 32 (0 = 32), or 8 for calls too small to fill the CUs with 32-destination groups
+    int group_rows;         // DENSE_GROUPMAX: rows per max group, 1, 2, 4, 8, 16 or 32 (0 = 32); M is a multiple of it
 };
 int launch_ws(int mode, int K, int N, const WsParams& p, hipStream_t st);
 
@@ -328,8 +330,12 @@ struct SaParams {
     int32_t* bounds_ws;      // [n_workgroups+1] scratch (balanced contiguous object ranges)
     int balanced;            // 1: bounds_ws was filled by launch_sa_balance_levels for this level's launch shape
     uint32_t* amax_out;      // f16x3 guard (nullable): largest output magnitude (the next dense kernel splits these rows)
+    int out_rows;            // output rows per object (0 = n_cent); rows past n_cent repeat centroid n_cent - 1 (ws_sa.hip, sa_x3.hip)
 };
 int launch_ws_sa(int H, int C, const SaParams& p, hipStream_t st);
+// sa_x3.hip: f16x3 kernel of any level shape (runtime n_dense / n_cent, n_cent * C <= 8192), centroid table B from HBM (Bc)
+int launch_sa_x3(int H, int C, const SaParams& p, hipStream_t st);
+int sa_x3_launch_shape(int H, int C, int64_t n_obj, int* tile_rows, int* n_wg);
 // sa_rows.hip: row-owning f16x3 kernel of SA level 2 (H = C = 128, LDS centroid table): true when launch_ws_sa routes p there
 bool sa_rows_selected(int H, int C, const SaParams& p);
 int launch_sa_rows(int H, int C, const SaParams& p, hipStream_t st);

@@ -69,7 +69,8 @@ struct WsCfg {
     static_assert(NW % (32 * WN) == 0, "NW must split into 32-column tiles per wave");
 };
 
-template <int K, int NW, int WN, int RT, int MODE, int X3, int SPLIT_IO, int W8 = 0>
+// GP (DENSE_GROUPMAX): rows per max group, 1 .. 32 (fewer than 32 points per object at SA level 3: 32 / GP objects per 32-row tile)
+template <int K, int NW, int WN, int RT, int MODE, int X3, int SPLIT_IO, int W8 = 0, int GP = 32>
 __global__ __launch_bounds__((WN > 4 || W8) ? 512 : 256, (WN > 4 || W8) ? 2 : 1) void k_ws(WsParams p, int n_slices) {
     using C = WsCfg<K, NW, WN, RT, MODE, X3, W8>;
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -345,13 +346,36 @@ __global__ __launch_bounds__((WN > 4 || W8) ? 512 : 256, (WN > 4 || W8) ? 2 : 1)
                                 if (FULL || r < n_rows) (p.out + o0)[rr * p.ldo] = v;
                             }
                         }
-                    } else {  // max over each 32-row tile = one object (ReLU = starting the max at 0)
+                    } else if constexpr (GP == 32) {  // max over each 32-row tile = one object (ReLU = starting the max at 0)
                         float m = 0.f;
 #pragma unroll
                         for (int e = 0; e < 16; e++) m = fmaxf(m, acc[rt][nt][e]);
                         m = fmaxf(m, __shfl_xor(m, 32, 64));
                         if (h == 0 && (FULL || trow0 < n_rows))
                             p.out[(g * (C::TR / 32) + wm * RT + rt) * (int64_t)p.ldo + slice * NW + lcol] = m;
+                    } else {  // groups of GP rows: element e of lane half h holds row 8 (e >> 2) + 4 h + (e & 3) of the 32-row tile
+                        // key of a row inside the lane: GP >= 8 - its group (the halves h then meet through one shuffle); GP <= 4 -
+                        // (8 (e >> 2) + (e & 3)) / GP, the group being key + 4 h / GP
+                        constexpr int NG = 32 / GP;
+                        float mg[NG];
+#pragma unroll
+                        for (int k = 0; k < NG; k++) mg[k] = 0.f;
+#pragma unroll
+                        for (int e = 0; e < 16; e++) {
+                            const int k = (8 * (e >> 2) + (GP >= 8 ? 0 : (e & 3))) / GP;
+                            mg[k] = fmaxf(mg[k], acc[rt][nt][e]);
+                        }
+                        const int64_t obj0 = (g * C::TR + trow0) / GP, n_obj = p.M / GP;
+#pragma unroll
+                        for (int k = 0; k < NG; k++) {
+                            if constexpr (GP >= 8) {
+                                const float m = fmaxf(mg[k], __shfl_xor(mg[k], 32, 64));
+                                if (h == 0 && obj0 + k < n_obj) p.out[(obj0 + k) * (int64_t)p.ldo + slice * NW + lcol] = m;
+                            } else if ((k * GP) % 8 < 4) {   // (keys that hold rows)
+                                const int64_t obj = obj0 + k + (4 / GP) * h;
+                                if (obj < n_obj) p.out[obj * (int64_t)p.ldo + slice * NW + lcol] = mg[k];
+                            }
+                        }
                     }
                 }
             }
@@ -474,10 +498,10 @@ __global__ __launch_bounds__((WN > 4 || W8) ? 512 : 256, (WN > 4 || W8) ? 2 : 1)
     }
 }
 
-template <int K, int NW, int WN, int RT, int MODE, int X3, int SPLIT_IO, int W8 = 0>
+template <int K, int NW, int WN, int RT, int MODE, int X3, int SPLIT_IO, int W8 = 0, int GP = 32>
 int launch_cfg(const WsParams& p_in, int n_slices, hipStream_t st) {
     using C = WsCfg<K, NW, WN, RT, MODE, X3, W8>;
-    auto kern = k_ws<K, NW, WN, RT, MODE, X3, SPLIT_IO, W8>;
+    auto kern = k_ws<K, NW, WN, RT, MODE, X3, SPLIT_IO, W8, GP>;
     T2P_TRY(reserve_lds((const void*)kern, C::lds_bytes(), "ws_gemm"));
     WsParams p = p_in;
     if (MODE != WS_EDGE_KNN) p.n_groups = (p.M + C::TR - 1) / C::TR;  // dense: one group = one batch of TR rows
@@ -499,8 +523,8 @@ int launch_cfg(const WsParams& p_in, int n_slices, hipStream_t st) {
 
 }  // namespace
 
-// mode DENSE_STORE: out[M][ldo] = act(A[M][K] W + b);  DENSE_GROUPMAX: out[M/32][ldo] = max over each 32-row group
-// (M = 32 * groups);  EDGE_KNN: see WsParams.
+// mode DENSE_STORE: out[M][ldo] = act(A[M][K] W + b);  DENSE_GROUPMAX: out[M/GP][ldo] = max over each GP-row group
+// (GP = group_rows, 0 = 32; M = GP * groups);  EDGE_KNN: see WsParams.
 int launch_ga2(const WsParams& p, hipStream_t st);  // ga2.hip
 
 int launch_ws(int mode, int K, int N, const WsParams& p, hipStream_t st) {
@@ -508,7 +532,10 @@ int launch_ws(int mode, int K, int N, const WsParams& p, hipStream_t st) {
                   "ws_gemm: A must be 16-byte aligned, lda %% 4 == 0");
     const int x3 = p.W_x3 != nullptr ? 1 : 0;
     if (x3) T2P_CHECK_ARG(((uintptr_t)p.W_x3 & 15) == 0, "ws_gemm: packed f16x3 weights must be 16-byte aligned");
-    if (mode == WS_DENSE_GROUPMAX) T2P_CHECK_ARG(p.M % 32 == 0, "ws_gemm: groupmax needs M %% 32 == 0");
+    const int gp = p.group_rows > 0 ? p.group_rows : 32;
+    if (mode == WS_DENSE_GROUPMAX)
+        T2P_CHECK_ARG(gp <= 32 && (gp & (gp - 1)) == 0 && p.M % gp == 0, "ws_gemm: groupmax needs group_rows in {1, 2, 4, 8, 16, 32} "
+                      "and M %% group_rows == 0 (group_rows=%d M=%lld)", p.group_rows, (long long)p.M);
     // split_io: 0 = fp32 in / fp32 out, 1 = fp16 hi/lo planes in, 2 = fp16 hi/lo planes out (f16x3 only)
     const int split_io = p.A_hi != nullptr ? 1 : (p.out_hi != nullptr ? 2 : 0);
     T2P_CHECK_ARG(split_io == 0 || x3 == 1, "ws_gemm: split fp16 activations need the f16x3 path");
@@ -535,11 +562,21 @@ int launch_ws(int mode, int K, int N, const WsParams& p, hipStream_t st) {
         return launch_cfg<80, 128, 4, 1, WS_DENSE_STORE, 1, 0, 1>(p, 1, st);
     WS_CASE(WS_DENSE_STORE, 144, 256, 256, 8, 1, 1, 0)  // 8 waves (two per SIMD), one 32-column block per wave
     WS_CASE(WS_DENSE_STORE, 272, 512, 256, 8, 1, 1, 2)  // 8 waves: two per SIMD, two column slices instead of four
-    // GA layer 2 + max over the 32 points of an object
-    WS_CASE(WS_DENSE_GROUPMAX, 512, 1024, 128, 4, 1, 0, 0)
+    // GA layer 2 + max over the 32 points of an object (or over groups of 16 .. 1 rows: fewer than 256 points per object)
+    if (mode == WS_DENSE_GROUPMAX && K == 512 && N == 1024 && x3 == 0 && split_io == 0) {
+        switch (gp) {
+            case 32: return launch_cfg<512, 128, 4, 1, WS_DENSE_GROUPMAX, 0, 0>(p, 8, st);
+            case 16: return launch_cfg<512, 128, 4, 1, WS_DENSE_GROUPMAX, 0, 0, 0, 16>(p, 8, st);
+            case 8: return launch_cfg<512, 128, 4, 1, WS_DENSE_GROUPMAX, 0, 0, 0, 8>(p, 8, st);
+            case 4: return launch_cfg<512, 128, 4, 1, WS_DENSE_GROUPMAX, 0, 0, 0, 4>(p, 8, st);
+            case 2: return launch_cfg<512, 128, 4, 1, WS_DENSE_GROUPMAX, 0, 0, 0, 2>(p, 8, st);
+            case 1: return launch_cfg<512, 128, 4, 1, WS_DENSE_GROUPMAX, 0, 0, 0, 1>(p, 8, st);
+        }
+    }
 #if !T2P_GA2_V1
     if (mode == WS_DENSE_GROUPMAX && K == 512 && N == 1024 && x3 == 1 && split_io == 1) return launch_ga2(p, st);
 #endif
+    T2P_CHECK_ARG(mode != WS_DENSE_GROUPMAX || gp == 32, "ws_gemm: group_rows=%d is built for the fp32 and the ga2.hip paths", gp);
     WS_CASE(WS_DENSE_GROUPMAX, 512, 1024, 128, 4, 1, 1, 1)
 #undef WS_CASE
     set_error("ws_gemm: no instantiation for mode=%d K=%d N=%d x3=%d split_io=%d", mode, K, N, x3, split_io);

@@ -1,5 +1,5 @@
 // Set-abstraction edge kernel, exact-fp32 path (precision = "fp32": v_mfma_f32_32x32x2_f32 fma chains): per-edge
-// ReLU(A_j - B_i) -> layer-2 GEMM -> max per centroid, for sa1/sa2/sa3.  The f16x3 path runs on sa_points.hip / sa_rows.hip / sa3.hip (levels 1 / 2 / 3); this file keeps the exact fp32 MFMA kernels and the range balancing.
+// ReLU(A_j - B_i) -> layer-2 GEMM -> max per centroid, for sa1/sa2/sa3.  The f16x3 path runs on sa_points.hip / sa_rows.hip / sa3.hip (levels 1 / 2 / 3 of 256 points) and on sa_x3.hip (every other object size); this file keeps the exact fp32 MFMA kernels, the range balancing and the kernel selection.
 // (reference: gnn.PointConv(local_nn)(x, (pos, pos[idx]), edge_index), models/pointcloud/pointnet2.py:31-35).
 //
 // Same arithmetic and register-resident weights as ws_gemm.hip (see the design notes there); this variant removes
@@ -115,6 +115,7 @@ __global__ __launch_bounds__(NT, 2) void k_ws_sa(SaParams p) {
     const int wn = wave % WN, wm = wave / WN, h = lane >> 5, l31 = lane & 31;
     const int nc = p.n_cent;
     const int maxr = nc * 33;
+    const int rows_out = p.out_rows > 0 ? p.out_rows : nc;
 
     float w[C::NTW][C::KS];
     #pragma unroll
@@ -171,7 +172,12 @@ __global__ __launch_bounds__(NT, 2) void k_ws_sa(SaParams p) {
             for (int k = 0; k < C::ITERS; k++) m[k] = 0xFFFF;
             if (valid(it) && it.r0 + rgrp < it.n) {
                 const uint32_t off = (uint32_t)(ga + it.gi) * (uint32_t)maxr + (uint32_t)(it.r0 + rgrp);
-                m = *(const metav*)(p.rows + off);
+                if ((maxr & 3) == 0) {   // (n_cent % 4 == 0: the vector is aligned for every object)
+                    m = *(const metav*)(p.rows + off);
+                } else {
+#pragma unroll
+                    for (int k = 0; k < C::ITERS; k++) m[k] = p.rows[off + k];
+                }
             }
         };
         auto fix_meta = [&](const BatchIt& it, metav& m) {
@@ -213,12 +219,16 @@ __global__ __launch_bounds__(NT, 2) void k_ws_sa(SaParams p) {
         };
         // flush one finished object's accumulator (feature columns; the [xyz 0] quad of the rows is written
         // by the centroid-table kernel), re-zero
+        // (out_rows > n_cent: the rows behind repeat centroid n_cent - 1, the padding of the GA max groups)
         auto flush = [&](int64_t g, int abuf) {
             int* a = acc_lds + abuf * C::ACC_INTS;
-            float* o = p.out + g * nc * (int64_t)p.ldo;
+            float* o = p.out + g * rows_out * (int64_t)p.ldo;
             for (int i = tid; i < nc * N; i += NT) {
                 const int c = i / N, col = i % N;
-                o[c * (int64_t)p.ldo + col] = __int_as_float(a[i]) * p.out_scale;
+                const float v = __int_as_float(a[i]) * p.out_scale;
+                o[c * (int64_t)p.ldo + col] = v;
+                if (c == nc - 1)
+                    for (int r = nc; r < rows_out; r++) o[r * (int64_t)p.ldo + col] = v;
                 a[i] = 0;
             }
         };
@@ -366,14 +376,29 @@ int launch_sa_balance(const SaParams& p, int tile_rows, int n_wg, hipStream_t st
 }
 
 
+// f16x3: the specialised kernels take exactly the level shape of 256 points per object they are built for (with the LDS centroid
+// table); every other shape runs on sa_x3.hip, which gathers the centroid table from HBM
+enum SaKernel { SA_FP32, SA_POINTS, SA_ROWS, SA_3, SA_X3, SA_NONE };
+static SaKernel sa_pick(int H, int Cout, const SaParams& p) {
+    if (p.W_x3 == nullptr) return SA_FP32;
+    if (p.n_dense == 128 && p.n_cent == 64 && sa_rows_selected(H, Cout, p)) return SA_ROWS;
+    if (p.n_dense == 256 && p.n_cent == 128 && sa_points_selected(H, Cout, p)) return SA_POINTS;
+    if (p.n_dense == 64 && p.n_cent == 32 && sa3_selected(H, Cout, p)) return SA_3;
+    if (p.wp == nullptr) return SA_X3;
+    set_error("ws_sa: no f16x3 kernel with an LDS centroid table for H=%d C=%d n_dense=%d n_cent=%d (built: the level shapes of "
+              "256 points; other shapes gather the table from HBM: wp unset)", H, Cout, p.n_dense, p.n_cent);
+    return SA_NONE;
+}
+
 // tile rows / workgroup count of the kernel launch_ws_sa will pick for (H, Cout)
 static int sa_launch_shape(int H, int Cout, const SaParams& p, int64_t n_obj, int* tile_rows, int* n_wg) {
-    if (sa_rows_selected(H, Cout, p)) return sa_rows_launch_shape(n_obj, tile_rows, n_wg);
-    if (sa_points_selected(H, Cout, p)) return sa_points_launch_shape(n_obj, tile_rows, n_wg);
-    if (sa3_selected(H, Cout, p)) return sa3_launch_shape(n_obj, tile_rows, n_wg);
-    if (p.W_x3 != nullptr) {
-        set_error("ws_sa: no f16x3 kernel for H=%d C=%d (built: 32/64 over 256 points, 128/128, 256/256, each with the LDS centroid table)", H, Cout);
-        return T2P_E_UNSUPPORTED;
+    switch (sa_pick(H, Cout, p)) {
+        case SA_ROWS: return sa_rows_launch_shape(n_obj, tile_rows, n_wg);
+        case SA_POINTS: return sa_points_launch_shape(n_obj, tile_rows, n_wg);
+        case SA_3: return sa3_launch_shape(n_obj, tile_rows, n_wg);
+        case SA_X3: return sa_x3_launch_shape(H, Cout, n_obj, tile_rows, n_wg);
+        case SA_NONE: return T2P_E_UNSUPPORTED;
+        case SA_FP32: break;
     }
     int n = num_cus();
     if (n > n_obj) n = (int)n_obj;
@@ -405,11 +430,13 @@ int launch_ws_sa(int H, int Cout, const SaParams& p, hipStream_t st) {
     T2P_CHECK_ARG((((uintptr_t)p.A | (uintptr_t)p.Bc) & 15) == 0, "ws_sa: tables must be 16-byte aligned");
     if (p.W_x3 != nullptr) {  // f16x3 split-precision path: one kernel per level
         T2P_CHECK_ARG(((uintptr_t)p.W_x3 & 15) == 0, "ws_sa: packed f16x3 weights must be 16-byte aligned");
-        if (sa_rows_selected(H, Cout, p)) return launch_sa_rows(H, Cout, p, st);
-        if (sa_points_selected(H, Cout, p)) return launch_sa_points(H, Cout, p, st);
-        if (sa3_selected(H, Cout, p)) return launch_sa3(p, st);
-        set_error("ws_sa: no f16x3 kernel for H=%d C=%d (built: 32/64 over 256 points, 128/128, 256/256, each with the LDS centroid table)", H, Cout);
-        return T2P_E_UNSUPPORTED;
+        switch (sa_pick(H, Cout, p)) {
+            case SA_ROWS: return launch_sa_rows(H, Cout, p, st);
+            case SA_POINTS: return launch_sa_points(H, Cout, p, st);
+            case SA_3: return launch_sa3(p, st);
+            case SA_X3: return launch_sa_x3(H, Cout, p, st);
+            default: return T2P_E_UNSUPPORTED;
+        }
     } else {
         if (H == 32 && Cout == 64) return launch_sa_cfg<32, 64, 2, 2>(p, st, "ws_edge_sa_k32_n64");
         if (H == 128 && Cout == 128) return launch_sa_cfg<128, 128, 4, 1>(p, st, "ws_edge_sa_k128_n128");

@@ -196,22 +196,46 @@ class OracleCellRetrieval(nn.Module):
         xyz, rgb = torch.as_tensor(xyz).float(), torch.as_tensor(rgb).float()
         cell_ptr = [int(v) for v in cell_ptr]
         p = xyz.shape[1]
-        batches, batch = [], []
+        batches = []
         for c in range(len(cell_ptr) - 1):
             lo, hi = cell_ptr[c], cell_ptr[c + 1]
             n = hi - lo
             batches.append(gnn.Batch(x=rgb[lo:hi].reshape(n * p, 3).clone(), pos=xyz[lo:hi].reshape(n * p, 3).clone(),
                                      batch=torch.arange(n).repeat_interleave(p)))
-            batch += [c] * n
-        batch = torch.tensor(batch, dtype=torch.long)
         emb = self.object_encoder(batches, torch.as_tensor(mean_rgb), torch.as_tensor(center), trace, class_idx, color_idx)
         if trace is not None:
             trace.append(dict(object_embeddings=emb.detach().clone()))
-        emb = F.normalize(emb, dim=-1)
-        x = self.graph1(emb, batch)
-        x = gnn.global_max_pool(x, batch) if self.variation == 0 else gnn.global_mean_pool(x, batch)
-        x = self.lin(x)
-        return F.normalize(x)
+        return self.cell_head(emb, cell_ptr)
+
+    def cell_head(self, object_embeddings, cell_ptr, knn=None, chunk_objects=32768):
+        """The cell head of encode_objects_packed_grad (models/cell_retrieval.py:95-107): F.normalize, graph1, max / mean pool
+        over each cell, lin, F.normalize.  object_embeddings [Nobj, D] (the ObjectEncoder's output), cell_ptr [B+1]; knn None
+        (graph1 builds its kNN graph) or an [Nobj, k] table of global neighbour rows padded with -1: the graph to use instead.
+        Runs in the module's dtype, so on a `.double()` copy in float64 throughout (a graph built here is still knn()'s, on the
+        fp32-rounded embeddings).  In eval mode the cells go through in slices of whole cells of at most `chunk_objects`
+        objects (the edge MLP's input is 8 x 2D values per object: 6 GB for 12,000 cells in float64); in train mode in one
+        piece, for BatchNorm's batch statistics."""
+        emb = torch.as_tensor(object_embeddings).to(self.lin[0][0].weight.dtype)
+        cell_ptr = [int(v) for v in cell_ptr]
+        n_cells = len(cell_ptr) - 1
+        if knn is not None:
+            knn = (knn.cpu().numpy() if isinstance(knn, torch.Tensor) else np.asarray(knn)).astype(np.int64)
+        bounds = [0]
+        while bounds[-1] < n_cells:
+            c0 = c1 = bounds[-1]
+            c1 += 1
+            while c1 < n_cells and (self.training or cell_ptr[c1 + 1] - cell_ptr[c0] <= chunk_objects):
+                c1 += 1
+            bounds.append(c1)
+        out = []
+        for c0, c1 in zip(bounds[:-1], bounds[1:]):
+            o0, o1 = cell_ptr[c0], cell_ptr[c1]
+            batch = torch.arange(c1 - c0).repeat_interleave(torch.tensor(np.diff(cell_ptr[c0: c1 + 1])))
+            table = None if knn is None else np.where(knn[o0:o1] >= 0, knn[o0:o1] - o0, -1)
+            x = self.graph1(F.normalize(emb[o0:o1], dim=-1), batch, knn=table)
+            x = gnn.global_max_pool(x, batch) if self.variation == 0 else gnn.global_mean_pool(x, batch)
+            out.append(F.normalize(self.lin(x)))
+        return out[0] if len(out) == 1 else torch.cat(out)
 
 
 def randomize_bn_stats(model: nn.Module, seed: int = 4321):

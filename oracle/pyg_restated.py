@@ -92,21 +92,35 @@ def radius(x, y, r, batch_x=None, batch_y=None, max_num_neighbors: int = 32):
     return torch.stack([row, col], dim=0)
 
 
-def knn(x, y, k, batch_x=None, batch_y=None):
-    """torch_cluster.knn for x is y (the only use on the path): [2, E] = (row = y index, col = x index)."""
-    assert x is y or torch.equal(x, y)
-    if batch_x is None:
-        batch_x = torch.zeros(x.shape[0], dtype=torch.long)
-    ptr = _segments(batch_x).numpy().astype(np.int32)
+def knn_table(x, k, batch=None):
+    """[n, k] int32 neighbour rows of torch_cluster.knn(x, x, k, batch, batch): per row its k nearest rows of the same
+    segment by (fp32 distance, index), self included, -1 past the segment's size (oracle/primitives.c)."""
+    if batch is None:
+        batch = torch.zeros(x.shape[0], dtype=torch.long)
+    ptr = _segments(batch).numpy().astype(np.int32)
     xn = np.ascontiguousarray(x.detach().cpu().numpy().astype(np.float32))
     n, dim = xn.shape
     out = np.zeros((n, k), dtype=np.int32)
     _lib().t2p_oracle_knn(_p(xn, ctypes.c_float), _p(ptr, ctypes.c_int32), ctypes.c_int32(len(ptr) - 1),
                           ctypes.c_int32(dim), ctypes.c_int32(k), _p(out, ctypes.c_int32))
+    return out
+
+
+def knn_edges(table):
+    """[2, E] = (row = target i, col = source j) of an [n, k] neighbour table padded with -1, in the order knn() emits its
+    edges: by target, then by the table's order."""
+    table = np.asarray(table)
+    n, k = table.shape
     row = np.repeat(np.arange(n, dtype=np.int64), k)
-    col = out.reshape(-1).astype(np.int64)
+    col = table.reshape(-1).astype(np.int64)
     keep = col >= 0
     return torch.from_numpy(np.stack([row[keep], col[keep]], 0))
+
+
+def knn(x, y, k, batch_x=None, batch_y=None):
+    """torch_cluster.knn for x is y (the only use on the path): [2, E] = (row = y index, col = x index)."""
+    assert x is y or torch.equal(x, y)
+    return knn_edges(knn_table(x, k, batch_x))
 
 
 def _scatter(msg, index, n_out, aggr):
@@ -181,8 +195,15 @@ class DynamicEdgeConv(nn.Module):
         self.k = k
         self.aggr = aggr
 
-    def forward(self, x, batch=None):
-        e = knn(x, x, self.k, batch, batch)  # (row = target i, col = source j)
+    def forward(self, x, batch=None, knn=None):
+        """knn: None (the graph of knn(x, x, k, batch, batch)) or an explicit [n, k'] table of neighbour rows of x padded
+        with -1 (knn_table's layout); the edges then come from that table, in the same order."""
+        if knn is None:
+            knn = knn_table(x, self.k, batch)
+        else:
+            knn = knn.cpu().numpy() if isinstance(knn, torch.Tensor) else np.asarray(knn)
+            assert knn.ndim == 2 and knn.shape[0] == x.shape[0] and knn.max(initial=-1) < x.shape[0], knn.shape
+        e = knn_edges(knn)  # (row = target i, col = source j)
         i, j = e[0], e[1]
         msg = self.nn(torch.cat([x[i], x[j] - x[i]], dim=-1))
         return _scatter(msg, i, x.shape[0], self.aggr)

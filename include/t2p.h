@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define T2P_ABI_VERSION 28
+#define T2P_ABI_VERSION 29
 #define T2P_DEFAULT_CHUNK_OBJECTS 65000 /* t2p_cell_config.chunk_objects == 0 */
 #define T2P_MAX_CHUNK_OBJECTS 65535     /* 32-bit table offsets / 16-bit local indices: chunk_objects and the largest single
                                            cell may not exceed it (T2P_E_ARG otherwise).  The caller-provided workspace holds
@@ -220,6 +220,38 @@ int t2p_encode_cells(const float* xyz, const float* rgb, const float* center, co
                      const int32_t* cell_ptr_host, const int32_t* cell_ptr, int64_t n_obj, int64_t n_cells,
                      const t2p_cell_weights* w, const t2p_cell_config* cfg, float* out, const t2p_cell_trace* trace,
                      void* workspace, size_t workspace_bytes, t2p_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * PointNet++ as a classifier of its own: PointNet2.forward (models/pointcloud/pointnet2.py:80-100) in eval mode, the model
+ * the reference pre-trains in training/pointcloud/pointnet2.py before the coarse stage loads it (models/object_encoder.py:46).
+ * The trunk is the cell encoder's (same kernels, same folded weights: the sa_*, ga_*, lin1_*, lin2_* members of
+ * t2p_cell_weights and their *_x3 images and guard norms; every other member is ignored), stopped behind lin2.  The reference
+ * hands a DataLoader batch to the model as ONE PyG batch, so the whole call is one cell of n_obj objects: PointConv's self-loop
+ * rewrite aliases dense row i of the BATCH onto centroid row i of the batch.  n_obj <= T2P_MAX_CHUNK_OBJECTS (T2P_E_ARG).
+ * Of cfg only n_pts, self_loops, radius, precision, overflow_flag and tuning are read (the guard word covers the stages that
+ * run: bits 0-4, 6, 7 and bit 5 for features0 / features1 as lin1 / lin2 split them).
+ * head_w [256][n_classes + n_colors] k-major (class_classifier.weight^T | color_classifier.weight^T side by side), head_b
+ * [n_classes + n_colors]; n_classes, n_colors in [1, 64] (T2P_E_UNSUPPORTED otherwise).  head_w == NULL: trunk only.
+ * Outputs (each may be NULL): features0 [n_obj][1024], features1 [n_obj][512], features2 [n_obj][256],
+ * class_pred [n_obj][n_classes], color_pred [n_obj][n_colors] (pointnet2.py:91-92; fp32, bias + 256 fma in ascending k).
+ * ---------------------------------------------------------------------------------------------------------- */
+size_t t2p_pointnet2_workspace_bytes(int64_t n_obj, const t2p_cell_config* cfg);
+int t2p_pointnet2_forward(const float* xyz, const float* rgb, int64_t n_obj, const t2p_cell_weights* w, const t2p_cell_config* cfg,
+                          const float* head_w, const float* head_b, int32_t n_classes, int32_t n_colors, float* features0,
+                          float* features1, float* features2, float* class_pred, float* color_pred, void* workspace,
+                          size_t workspace_bytes, t2p_stream_t stream);
+/* The two heads alone (csrc/classify.hip): features2 [n][256] -> class_pred [n][n_classes], color_pred [n][n_colors]. */
+int t2p_classifier_heads(const float* features2, const float* head_w, const float* head_b, int64_t n, int32_t n_classes,
+                         int32_t n_colors, float* class_pred, float* color_pred, t2p_stream_t stream);
+/* nn.CrossEntropyLoss()(class_pred, batch.y) with its gradient and the accuracy count of the pre-training loop
+ * (training/pointcloud/pointnet2.py:37, :42, :134) in one launch.  logits [n][n_classes] with row pitch ld_logits (floats),
+ * labels int32 [n].  row_loss [n] = logsumexp(row) - row[label] (loss = sum(row_loss) / n, summed by the caller in a fixed
+ * order); d_logits [n][n_classes] (row pitch ld_d) = (softmax(row) - onehot(label)) / n; correct int32 [n] =
+ * (argmax(row) == label), ties to the lower index as torch.argmax.  The row maximum is subtracted before exp; reductions are
+ * cross-lane butterflies, no atomics: deterministic.  A label outside [0, n_classes) gives NaN in row_loss and in the row of
+ * d_logits and correct = 0; nothing is read or written through it. */
+int t2p_softmax_xent(const float* logits, int32_t ld_logits, const int32_t* labels, int64_t n, int32_t n_classes, float* row_loss,
+                     float* d_logits, int32_t ld_d, int32_t* correct, t2p_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Input packing on the device: replaces the per-object host work of

@@ -11,7 +11,7 @@ import torch  # noqa: F401  (must precede CDLL: shares torch's libamdhip64)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("T2P_LIB") or os.path.join(_HERE, "libt2p_hip.so")  # T2P_LIB: A/B builds of the same ABI
-ABI_VERSION = 28
+ABI_VERSION = 29
 
 c_float_p = C.POINTER(C.c_float)
 c_void = C.c_void_p
@@ -68,6 +68,11 @@ SYMBOLS = {
     "t2p_encode_cells": (C.c_int, [c_void, c_void, c_void, c_void, c_void, c_void, C.c_int64, C.c_int64,
                                    C.POINTER(CellWeights), C.POINTER(CellConfig), c_void, C.POINTER(CellTrace), c_void,
                                    C.c_size_t, c_void]),
+    "t2p_pointnet2_workspace_bytes": (C.c_size_t, [C.c_int64, C.POINTER(CellConfig)]),
+    "t2p_pointnet2_forward": (C.c_int, [c_void, c_void, C.c_int64, C.POINTER(CellWeights), C.POINTER(CellConfig), c_void, c_void,
+                                        C.c_int32, C.c_int32, c_void, c_void, c_void, c_void, c_void, c_void, C.c_size_t, c_void]),
+    "t2p_classifier_heads": (C.c_int, [c_void, c_void, c_void, C.c_int64, C.c_int32, C.c_int32, c_void, c_void, c_void]),
+    "t2p_softmax_xent": (C.c_int, [c_void, C.c_int32, c_void, C.c_int64, C.c_int32, c_void, c_void, C.c_int32, c_void, c_void]),
     "t2p_encode_text_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
     "t2p_encode_text": (C.c_int, [c_void, c_void, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(TextWeights),
                                   c_void, c_void, c_void, C.c_size_t, c_void]),

@@ -8,7 +8,6 @@ t2p_encode_text); train() runs the batch-statistics path of train_cell.py / modu
 (SURVEY.md 8(f) #4).  Anything else (gradients through the folded kernels, the stage trace in train mode) raises; nothing
 falls back to another implementation.
 """
-import warnings
 from typing import List
 
 import numpy as np
@@ -17,7 +16,7 @@ import torch.nn as nn
 
 from . import ops, packing
 from .data import HostStaging, ObjectMeansCache, pack_cells
-from .modules import LanguageEncoder, PicklableModule, get_mlp
+from .modules import Fp16RangeGuard, LanguageEncoder, PicklableModule, get_mlp
 from .object_encoder import ObjectEncoder
 
 
@@ -29,7 +28,7 @@ class DynamicEdgeConv(nn.Module):
         self.nn, self.k, self.aggr = nn_, k, aggr
 
 
-class CellRetrievalNetwork(PicklableModule):
+class CellRetrievalNetwork(Fp16RangeGuard, PicklableModule):
     # what `torch.save(model, path)` (training/coarse.py:323-324) must not try to pickle: packed-weight descriptors, the guard word,
     # HIP streams, pinned staging, the per-cell means memo (it would drag the dataset's objects into the checkpoint)
     _TRANSIENT = {"_pack": None, "_overflow": None, "_aux_streams": None, "_aux_beside": None, "_copy_stream": None, "_staging": HostStaging,
@@ -103,22 +102,6 @@ class CellRetrievalNetwork(PicklableModule):
             self._pack = (ver, tensors, ops.make_cell_weights(tensors), x3)
         return self._pack[2]
 
-    def _overflow_word(self):
-        """The sticky fp16-range guard word of this model's f16x3 calls (int32 [1] on the device)."""
-        if self._overflow is None or self._overflow.device != self.device:
-            self._overflow = torch.zeros(1, dtype=torch.int32, device=self.device)
-        return self._overflow
-
-    def overflow_detected(self) -> int:
-        """Reads (synchronises) and clears the guard word: non-zero = some f16x3 call since the last check converted an
-        activation outside fp16's range and its result must not be used (bit meanings: include/t2p.h)."""
-        if self._overflow is None:
-            return 0
-        code = int(self._overflow.item())
-        if code:
-            self._overflow.zero_()
-        return code
-
     def _cell_config(self, n_pts, chunk_objects=0, class_idx=None, color_idx=None, precision=None):
         a = self.args
         if bool(getattr(a, "class_embed", False)) != (class_idx is not None) or \
@@ -133,32 +116,6 @@ class CellRetrievalNetwork(PicklableModule):
                                     chunk_objects=chunk_objects, precision=precision or self.precision,
                                     class_idx=class_idx, color_idx=color_idx, tuning=self.tuning,
                                     overflow_flag=self._overflow_word() if (precision or self.precision) == "f16x3" else None)
-
-    _GUARD_BITS = ("bits 0-2 = SA level 1-3 edge inputs, 3 = SA output rows, 4 = GA hidden planes, 5 = GEMM rows (PointNet2 "
-                   "features, kNN edge rows) past fp16's largest value; 6 = NaN among the input points / colours; 7 = a stage's "
-                   "activations too SMALL for the fp16 pieces (SA levels, GA hidden planes, PointNet2 features, kNN edge rows: "
-                   "largest magnitude below 2^-7, their low parts would underflow)")
-
-    def _with_guard(self, run):
-        """run() -> result of an encode on the CURRENT precision.  On the f16x3 path the sticky guard word is read after the
-        launch (one host synchronisation) and acted on as `on_overflow` says: raise, or warn and call run() again with the
-        model switched to the exact fp32 path.  The one place this logic lives: every entry point (single stream, several
-        streams, pinned-host blocks, the two pipelined halves of encode_objects, the scene path) goes through it."""
-        out = run()
-        if self.precision != "f16x3":
-            return out
-        code = self.overflow_detected()
-        if not code:
-            return out
-        msg = f"f16x3 path: an activation left the range its fp16 pieces cover (guard code {code:#x}: {self._GUARD_BITS})"
-        if self.on_overflow != "fp32":
-            raise FloatingPointError(msg + "; construct the model with precision=\"fp32\" or on_overflow=\"fp32\"")
-        warnings.warn(msg + "; recomputing this call on the exact fp32 path", RuntimeWarning)
-        saved, self.precision = self.precision, "fp32"
-        try:
-            return run()
-        finally:
-            self.precision = saved
 
     def _trim(self, out):
         """Cuts the zero padding of kernel_dim off an [n, kernel_dim] result (or an (embeddings, trace) pair)."""

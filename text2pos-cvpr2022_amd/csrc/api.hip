@@ -258,7 +258,9 @@ int copy_trace(T* dst, const T* src, size_t n, hipStream_t st) {
 int encode_chunk(const float* xyz, const float* rgb, const float* center, const float* mean_rgb,
                  const int32_t* cell_ptr_dev /* at first cell of chunk */, int32_t o_lo, int64_t n, int64_t nb,
                  int max_cell, const t2p_cell_weights& W, const t2p_cell_config& cfg, float* out,
-                 const t2p_cell_trace* tr, int64_t trace_obj0, CellWs& ws, hipStream_t st) {
+                 const t2p_cell_trace* tr, int64_t trace_obj0, CellWs& ws, hipStream_t st, bool trunk_only = false) {
+    // trunk_only (t2p_pointnet2_forward): the chunk is ONE cell of n objects (cell_ptr_dev is not read), the run stops behind
+    // lin2 and hands features0 / 1 / 2 back through tr
     Geo g(cfg.n_pts);
     const int D = cfg.embed_dim;
     // fp16-range guard (f16x3 only): the chunk's words are cleared by the first kernel and judged by the last
@@ -277,7 +279,10 @@ int encode_chunk(const float* xyz, const float* rgb, const float* center, const 
     for (int l = 0; l < 3; l++) lds_btab[l] = cfg.precision == 1 && g.specialised(l);
     // level 0 runs on sa_points.hip, which computes layer 1 per edge from the points themselves: no point table A_1 either
     const bool sa1_points = lds_btab[0];
-    T2P_TRY(launch_cell_index(cell_ptr_dev, (int)nb, o_lo, ws.seg_ptr, ws.first, st, guard));
+    if (trunk_only)
+        T2P_TRY(launch_one_cell_index(n, ws.seg_ptr, ws.first, st, guard));
+    else
+        T2P_TRY(launch_cell_index(cell_ptr_dev, (int)nb, o_lo, ws.seg_ptr, ws.first, st, guard));
     // models/object_encoder.py:86: the PointNet++ only runs when the "class" feature does not come from class_embedding
     const bool run_pointnet = cfg.use_class && !cfg.class_embed;
     if (run_pointnet) {
@@ -433,6 +438,13 @@ int encode_chunk(const float* xyz, const float* rgb, const float* center, const 
         T2P_TRY(launch_gemm(ws.f1, 512, W.lin2_w, W.lin2_b, ws.f2, 256, 0, n, 512, 256, 1, st));
     }
     }  // run_pointnet
+    if (trunk_only) {
+        T2P_TRY(copy_trace(tr->features0, ws.f0, (size_t)n * 1024, st));
+        T2P_TRY(copy_trace(tr->features1, ws.f1, (size_t)n * 512, st));
+        T2P_TRY(copy_trace(tr->features2, ws.f2, (size_t)n * 256, st));
+        T2P_TRY(launch_guard_check(guard, cfg.overflow_flag, gbounds, st));
+        return 0;
+    }
     const int nfeat = (cfg.use_class ? 1 : 0) + (cfg.use_color ? 1 : 0) + (cfg.use_position ? 1 : 0);
     const int ldcat = nfeat * D;
     int slot = 0;
@@ -682,6 +694,101 @@ int t2p_encode_cells(const float* xyz, const float* rgb, const float* center, co
                              st));
         c0 = c1;
     }
+    return 0;
+}
+
+// ---- PointNet++ as a classifier of its own (models/pointcloud/pointnet2.py:80-100) ------------------------------------------
+// The trunk-only configuration the chunk runner is driven with: the caller's geometry / precision / guard / tuning, everything
+// behind lin2 at the values that make carve() and check_cfg() happy (those stages do not run).
+static t2p_cell_config trunk_cfg(const t2p_cell_config& in) {
+    t2p_cell_config c{};
+    c.n_pts = in.n_pts;
+    c.embed_dim = 256;
+    c.pointnet_features = 2;
+    c.use_class = 1;
+    c.self_loops = in.self_loops;
+    c.knn_k = 8;
+    for (int l = 0; l < 3; l++) c.radius[l] = in.radius[l];
+    c.precision = in.precision;
+    c.overflow_flag = in.overflow_flag;
+    c.tuning = in.tuning;
+    return c;
+}
+
+size_t t2p_pointnet2_workspace_bytes(int64_t n_obj, const t2p_cell_config* cfg) {
+    if (cfg == nullptr || n_obj <= 0) return 256;
+    const t2p_cell_config c = trunk_cfg(*cfg);
+    Bump b{nullptr, 0, 0};
+    return carve(b, n_obj, 1, c, nullptr) + 256;
+}
+
+int t2p_classifier_heads(const float* features2, const float* head_w, const float* head_b, int64_t n, int32_t n_classes,
+                         int32_t n_colors, float* class_pred, float* color_pred, t2p_stream_t stream) {
+    T2P_CHECK_ARG(features2 && head_w && head_b && class_pred && color_pred, "classifier_heads: NULL argument");
+    T2P_CHECK_ARG(n >= 0, "classifier_heads: negative size");
+    if (n_classes < 1 || n_classes > 64 || n_colors < 1 || n_colors > 64) {
+        set_error("classifier_heads: n_classes=%d / n_colors=%d outside [1, 64]", n_classes, n_colors);
+        return T2P_E_UNSUPPORTED;
+    }
+    T2P_CHECK_ARG(((uintptr_t)features2 & 15) == 0, "classifier_heads: features2 must be 16-byte aligned");
+    return launch_classifier_heads(features2, head_w, head_b, n, n_classes, n_colors, class_pred, color_pred, (hipStream_t)stream);
+}
+
+int t2p_softmax_xent(const float* logits, int32_t ld_logits, const int32_t* labels, int64_t n, int32_t n_classes, float* row_loss,
+                     float* d_logits, int32_t ld_d, int32_t* correct, t2p_stream_t stream) {
+    T2P_CHECK_ARG(logits && labels && row_loss && d_logits && correct, "softmax_xent: NULL argument");
+    T2P_CHECK_ARG(n >= 0 && n_classes >= 1, "softmax_xent: n=%lld, n_classes=%d", (long long)n, n_classes);
+    T2P_CHECK_ARG(ld_logits >= n_classes && ld_d >= n_classes, "softmax_xent: row pitch below n_classes=%d", n_classes);
+    return launch_softmax_xent(logits, ld_logits, labels, n, n_classes, row_loss, d_logits, ld_d, correct, (hipStream_t)stream);
+}
+
+int t2p_pointnet2_forward(const float* xyz, const float* rgb, int64_t n_obj, const t2p_cell_weights* w, const t2p_cell_config* cfg,
+                          const float* head_w, const float* head_b, int32_t n_classes, int32_t n_colors, float* features0,
+                          float* features1, float* features2, float* class_pred, float* color_pred, void* workspace,
+                          size_t workspace_bytes, t2p_stream_t stream) {
+    hipStream_t st = (hipStream_t)stream;
+    T2P_CHECK_ARG(cfg != nullptr && w != nullptr, "pointnet2_forward: NULL argument");
+    const t2p_cell_config c = trunk_cfg(*cfg);
+    T2P_TRY(check_cfg(&c));
+    T2P_CHECK_ARG(n_obj >= 0, "pointnet2_forward: negative size");
+    T2P_CHECK_ARG(n_obj <= T2P_MAX_CHUNK_OBJECTS,
+                  "pointnet2_forward: %lld objects in one batch; the batch is one cell, limited to %d objects", (long long)n_obj,
+                  T2P_MAX_CHUNK_OBJECTS);
+    const bool heads = head_w != nullptr;
+    if (heads) {
+        T2P_CHECK_ARG(head_b != nullptr && class_pred != nullptr && color_pred != nullptr,
+                      "pointnet2_forward: the heads need head_b, class_pred and color_pred");
+        if (n_classes < 1 || n_classes > 64 || n_colors < 1 || n_colors > 64) {
+            set_error("pointnet2_forward: n_classes=%d / n_colors=%d outside [1, 64]", n_classes, n_colors);
+            return T2P_E_UNSUPPORTED;
+        }
+    }
+    if (n_obj == 0) return 0;
+    T2P_CHECK_ARG(xyz != nullptr && rgb != nullptr && workspace != nullptr, "pointnet2_forward: NULL argument");
+    if (c.precision == 1)
+        T2P_CHECK_ARG(w->sa_w2_x3[0] && w->sa_w2_x3[1] && w->sa_w2_x3[2] && w->sa_b2_x3[0] && w->sa_b2_x3[1] && w->sa_b2_x3[2] &&
+                          w->sa_w2_scale[0] > 0.f && w->sa_w2_scale[1] > 0.f && w->sa_w2_scale[2] > 0.f && w->sa_w1_x3[1] &&
+                          w->sa_w1_x3[2] && w->ga_w1_x3 && w->ga_w2_x3,
+                      "pointnet2_forward: precision = f16x3 needs the packed *_x3 weight images");
+    if (c.precision == 1 && c.overflow_flag != nullptr)
+        T2P_CHECK_ARG(w->ga_w1_l1 > 0.f && w->ga_b1_absmax >= 0.f && w->sa_a1_l1 > 0.f && w->sa_wp_l1[0] >= 0.f,
+                      "pointnet2_forward: the fp16-range guard needs the weight norms of t2p_cell_weights (packing.py)");
+    T2P_CHECK_ARG((((uintptr_t)xyz | (uintptr_t)rgb | (uintptr_t)workspace) & 15) == 0,
+                  "pointnet2_forward: xyz, rgb and workspace must be 16-byte aligned");
+    Bump b{(char*)workspace, 0, workspace_bytes};
+    CellWs ws;
+    const size_t need = carve(b, n_obj, 1, c, &ws);
+    if (need > workspace_bytes) {
+        set_error("pointnet2_forward: workspace %zu B < %zu B needed for %lld objects", workspace_bytes, need, (long long)n_obj);
+        return T2P_E_WORKSPACE;
+    }
+    t2p_cell_trace tr{};
+    tr.features0 = features0;
+    tr.features1 = features1;
+    tr.features2 = features2;
+    T2P_TRY(encode_chunk(xyz, rgb, nullptr, nullptr, nullptr, 0, n_obj, 1, (int)n_obj, *w, c, nullptr, &tr, 0, ws, st, true));
+    if (heads)   // (on the workspace's copy of features2: the caller need not ask for it)
+        T2P_TRY(launch_classifier_heads(ws.f2, head_w, head_b, n_obj, n_classes, n_colors, class_pred, color_pred, st));
     return 0;
 }
 

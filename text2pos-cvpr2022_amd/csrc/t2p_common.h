@@ -388,6 +388,14 @@ int launch_segment_max(const float* x, const int32_t* seg_ptr, int n_seg, int C,
 int launch_segment_max_backward(const float* dout, const int32_t* arg, const int32_t* seg_ptr, int n_seg, int C, float* dx,
                                 hipStream_t st);
 
+// ---- classify.hip: PointNet++ pre-training (classifier heads, softmax cross-entropy) -----------------------------------------
+int launch_classifier_heads(const float* f2, const float* w, const float* bias, int64_t n, int C1, int C2, float* class_pred,
+                            float* color_pred, hipStream_t st);
+int launch_softmax_xent(const float* logits, int ld, const int32_t* labels, int64_t n, int C, float* row_loss, float* d_logits,
+                        int ldd, int32_t* correct, hipStream_t st);
+// launch_cell_index for a batch that is ONE cell of n objects (no device cell_ptr needed)
+int launch_one_cell_index(int64_t n, int32_t* seg_ptr_local, int32_t* first, hipStream_t st, uint32_t* guard_to_clear);
+
 // ---- sim_topk.hip -----------------------------------------------------------------------------------------
 size_t sim_topk_workspace_bytes(int64_t nq, int64_t nc, int k);
 int launch_sim_topk(const float* Q, const float* C, int64_t nq, int64_t nc, int dim, int k, int64_t c_index_offset,

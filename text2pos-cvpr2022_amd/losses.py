@@ -3,7 +3,9 @@
 Same call `criterion(anchor, positive)`; the reference's hard-coded `.cuda()` is gone (tensors stay on their device).
 The hinge terms, their sum and the gradient with respect to the score matrix come from t2p_pairwise_ranking
 (csrc/small_kernels.hip); the score matrix and its two gradient products run on the library's own fp32-MFMA GEMM (ops.matmul).
-`HardestRankingLoss` (training/losses.py:167-201, --ranking_loss hardest) shares the wrapper on t2p_hardest_ranking."""
+`HardestRankingLoss` (training/losses.py:167-201, --ranking_loss hardest) shares the wrapper on t2p_hardest_ranking.
+`CrossEntropyLoss` is the criterion of the PointNet++ pre-training stage (training/pointcloud/pointnet2.py:37, :134:
+`nn.CrossEntropyLoss()(output.class_pred, batch.y)`) on t2p_softmax_xent (csrc/classify.hip)."""
 import torch
 import torch.nn as nn
 
@@ -53,3 +55,49 @@ class HardestRankingLoss(nn.Module):
         if images.shape != captions.shape or images.dim() != 2:
             raise RuntimeError("HardestRankingLoss: images and captions must both be [B, D]")
         return _PairwiseRankingFn.apply(images, captions, float(self.margin), True)
+
+
+class _CrossEntropyFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, target):
+        x = logits.detach()
+        if x.dtype != torch.float32:
+            x = x.float()
+        row_loss, d_logits, correct = ops.softmax_xent(x, target.to(device=x.device, dtype=torch.int32).contiguous())
+        ctx.save_for_backward(d_logits)
+        ctx.mark_non_differentiable(correct)
+        return row_loss.sum() / logits.shape[0], correct      # the mean as a fixed-order sum: no float atomics
+
+    @staticmethod
+    def backward(ctx, g, _g_correct):
+        (d_logits,) = ctx.saved_tensors
+        return g * d_logits, None
+
+
+class CrossEntropyLoss(nn.Module):
+    """`nn.CrossEntropyLoss()` as the pre-training loop uses it: criterion(logits [n, C], target [n] of class indices), mean
+    reduction.  Loss, gradient and the per-row hit (argmax == target, the accuracy line training/pointcloud/pointnet2.py:42)
+    come from ONE kernel launch; `last_correct` (int32 [n], on the device) holds the hits of the latest call.
+    A target outside [0, C) raises (the kernel marks the row with NaN instead of reading through the label; reading the loss
+    back here costs the host synchronisation the loop's `loss.item()` pays anyway)."""
+
+    def __init__(self):
+        super().__init__()
+        self.last_correct = None
+
+    def forward(self, logits, target):
+        if logits.dim() != 2 or target.dim() != 1 or target.shape[0] != logits.shape[0]:
+            raise RuntimeError("CrossEntropyLoss: logits must be [n, C] and target [n] (class indices)")
+        if target.is_floating_point():
+            raise RuntimeError("CrossEntropyLoss: target must hold class indices (class probabilities are not built)")
+        if logits.shape[0] == 0:
+            raise RuntimeError("CrossEntropyLoss: empty batch")
+        loss, correct = _CrossEntropyFn.apply(logits, target)
+        self.last_correct = correct
+        if bool(torch.isnan(loss.detach())):
+            t = target.detach()
+            bad = ((t < 0) | (t >= logits.shape[1])).nonzero()
+            if bad.numel():
+                raise IndexError(f"CrossEntropyLoss: target {int(t[bad[0, 0]])} of row {int(bad[0, 0])} is outside [0, {logits.shape[1]})")
+            raise FloatingPointError("CrossEntropyLoss: the loss is NaN (NaN among the logits)")
+        return loss

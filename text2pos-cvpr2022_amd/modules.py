@@ -4,6 +4,7 @@ state_dict layout) and `LanguageEncoder` (host tokenisation + HIP embedding/biLS
 Reference: models/modules.py:11-36 (get_mlp: every layer, including the last, is Linear -> BatchNorm1d -> ReLU),
 models/modules.py:39-92 (LanguageEncoder).
 """
+import warnings
 from typing import List
 
 import numpy as np
@@ -162,6 +163,55 @@ class PicklableModule(nn.Module):
             if name in state:
                 state[name] = fresh() if callable(fresh) else fresh
         return state
+
+
+class Fp16RangeGuard:
+    """The fp16-range guard of the f16x3 path as the models that own packed inference weights use it (CellRetrievalNetwork,
+    pointnet2.PointNet2): the sticky device word the kernels OR their verdict into (include/t2p.h, t2p_cell_config.overflow_flag)
+    and what happens when it fires.  The owner has `precision` ("f16x3" | "fp32"), `on_overflow` ("raise" | "fp32"), `device` and
+    an `_overflow` attribute that starts as None."""
+
+    def _overflow_word(self):
+        """The sticky fp16-range guard word of this model's f16x3 calls (int32 [1] on the device)."""
+        if self._overflow is None or self._overflow.device != self.device:
+            self._overflow = torch.zeros(1, dtype=torch.int32, device=self.device)
+        return self._overflow
+
+    def overflow_detected(self) -> int:
+        """Reads (synchronises) and clears the guard word: non-zero = some f16x3 call since the last check converted an
+        activation outside fp16's range and its result must not be used (bit meanings: include/t2p.h)."""
+        if self._overflow is None:
+            return 0
+        code = int(self._overflow.item())
+        if code:
+            self._overflow.zero_()
+        return code
+
+    _GUARD_BITS = ("bits 0-2 = SA level 1-3 edge inputs, 3 = SA output rows, 4 = GA hidden planes, 5 = GEMM rows (PointNet2 "
+                   "features, kNN edge rows) past fp16's largest value; 6 = NaN among the input points / colours; 7 = a stage's "
+                   "activations too SMALL for the fp16 pieces (SA levels, GA hidden planes, PointNet2 features, kNN edge rows: "
+                   "largest magnitude below 2^-7, their low parts would underflow)")
+
+    def _with_guard(self, run):
+        """run() -> result of an encode on the CURRENT precision.  On the f16x3 path the sticky guard word is read after the
+        launch (one host synchronisation) and acted on as `on_overflow` says: raise, or warn and call run() again with the
+        model switched to the exact fp32 path.  The one place this logic lives: every entry point (single stream, several
+        streams, pinned-host blocks, the two pipelined halves of encode_objects, the scene path) goes through it."""
+        out = run()
+        if self.precision != "f16x3":
+            return out
+        code = self.overflow_detected()
+        if not code:
+            return out
+        msg = f"f16x3 path: an activation left the range its fp16 pieces cover (guard code {code:#x}: {self._GUARD_BITS})"
+        if self.on_overflow != "fp32":
+            raise FloatingPointError(msg + "; construct the model with precision=\"fp32\" or on_overflow=\"fp32\"")
+        warnings.warn(msg + "; recomputing this call on the exact fp32 path", RuntimeWarning)
+        saved, self.precision = self.precision, "fp32"
+        try:
+            return run()
+        finally:
+            self.precision = saved
 
 
 class LanguageEncoder(PicklableModule):

@@ -518,6 +518,84 @@ def encode_cells(xyz, rgb, center, mean_rgb, cell_ptr_host: np.ndarray, cell_ptr
     return (out, trace) if want_trace else out
 
 
+MAX_HEAD_COLUMNS = 64   # include/t2p.h: n_classes, n_colors of t2p_classifier_heads
+
+
+def pointnet2_forward(xyz, rgb, weights: L.CellWeights, cfg: L.CellConfig, head_w=None, head_b=None, n_classes: int = 0,
+                      n_colors: int = 0, ws_tag: str = "pointnet2"):
+    """PointNet2.forward in eval mode on packed, device-resident inputs (t2p_pointnet2_forward): the whole batch is ONE cell.
+    xyz / rgb [n, P, 3]; head_w [256, n_classes + n_colors] k-major and head_b, or None for the trunk alone.
+    Returns dict(features0 [n, 1024], features1 [n, 512], features2 [n, 256][, class_pred [n, n_classes], color_pred])."""
+    _need(xyz, "xyz", torch.float32, 3)
+    dev = xyz.device
+    _need(rgb, "rgb", torch.float32, 3, dev)
+    n, n_pts = xyz.shape[0], xyz.shape[1]
+    if tuple(rgb.shape) != tuple(xyz.shape) or xyz.shape[2] != 3:
+        raise RuntimeError(f"pointnet2_forward: xyz {tuple(xyz.shape)} / rgb {tuple(rgb.shape)} must both be [n_obj, n_pts, 3]")
+    if n_pts != cfg.n_pts:
+        raise RuntimeError(f"pointnet2_forward: objects have {n_pts} points, config says {cfg.n_pts}")
+    out = dict(features0=torch.empty((n, 1024), dtype=torch.float32, device=dev),
+               features1=torch.empty((n, 512), dtype=torch.float32, device=dev),
+               features2=torch.empty((n, 256), dtype=torch.float32, device=dev))
+    if head_w is not None:
+        _need(head_w, "head_w", torch.float32, 2, dev)
+        _need(head_b, "head_b", torch.float32, 1, dev)
+        if tuple(head_w.shape) != (256, n_classes + n_colors) or head_b.numel() != n_classes + n_colors:
+            raise RuntimeError(f"pointnet2_forward: head_w {tuple(head_w.shape)} is not [256, {n_classes} + {n_colors}]")
+        out["class_pred"] = torch.empty((n, n_classes), dtype=torch.float32, device=dev)
+        out["color_pred"] = torch.empty((n, n_colors), dtype=torch.float32, device=dev)
+    ws = workspace(dev, L.lib().t2p_pointnet2_workspace_bytes(n, C.byref(cfg)), ws_tag)
+    rc = L.lib().t2p_pointnet2_forward(_ptr(xyz), _ptr(rgb), n, C.byref(weights), C.byref(cfg), _ptr(head_w), _ptr(head_b),
+                                       int(n_classes), int(n_colors), _ptr(out["features0"]), _ptr(out["features1"]),
+                                       _ptr(out["features2"]), _ptr(out.get("class_pred")), _ptr(out.get("color_pred")),
+                                       _ptr(ws), ws.numel(), _stream(dev))
+    L.check(rc, "t2p_pointnet2_forward")
+    return out
+
+
+def classifier_heads(features2, head_w, head_b, n_classes: int, n_colors: int):
+    """features2 [n, 256] -> (class_pred [n, n_classes], color_pred [n, n_colors]) on t2p_classifier_heads; head_w
+    [256, n_classes + n_colors] k-major (the two heads side by side), head_b [n_classes + n_colors]."""
+    _need(features2, "features2", torch.float32, 2)
+    dev = features2.device
+    _need(head_w, "head_w", torch.float32, 2, dev)
+    _need(head_b, "head_b", torch.float32, 1, dev)
+    n = features2.shape[0]
+    if features2.shape[1] != 256 or tuple(head_w.shape) != (256, n_classes + n_colors) or head_b.numel() != n_classes + n_colors:
+        raise RuntimeError(f"classifier_heads: features2 {tuple(features2.shape)} / head_w {tuple(head_w.shape)} / head_b "
+                           f"{tuple(head_b.shape)} do not fit [n, 256] x [256, {n_classes} + {n_colors}]")
+    class_pred = torch.empty((n, n_classes), dtype=torch.float32, device=dev)
+    color_pred = torch.empty((n, n_colors), dtype=torch.float32, device=dev)
+    L.check(L.lib().t2p_classifier_heads(_ptr(features2), _ptr(head_w), _ptr(head_b), n, int(n_classes), int(n_colors),
+                                         _ptr(class_pred), _ptr(color_pred), _stream(dev)), "t2p_classifier_heads")
+    return class_pred, color_pred
+
+
+def softmax_xent(logits: torch.Tensor, labels: torch.Tensor):
+    """logits [n, C] fp32 (rows may be strided: a column slice of a wider matrix), labels int32 [n] ->
+    (row_loss [n], d_logits [n, C] = d mean-loss / d logits, correct int32 [n]) of t2p_softmax_xent."""
+    if not isinstance(logits, torch.Tensor) or logits.dim() != 2 or logits.stride(1) != 1:
+        raise RuntimeError("softmax_xent: logits must be a [n, C] tensor with unit column stride")
+    if not logits.is_cuda or logits.dtype != torch.float32:
+        raise RuntimeError(f"softmax_xent: logits must be fp32 on the GPU (got {logits.dtype} on {logits.device}); there is no CPU path")
+    dev = logits.device
+    _need(labels, "labels", torch.int32, 1, dev)
+    n, c = logits.shape
+    if labels.numel() != n:
+        raise RuntimeError(f"softmax_xent: {n} rows of logits but {labels.numel()} labels")
+    if c < 1:
+        raise RuntimeError("softmax_xent: no classes")
+    ld = logits.stride(0) if n > 1 else c
+    if ld < c:
+        raise RuntimeError("softmax_xent: rows of logits overlap")
+    row_loss = torch.empty((n,), dtype=torch.float32, device=dev)
+    d_logits = torch.empty((n, c), dtype=torch.float32, device=dev)
+    correct = torch.empty((n,), dtype=torch.int32, device=dev)
+    L.check(L.lib().t2p_softmax_xent(_ptr(logits), int(ld), _ptr(labels), n, c, _ptr(row_loss), _ptr(d_logits), c, _ptr(correct),
+                                     _stream(dev)), "t2p_softmax_xent")
+    return row_loss, d_logits, correct
+
+
 def pack_objects(raw_xyz, raw_rgb, obj_ptr, sample_idx, rot=None):
     """Device-side FixedPoints gather (+ RandomRotate about z) + NormalizeScale + per-object means.  raw_xyz/raw_rgb
     [Np,3] fp32, obj_ptr [Nobj+1] int32, sample_idx [Nobj,P] int32 (local indices), rot None or [Nobj,2] fp32 (cos, sin

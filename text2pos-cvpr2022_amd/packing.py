@@ -165,7 +165,8 @@ def pack_cell_weights(model, device, x3: bool = True) -> Dict[str, object]:
     return p
 
 
-def _add_x3_images(p: Dict[str, object], device, cell_head: bool):
+def _add_trunk_x3_images(p: Dict[str, object], device):
+    """The f16x3 images and fp16-range guard norms of the PointNet++ trunk (SA levels, GA, lin1, lin2)."""
     scales = [f16x3_scale(t) for t in p["sa_w2"]]
     p["sa_w2_scale"] = scales
     p["sa_w2_x3"] = [pack_f16x3_scaled(t, sc).to(device) for t, sc in zip(p["sa_w2"], scales)]
@@ -183,16 +184,24 @@ def _add_x3_images(p: Dict[str, object], device, cell_head: bool):
     p["sa_wp_l1"] = [float(w[c: c + 3].double().abs().sum(0).max()) for w, c in zip(p["sa_w1"], feat)]
     p["sa_a1_l1"] = float(p["sa_w1"][0].double().abs().sum(0).max())
     p["sa_b1_absmax"] = float(p["sa_b1"][0].double().abs().max())
-    for name, src in (("lin1", "lin1_w"), ("lin2", "lin2_w"), ("pn", "pn_w"), ("merge", "merge_w")) + \
-            ((("g_wp", "g_wp"), ("g_wq", "g_wq")) if cell_head else ()):
+    _add_gemm_x3_images(p, device, (("lin1", "lin1_w"), ("lin2", "lin2_w")))
+
+
+def _add_gemm_x3_images(p: Dict[str, object], device, pairs):
+    for name, src in pairs:
         sc = f16x3_scale(p[src])
         p[name + "_scale"], p[name + "_x3"] = sc, pack_gemm_x3(p[src], sc).to(device)
+
+
+def _add_x3_images(p: Dict[str, object], device, cell_head: bool):
+    _add_trunk_x3_images(p, device)
+    _add_gemm_x3_images(p, device, (("pn", "pn_w"), ("merge", "merge_w")) + ((("g_wp", "g_wp"), ("g_wq", "g_wq")) if cell_head else ()))
     if cell_head and p["g_w2"].shape[0] % 32 == 0 and p["g_w2"].shape[1] % 32 == 0:
         p["g_w2_x3"] = pack_f16x3(p["g_w2"]).to(device)
 
 
-def _pack_cell_weights_fp32(model, device) -> Dict[str, object]:
-    oe, pn = model.object_encoder, model.object_encoder.pointnet
+def _pack_pointnet_fp32(pn, device) -> Dict[str, object]:
+    """The folded fp32 pack of a bare PointNet2 trunk (this package's pointnet2.PointNet2): SA levels, GA, lin1, lin2."""
     p: Dict[str, object] = {}
     sa_w1, sa_b1, sa_w2, sa_b2 = [], [], [], []
     for sa, kpad in ((pn.sa1, 6), (pn.sa2, 96), (pn.sa3, 160)):
@@ -211,6 +220,24 @@ def _pack_cell_weights_fp32(model, device) -> Dict[str, object]:
     for name, lin in (("lin1", pn.lin1), ("lin2", pn.lin2)):
         p[name + "_w"] = kmajor(lin.weight.detach().double()).to(device)
         p[name + "_b"] = f32(lin.bias.detach().double()).to(device)
+    return p
+
+
+def pack_pointnet_weights(pn, device, x3: bool = True) -> Dict[str, object]:
+    """pn: a stand-alone PointNet2.  The trunk's part of pack_cell_weights (same tensors, bit for bit: the same functions make
+    them) plus the two classifier heads side by side for t2p_classifier_heads: head_w [256][C1 + C2] k-major, head_b."""
+    p = _pack_pointnet_fp32(pn, device)
+    if x3:
+        _add_trunk_x3_images(p, device)
+    w = torch.cat([pn.class_classifier.weight.detach().double(), pn.color_classifier.weight.detach().double()], 0)
+    b = torch.cat([pn.class_classifier.bias.detach().double(), pn.color_classifier.bias.detach().double()], 0)
+    p.update(head_w=kmajor(w).to(device), head_b=f32(b).to(device))
+    return p
+
+
+def _pack_cell_weights_fp32(model, device) -> Dict[str, object]:
+    oe = model.object_encoder
+    p = _pack_pointnet_fp32(oe.pointnet, device)
     w, b = fold_linear_bn(oe.mlp_pointnet[0])
     p.update(pn_w=kmajor(w).to(device), pn_b=f32(b).to(device))
     for pre, enc in (("col", oe.color_encoder), ("pos", oe.pos_encoder)):

@@ -66,6 +66,41 @@ def _host_plan(cp: np.ndarray, k: int, dev):
                 seg={n: v for n, v in zip(segs, views[5:])}, _host=host)   # (the pinned buffer outlives the copy with the plan)
 
 
+def pointnet_trunk_train(pn, xyz, rgb, first_obj, cell_ptr_dev, add_self_loops=True, zero_color=False):
+    """PointNet2.forward up to features2 in train() mode (models/pointcloud/pointnet2.py:83-90): three set-abstraction levels,
+    global abstraction, lin1, lin2; every BatchNorm takes its statistics per CELL (one row segment per cell and layer).  Shared by
+    the coarse cell branch (encode_objects_train: the reference runs the PointNet++ once per cell) and by the stand-alone
+    classifier (pointnet2.PointNet2 in train(): the whole batch is one cell, cell_ptr = [0, n]).
+    pn: PointNet2; xyz / rgb [n_obj, P, 3]; first_obj [n_obj], cell_ptr_dev [B + 1] int32 on the device.
+    Returns (features0 [n_obj, 1024], features1 [n_obj, 512], features2 [n_obj, 256]) with a grad_fn."""
+    dev = xyz.device
+    n_obj, n_pts = xyz.shape[0], xyz.shape[1]
+    # FPS + ball query + torch_geometric's self-loop rewrite as edge lists, built on the device (ops.group_edges; the torch
+    # formulation of the same lists - hit mask, nonzero, remove / append self loops, stable sort - is the statement
+    # tests/test_gpu_parity.py::test_group_edges_equal_the_tensor_formulation compares it against)
+    levels = ops.group_edges(xyz.contiguous(), first_obj, pn.radii, add_self_loops)
+    pos = xyz.reshape(n_obj * n_pts, 3)
+    x = rgb.reshape(n_obj * n_pts, 3)
+    if zero_color:
+        x = torch.zeros_like(x)
+    nd = n_pts
+    for lvl, sa in enumerate((pn.sa1, pn.sa2, pn.sa3)):
+        nc = (nd + 1) // 2
+        g = levels[lvl]
+        fps = g["fps_idx"].long()
+        pos_c = pos.view(n_obj, nd, 3).gather(1, fps[:, :, None].expand(-1, -1, 3)).reshape(n_obj * nc, 3)
+        cent_ptr = g["cent_ptr"]
+        cell_edge_ptr = cent_ptr[cell_ptr_dev.long() * nc].contiguous()      # edges per cell = BatchNorm's row segments
+        msg = TO.edge_features(x, pos, pos_c, g["src"], g["dst"])
+        h = _mlp_train(msg, sa.point_conv.local_nn, cell_edge_ptr, nc)    # >= one self loop / hit per centroid
+        x, pos, nd = TO.segment_max(h, cent_ptr, covers_all_rows=True), pos_c, nc    # (cent_ptr is the CSR over ALL edge rows)
+    h = _mlp_train(torch.cat([x, pos], dim=1), pn.ga.mlp, _i32(cell_ptr_dev.long() * nd), nd)
+    f0 = TO.segment_max(h, _i32(torch.arange(n_obj + 1, device=dev) * nd), covers_all_rows=True)
+    f1 = torch.relu(TO.linear(f0, pn.lin1))
+    f2 = torch.relu(TO.linear(f1, pn.lin2))
+    return f0, f1, f2
+
+
 def encode_objects_train(model, xyz, rgb, center, mean_rgb, cell_ptr, class_idx=None, color_idx=None):
     """model: CellRetrievalNetwork in train(); packed device inputs as encode_objects_packed.  Returns [B, D] unit rows with
     a grad_fn; BatchNorm running estimates are updated as the reference's per-cell / per-batch module calls would."""
@@ -87,30 +122,8 @@ def encode_objects_train(model, xyz, rgb, center, mean_rgb, cell_ptr, class_idx=
 
     def pointnet_branch():
         """models/object_encoder.py:86-98: the PointNet++ (one call per cell) + mlp_pointnet."""
-        # FPS + ball query + torch_geometric's self-loop rewrite as edge lists, built on the device (ops.group_edges; the torch
-        # formulation of the same lists - hit mask, nonzero, remove / append self loops, stable sort - is the statement
-        # tests/test_gpu_parity.py::test_group_edges_equal_the_tensor_formulation compares it against)
-        levels = ops.group_edges(xyz.contiguous(), first_obj, pn.radii, model.add_self_loops)
-        pos = xyz.reshape(n_obj * n_pts, 3)
-        x = rgb.reshape(n_obj * n_pts, 3)
-        if "color" not in a.use_features:                       # models/object_encoder.py:87-90
-            x = torch.zeros_like(x)
-        nd = n_pts
-        for lvl, sa in enumerate((pn.sa1, pn.sa2, pn.sa3)):
-            nc = (nd + 1) // 2
-            g = levels[lvl]
-            fps = g["fps_idx"].long()
-            pos_c = pos.view(n_obj, nd, 3).gather(1, fps[:, :, None].expand(-1, -1, 3)).reshape(n_obj * nc, 3)
-            cent_ptr = g["cent_ptr"]
-            cell_edge_ptr = cent_ptr[cell_ptr_dev.long() * nc].contiguous()      # edges per cell = BatchNorm's row segments
-            msg = TO.edge_features(x, pos, pos_c, g["src"], g["dst"])
-            h = _mlp_train(msg, sa.point_conv.local_nn, cell_edge_ptr, nc)    # >= one self loop / hit per centroid
-            x, pos, nd = TO.segment_max(h, cent_ptr, covers_all_rows=True), pos_c, nc    # (cent_ptr is the CSR over ALL edge rows)
-        h = _mlp_train(torch.cat([x, pos], dim=1), pn.ga.mlp, _i32(cell_ptr_dev.long() * nd), nd)
-        f0 = TO.segment_max(h, _i32(torch.arange(n_obj + 1, device=dev) * nd), covers_all_rows=True)
-        f1 = torch.relu(TO.linear(f0, pn.lin1))
-        f2 = torch.relu(TO.linear(f1, pn.lin2))
-        feats = (f0, f1, f2)[a.pointnet_features]
+        feats = pointnet_trunk_train(pn, xyz, rgb, first_obj, cell_ptr_dev, model.add_self_loops,
+                                     zero_color="color" not in a.use_features)[a.pointnet_features]   # models/object_encoder.py:87-90
         return _mlp_train(feats, oe.mlp_pointnet, one(n_obj), n_obj)
 
     if "class" in a.use_features and class_embed:               # models/object_encoder.py:103-109: no PointNet++ at all

@@ -1,4 +1,5 @@
-"""Host loop of the reference's coarse training (training/coarse.py:31-62, `train_epoch`) on the HIP path: same batch
+"""Host loops of the reference's PointNet++ pre-training (training/pointcloud/pointnet2.py:24-67, `train_epoch` / `val_epoch`:
+train_pointnet_epoch, val_pointnet_epoch below) and of the reference's coarse training (training/coarse.py:31-62, `train_epoch`) on the HIP path: same batch
 dictionary (`texts`, `objects`, `object_points` as the reference's Kitti360CoarseDataset.collate_fn yields them), same
 order of calls; the arithmetic is docs/notebook.md 4.8.  The data side (datasets, augmentation, plotting) stays with the caller."""
 from typing import Iterable, Optional
@@ -65,3 +66,44 @@ def train_epoch(model, dataloader: Iterable[dict], optimizer, criterion, max_bat
         epoch_losses.append(loss.item())
         batches.append(batch)
     return float(np.mean(epoch_losses)) if epoch_losses else float("nan"), batches
+
+
+def _hits(output, batch, criterion=None):
+    """training/pointcloud/pointnet2.py:42 / :60: torch.sum(torch.argmax(class_pred, -1) == batch.y) / len(class_pred).  The
+    criterion's kernel has counted the hits of this very call already (losses.CrossEntropyLoss.last_correct); any other
+    criterion, and the validation loop, take the line as written."""
+    n = len(output.class_pred)
+    hits = getattr(criterion, "last_correct", None)
+    if hits is not None and hits.shape[0] == n:
+        return int(hits.sum().item()) / n
+    y = batch.y.to(output.class_pred.device)
+    return torch.sum(torch.argmax(output.class_pred.detach(), dim=-1) == y).item() / n
+
+
+def train_pointnet_epoch(model, dataloader: Iterable, optimizer, criterion, max_batches: Optional[int] = None):
+    """One pass of the pre-training loop (training/pointcloud/pointnet2.py:24-49) over `dataloader`: batches with .x, .pos,
+    .batch and the class labels .y.  model: pointnet2.PointNet2; criterion: losses.CrossEntropyLoss.  Returns (mean loss, mean
+    accuracy) over the batches."""
+    model.train()
+    epoch_losses, epoch_accs = [], []
+    for i_batch, batch in enumerate(dataloader):
+        if max_batches is not None and i_batch >= max_batches:
+            break
+        optimizer.zero_grad()
+        output = model(batch)
+        loss = criterion(output.class_pred, batch.y.to(output.class_pred.device))
+        loss.backward()
+        optimizer.step()
+        epoch_losses.append(loss.item())
+        epoch_accs.append(_hits(output, batch, criterion))
+    if not epoch_losses:
+        return float("nan"), float("nan")
+    return float(np.mean(epoch_losses)), float(np.mean(epoch_accs))
+
+
+@torch.no_grad()
+def val_pointnet_epoch(model, dataloader: Iterable):
+    """training/pointcloud/pointnet2.py:52-67: eval() mode, mean accuracy over the batches."""
+    model.eval()
+    epoch_accs = [_hits(model(batch), batch) for batch in dataloader]
+    return float(np.mean(epoch_accs)) if epoch_accs else float("nan")

@@ -116,25 +116,31 @@ def load_into(model, path):
     return model
 
 
-def fresh_model(precision="f16x3", device="cuda:0"):
+def fresh_model(precision="f16x3", device="cuda:0", pointnet_path=None, pointnet_freeze=False):
+    """pointnet_path / pointnet_freeze: training/args.py's --pointnet_path / --pointnet_freeze (models/object_encoder.py:46-49): start
+    from the trunk pretrain_pointnet.py wrote, optionally keeping it fixed.  Default: the randomly initialised trunk."""
     import torch
     import text2pos_amd as t2p
     from text2pos_amd import synthetic as S
     torch.manual_seed(1234)
-    return t2p.CellRetrievalNetwork(S.LABELS + ["pad"], S.COLOR_NAMES, S.known_words(), S.default_args(), precision=precision).to(device)
+    return t2p.CellRetrievalNetwork(S.LABELS + ["pad"], S.COLOR_NAMES, S.known_words(),
+                                    S.default_args(pointnet_path=pointnet_path, pointnet_freeze=bool(pointnet_freeze)),
+                                    precision=precision).to(device)
 
 
-def trained_model(path=None, precision="f16x3", device="cuda:0", log=None, **kw):
+def trained_model(path=None, precision="f16x3", device="cuda:0", log=None, pointnet_path=None, pointnet_freeze=False, **kw):
     """A model carrying trained weights: from `path` when it exists, else trained here (and written to `path` when given) and
     then - either way - loaded back through the reference-format file, so the weights always took the route a reference
     checkpoint takes.  Returns (model in eval mode, info dict)."""
     import tempfile
     info = {"source": path}
     if path is None or not os.path.exists(path):
-        m = fresh_model(precision, device)
+        m = fresh_model(precision, device, pointnet_path, pointnet_freeze)
         before = hit_at_k_untrained(m)
         t0 = time.perf_counter()
         losses = train(m, log=log, **kw)
+        if pointnet_path is not None:
+            info.update(pointnet_path=pointnet_path, pointnet_freeze=bool(pointnet_freeze))
         info.update(trained_here=True, train_s=round(time.perf_counter() - t0, 1), epoch_losses=[round(v, 4) for v in losses],
                     hit_at_k_before_training=before, **{k: kw.get(k, DEFAULTS[k]) for k in DEFAULTS})
         tmp = None
@@ -168,11 +174,14 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "gpurun_out", "trained.pth"))
     for k, v in DEFAULTS.items():
         ap.add_argument("--" + k.replace("_", "-"), type=type(v), default=v)
+    ap.add_argument("--pointnet-path", default=None, help="start from a pre-trained PointNet++ (pretrain_pointnet.py's file)")
+    ap.add_argument("--pointnet-freeze", action="store_true", help="keep the pre-trained trunk fixed (training/args.py --pointnet_freeze)")
     args = ap.parse_args()
     log = lambda m: print(m, file=sys.stderr, flush=True)
     if os.path.exists(args.out):
         os.unlink(args.out)
-    model, info = trained_model(args.out, log=log, **{k: getattr(args, k) for k in DEFAULTS})
+    model, info = trained_model(args.out, log=log, pointnet_path=args.pointnet_path, pointnet_freeze=args.pointnet_freeze,
+                                **{k: getattr(args, k) for k in DEFAULTS})
     code = model.overflow_detected()
     info["fp16_range_guard_after_hit_at_k"] = "clear" if code == 0 else hex(code)
     print(json.dumps(info))

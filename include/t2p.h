@@ -29,14 +29,14 @@
 extern "C" {
 #endif
 
-#define T2P_ABI_VERSION 29
+#define T2P_ABI_VERSION 30
 #define T2P_DEFAULT_CHUNK_OBJECTS 65000 /* t2p_cell_config.chunk_objects == 0 */
 #define T2P_MAX_CHUNK_OBJECTS 65535     /* 32-bit table offsets / 16-bit local indices: chunk_objects and the largest single
                                            cell may not exceed it (T2P_E_ARG otherwise).  The caller-provided workspace holds
                                            one chunk: ~0.6 MB per object, i.e. ~38 GB at the default chunk for a batch that
                                            fills it (t2p_encode_cells_workspace_bytes gives the exact figure; a second
                                            stream's call needs its own workspace) */
-#define T2P_TUNING_MASK 0x1              /* t2p_cell_config.tuning: the bits that select a built plan */
+#define T2P_TUNING_MASK 0x5              /* t2p_cell_config.tuning: the bits that select a built plan */
 #define T2P_E_ARG (-1)
 #define T2P_E_WORKSPACE (-2)
 #define T2P_E_UNSUPPORTED (-3)
@@ -187,6 +187,9 @@ typedef struct t2p_cell_config {
     /* A/B switch between equivalent execution plans (0 = the default plan):
      *   bit 0: keep the edge rows of repeated points in SA level 1's row lists (default: t2p_dedup_rows drops them; every
      *          output bit is the same either way)
+     *   bit 2: keep the edge rows of repeated centroids in the row list of SA level 2 (default: the centroids FPS
+     *          repeats once an object's distinct positions are used up share one copy of their rows, see
+     *          t2p_group_rows_shared; every output bit is the same either way)
      * Bits outside T2P_TUNING_MASK are refused (T2P_E_ARG).  (Rounds 1-3 kept alternative SA kernels behind further bits; the
      * measured record is docs/notebook.md, the code is in the git history.) */
     int32_t tuning;
@@ -479,6 +482,24 @@ int t2p_sample_group(const float* xyz, int64_t n_obj, int32_t n_pts, const float
 int t2p_group_rows(const float* xyz, int64_t n_obj, int32_t n_pts, const float* radius_host /*[3]*/, int32_t self_loops,
                    uint8_t* const* fps_idx /*[3]*/, uint16_t* const* rows /*[3]*/, uint16_t* const* n_rows /*[3]*/,
                    t2p_stream_t stream);
+/* t2p_group_rows with the row list of SA level 2 in the SHARED form its f16x3 kernel consumes (share_mask bit 1; every other
+ * bit must be clear: levels 1 and 3 have no shared form; n_pts = 256 unless share_mask = 0).  For inspection and tests.
+ * T.FixedPoints draws with replacement, so an object with few base points has few distinct positions; FPS (start at point 0,
+ * ties to the lowest index) takes each once and then picks point 0 for the rest of the level.  Those TAIL centroids - c > 0 with
+ * fps_idx[c] == 0, a suffix of the centroid list - stand at centroid 0's position: their ball-query hits are centroid 0's and
+ * each of their edge rows is centroid 0's row, bit for bit; only the self-loop row (dense row c of the cell's batch) is their
+ * own.  In a shared list
+ *   - a centroid that is not in the tail has its hits and its self-loop row, as in t2p_group_rows;
+ *   - the FIRST tail centroid's hits appear once under the pseudo-centroid code X = 64 in the centroid byte (no self-loop
+ *     flag), followed by its self-loop row ((c | 0x80) << 8 | c);
+ *   - every later tail centroid has its self-loop row only (self_loops = 0: no row at all).
+ * The consumer accumulates the X rows against centroid 0's B row in a slot of their own and takes max(acc[c], acc[X]) for every
+ * tail centroid c - what the full list leaves in acc[c], since max is idempotent.  A shared list is not sorted by centroid;
+ * n_rows, the 0xFFFF terminator and the alignment are those of t2p_group_rows.  t2p_edge_counts / t2p_edge_expand and
+ * t2p_dedup_rows take full lists only. */
+int t2p_group_rows_shared(const float* xyz, int64_t n_obj, int32_t n_pts, const float* radius_host /*[3]*/, int32_t self_loops,
+                          int32_t share_mask, uint8_t* const* fps_idx /*[3]*/, uint16_t* const* rows /*[3]*/,
+                          uint16_t* const* n_rows /*[3]*/, t2p_stream_t stream);
 int t2p_edge_counts(const uint16_t* rows, const uint16_t* n_rows, const int32_t* first_obj, int64_t n_obj, int32_t n_dense,
                     int32_t n_cent, int32_t self_loops, int32_t* counts, t2p_stream_t stream);
 int t2p_edge_expand(const uint16_t* rows, const uint16_t* n_rows, const int32_t* first_obj, const int32_t* cent_ptr, int64_t n_obj,

@@ -11,7 +11,7 @@ import torch  # noqa: F401  (must precede CDLL: shares torch's libamdhip64)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("T2P_LIB") or os.path.join(_HERE, "libt2p_hip.so")  # T2P_LIB: A/B builds of the same ABI
-ABI_VERSION = 29
+ABI_VERSION = 30
 
 c_float_p = C.POINTER(C.c_float)
 c_void = C.c_void_p
@@ -118,6 +118,8 @@ SYMBOLS = {
                                    C.POINTER(c_void), c_void]),
     "t2p_group_rows": (C.c_int, [c_void, C.c_int64, C.c_int32, c_float_p, C.c_int32, C.POINTER(c_void), C.POINTER(c_void),
                                  C.POINTER(c_void), c_void]),
+    "t2p_group_rows_shared": (C.c_int, [c_void, C.c_int64, C.c_int32, c_float_p, C.c_int32, C.c_int32, C.POINTER(c_void),
+                                        C.POINTER(c_void), C.POINTER(c_void), c_void]),
     "t2p_edge_counts": (C.c_int, [c_void, c_void, c_void, C.c_int64, C.c_int32, C.c_int32, C.c_int32, c_void, c_void]),
     "t2p_edge_expand": (C.c_int, [c_void, c_void, c_void, c_void, C.c_int64, C.c_int32, C.c_int32, C.c_int32, c_void, c_void, c_void]),
     "t2p_dedup_rows": (C.c_int, [c_void, c_void, C.c_int64, C.c_int32, c_void, c_void, c_void]),

@@ -311,11 +311,7 @@ int encode_chunk(const float* xyz, const float* rgb, const float* center, const 
         gt.H1 = Geo::H[0];
         gt.guard = guard;
 
-        T2P_TRY(launch_sample_group(xyz, n, cfg.n_pts, cfg.radius, gt, st));
-        // level 0: edges of repeated points leave the row list (same max-aggregate, -36 % SA1 rows on the synthetic cells)
-        if (!(cfg.tuning & 1) && cfg.n_pts == 256)
-            T2P_TRY(launch_dedup_rows(xyz, rgb, n, cfg.n_pts, gt.rows[0], gt.n_rows[0], g.nc[0], st));
-        // the per-centroid row counts of all three levels exist now: cut every level's balanced object ranges at once
+        // the launch shapes of the three SA levels (which kernel runs a level decides its row-list form and its balancing)
         SaParams bp[3] = {};
         for (int l = 0; l < 3; l++) {
             bp[l].n_rows = gt.n_rows[l];
@@ -328,6 +324,15 @@ int encode_chunk(const float* xyz, const float* rgb, const float* center, const 
             bp[l].n_cent = g.nc[l];
         }
         bp[0].w1 = sa1_points ? W.sa_w1[0] : nullptr;
+        // level 2: the centroids FPS repeats once an object's distinct positions are used up share one copy of their edge rows
+        // (GroupTables::share_tail; same bits, -13 % rows on the synthetic cells) where k_sa_rows consumes them
+        for (int l = 0; l < 3; l++) gt.share_tail[l] = sa_shares_tail_rows(l, Geo::H[l], Geo::C[l], bp[l], cfg.n_pts, cfg.tuning) ? 1 : 0;
+
+        T2P_TRY(launch_sample_group(xyz, n, cfg.n_pts, cfg.radius, gt, st));
+        // level 0: edges of repeated points leave the row list (same max-aggregate, -36 % SA1 rows on the synthetic cells)
+        if (!(cfg.tuning & 1) && cfg.n_pts == 256)
+            T2P_TRY(launch_dedup_rows(xyz, rgb, n, cfg.n_pts, gt.rows[0], gt.n_rows[0], g.nc[0], st));
+        // the per-centroid row counts of all three levels exist now: cut every level's balanced object ranges at once
         T2P_TRY(launch_sa_balance_levels(bp, Geo::H, Geo::C, st));
     }
 
@@ -1052,6 +1057,27 @@ int t2p_group_rows(const float* xyz, int64_t n_obj, int32_t n_pts, const float* 
         gt.n_rows[l] = n_rows[l];
         gt.n_dense[l] = g.nd[l];
         gt.n_cent[l] = g.nc[l];
+    }
+    return launch_sample_group(xyz, n_obj, n_pts, radius_host, gt, (hipStream_t)stream);
+}
+
+int t2p_group_rows_shared(const float* xyz, int64_t n_obj, int32_t n_pts, const float* radius_host, int32_t self_loops,
+                          int32_t share_mask, uint8_t* const* fps_idx, uint16_t* const* rows, uint16_t* const* n_rows,
+                          t2p_stream_t stream) {
+    T2P_CHECK_ARG(xyz && radius_host && fps_idx && rows && n_rows, "group_rows_shared: NULL argument");
+    T2P_CHECK_ARG((share_mask & ~2) == 0, "group_rows_shared: share_mask=%#x (bit 1: SA level 2; no other level has a shared form)", share_mask);
+    T2P_CHECK_ARG(share_mask == 0 || n_pts == 256, "group_rows_shared: shared lists exist for 256 points per object (n_pts = %d)", n_pts);
+    Geo g(n_pts);
+    GroupTables gt{};
+    gt.self_loops = self_loops ? 1 : 0;
+    for (int l = 0; l < 3; l++) {
+        T2P_CHECK_ARG(fps_idx[l] && rows[l] && n_rows[l], "group_rows_shared: NULL table of level %d", l);
+        gt.fps_idx[l] = fps_idx[l];
+        gt.rows[l] = rows[l];
+        gt.n_rows[l] = n_rows[l];
+        gt.n_dense[l] = g.nd[l];
+        gt.n_cent[l] = g.nc[l];
+        gt.share_tail[l] = (share_mask >> l) & 1;
     }
     return launch_sample_group(xyz, n_obj, n_pts, radius_host, gt, (hipStream_t)stream);
 }

@@ -17,6 +17,9 @@
 //     address so that the lane-linear LDS image is read conflict-free with ds_read_b128; counted s_waitcnt vmcnt(8), never vmcnt(0)
 //     inside the stream.  Round 6 (default): every lane loads its own operand bytes straight into registers - T2P_ROWS_DIRECT below;
 //   * the row lists and centroid positions of the objects ahead travel by LDS-DMA;
+//   * the rows of repeated centroids arrive once (GroupTables::share_tail): centroid code NC names one more accumulator row, whose B row
+//     is centroid 0's (table row = code & (NC - 1)); the drain folds it into every tail centroid's row first (max is idempotent: the
+//     same bits as the full list).  The tile loop is the same for both list forms; an object without a tail pays one ballot;
 //   * natural k order (lane half h owns k = 16 s + 8 h .. + 7 of MFMA step s): the host's register-order weight image is
 //     re-indexed at load time; every fp32 accumulation runs hi.hi, hi.lo, lo.hi per step like ws_sa2.hip, with another
 //     grouping of the k's (results agree to fp32 rounding, not bit for bit).
@@ -125,7 +128,8 @@ struct RowsCfg {
     static constexpr int CPOS_BUF = 3 * NC * 4;
     // LDS map (bytes)
     static constexpr int ACC_OFF = 0;
-    static constexpr int BT_OFF = ACC_OFF + NC * N * 4;
+    static constexpr int XROW = kSaTailCode;             // accumulator row of the shared tail rows (GroupTables::share_tail)
+    static constexpr int BT_OFF = ACC_OFF + (NC + 1) * N * 4;
     static constexpr int ROWS_OFF = BT_OFF + NC * BT_STRIDE;
     static constexpr int CPOS_OFF = ROWS_OFF + 3 * ROWS_BUF;
     static constexpr int NR_OFF = CPOS_OFF + 2 * CPOS_BUF;
@@ -135,6 +139,8 @@ struct RowsCfg {
     static constexpr size_t lds_bytes() { return (size_t)RING_OFF + (T2P_ROWS_DIRECT ? (size_t)0 : (size_t)NW * RING_BYTES); }
     static_assert(K % 32 == 0 && N % 32 == 0 && NC % 64 == 0 && (NC * N / 4) % NT == 0, "shape");
     static_assert(SLOTS == 4, "the counted waits below assume four ring slots per tile (K = 128)");
+    // the tail code is accumulator row NC (its B row is row XROW & (NC - 1) = 0 of the table); its byte offset fits the u16 entries
+    static_assert(XROW == NC && (NC & (NC - 1)) == 0 && XROW * N * 4 <= 0xFFFF && XROW < 128, "shared tail slot");
 };
 
 template <int SEL>
@@ -229,7 +235,7 @@ __global__ __launch_bounds__(64 * NW, 1) void k_sa_rows(SaParams p) {
         dma_chunk[q] = (uint32_t)((((lane & 7) ^ ((r >> 1) & 7))) * 16);
     }
 
-    for (int i = tid; i < NC * N; i += C::NT) acc_lds[i] = (int)0xFF800000;   // -inf
+    for (int i = tid; i < (NC + 1) * N; i += C::NT) acc_lds[i] = (int)0xFF800000;   // -inf (row NC: the shared tail rows)
     int gtop = 0;         // fp16-range guard: this lane's maximum (bit pattern, before out_scale) of the drained outputs; reduced over
                           // the wave once, at the end (six ds_bpermute round trips per drain otherwise)
 
@@ -328,10 +334,28 @@ __global__ __launch_bounds__(64 * NW, 1) void k_sa_rows(SaParams p) {
 #endif
 
         // ---- per-object phases --------------------------------------------------------------------------------------------
-        auto flush = [&](int g) {   // accumulator -> output rows of object g: relu(max + bias); leaves the accumulator at -inf
+        // t0 (uniform): the object's first tail centroid (NC: none).  The tail centroids c >= t0 share the rows accumulated in row
+        // XROW (GroupTables::share_tail): max(acc[c], acc[XROW]) is what the full list would have left in acc[c].
+        auto flush = [&](int g, int t0) {   // accumulator -> output rows of object g: relu(max + bias); leaves the accumulator at -inf
             float* o = p.out + (int64_t)g * NC * (int64_t)p.ldo;
             int top = gtop;
             static_assert(C::NT % (N / 4) == 0, "a thread keeps its column quad over the drain");
+            if (t0 < NC) {   // (uniform over the workgroup) the shared rows first, into the accumulator rows this thread drains below
+                f32x4* const ax = (f32x4*)(acc_lds + C::XROW * N + (tid % (N / 4)) * 4);
+                const f32x4 xq = *ax;
+#pragma unroll 1
+                for (int c = tid / (N / 4); c < NC; c += C::NT / (N / 4)) {   // the rows of the drain loop below
+                    if (c < t0) continue;
+                    f32x4* a = (f32x4*)(acc_lds + c * N + (tid % (N / 4)) * 4);
+                    f32x4 r = *a;
+#pragma unroll
+                    for (int e = 0; e < 4; e++) r[e] = fmaxf(r[e], xq[e]);
+                    *a = r;
+                }
+                lds_barrier_r();   // every thread has read row XROW: back to -inf (barrier B stands before the next object's atomics)
+                typedef int i32x4 __attribute__((ext_vector_type(4)));
+                if (tid < N / 4) *(i32x4*)ax = i32x4{(int)0xFF800000, (int)0xFF800000, (int)0xFF800000, (int)0xFF800000};
+            }
 #pragma unroll
             for (int k = 0; k < NC * N / 4 / C::NT; k++) {
                 const int i = tid + k * C::NT;
@@ -390,6 +414,17 @@ __global__ __launch_bounds__(64 * NW, 1) void k_sa_rows(SaParams p) {
             const int n_g = rows_of(gi), n_g1 = gi + 1 < cnt ? rows_of(gi + 1) : 0;
             const uint32_t sb_g = (uint32_t)__builtin_amdgcn_readfirstlane(sbase[gi]);
             const uint32_t sb_g1 = gi + 1 < cnt ? (uint32_t)__builtin_amdgcn_readfirstlane(sbase[gi + 1]) : 0u;
+            // first tail centroid of the object: c > 0 at centroid 0's position, bit for bit (FPS picked point 0 again, fps_idx[c] == 0:
+            // it only returns to a position it has taken when no other is left, and then to the lowest index).  The positions are in
+            // LDS (build_b read them); lane = centroid.
+            int t0;
+            {
+                static_assert(NC == 64, "one lane per centroid");
+                const uint32_t* cp = (const uint32_t*)(lds + C::CPOS_OFF + ((ga + gi) & 1) * C::CPOS_BUF);
+                const bool same = lane > 0 && cp[lane] == cp[0] && cp[NC + lane] == cp[NC] && cp[2 * NC + lane] == cp[2 * NC];
+                const unsigned long long tm = __ballot(same);
+                t0 = tm ? (int)__builtin_ctzll(tm) : NC;
+            }
             int r0 = wave * 32;
             bool have = r0 < n_g;
             const bool did_tile = have;
@@ -456,7 +491,7 @@ __global__ __launch_bounds__(64 * NW, 1) void k_sa_rows(SaParams p) {
                 {   // step 0 of the wave's first tile in this object: converted here, every later tile's step 0 inside its predecessor's last step
                     if constexpr (!T2P_ROWS_DIRECT) wait_ring();
                     f32x4 x[2], b[2];
-                    read_step(0, (uint32_t)C::BT_OFF + ((m_cur >> 8) & 127u) * (uint32_t)C::BT_STRIDE + (uint32_t)(h * 32), x, b);
+                    read_step(0, (uint32_t)C::BT_OFF + ((m_cur >> 8) & (uint32_t)(NC - 1)) * (uint32_t)C::BT_STRIDE + (uint32_t)(h * 32), x, b);
                     uint32_t nh[4], nl[4];
 #pragma unroll
                     for (int pr = 0; pr < 4; pr++) {
@@ -486,8 +521,8 @@ __global__ __launch_bounds__(64 * NW, 1) void k_sa_rows(SaParams p) {
                 (void)vn;
 #endif
                 // this tile: centroid of the lane's row -> table row, accumulator row
-                const uint32_t dl = (m_cur >> 8) & 127u;
-                const uint32_t brow = (uint32_t)C::BT_OFF + dl * (uint32_t)C::BT_STRIDE + (uint32_t)(h * 32);
+                const uint32_t dl = (m_cur >> 8) & 127u;     // accumulator row: a centroid, or XROW = NC for the shared tail rows ...
+                const uint32_t brow = (uint32_t)C::BT_OFF + (dl & (uint32_t)(NC - 1)) * (uint32_t)C::BT_STRIDE + (uint32_t)(h * 32);   // ... whose B row is centroid 0's
                 // (inline asm: hipcc puts s_waitcnt vmcnt(0) in front of an ordinary LDS access it cannot separate from the
                 // outstanding LDS-DMA pieces, which would drain the ring once per tile)
                 asm volatile("ds_write_b16 %0, %1" ::"v"(dstl_addr + (uint32_t)(rr * 2)), "v"(dl * (uint32_t)(N * 4)) : "memory");
@@ -539,7 +574,7 @@ __global__ __launch_bounds__(64 * NW, 1) void k_sa_rows(SaParams p) {
 #else
                             if (c == 4) tile_voff(rowbyte_n, vn);
 #endif
-                            if (c == 6) brow_n = (uint32_t)C::BT_OFF + ((m_nxt >> 8) & 127u) * (uint32_t)C::BT_STRIDE + (uint32_t)(h * 32);
+                            if (c == 6) brow_n = (uint32_t)C::BT_OFF + ((m_nxt >> 8) & (uint32_t)(NC - 1)) * (uint32_t)C::BT_STRIDE + (uint32_t)(h * 32);
                         }
 #if T2P_ROWS_DIRECT
                         {   // this chunk's load, if the schedule has one (rows_load_slot): at most one per MFMA gap
@@ -623,7 +658,7 @@ __global__ __launch_bounds__(64 * NW, 1) void k_sa_rows(SaParams p) {
             // counted wait has since retired - unless the wave had no tile here
             if (!did_tile) wait_all_vm();
             if constexpr (!(T2P_RABL & 16)) lds_barrier_r();    // A: all atomics of object gi are in the accumulator
-            if constexpr (!(T2P_RABL & 4)) flush(ga + gi);
+            if constexpr (!(T2P_RABL & 4)) flush(ga + gi, t0);
             if (gi + 1 < cnt) {
                 if constexpr (!(T2P_RABL & 4)) build_b(ga + gi + 1);
                 if (gi + 3 < cnt) dma_rows(ga + gi + 3);

@@ -106,6 +106,7 @@ __device__ void level(const float* px, const float* py, const float* pz, int n_d
     // of centroid c -- same dist2() call, so the same bits as two separate passes.
     // The hits are emitted as the object's compact edge-row list (sorted by centroid), one u16 per row: low byte =
     // source (dense index; for a self-loop row: the centroid index), high byte = centroid | 0x80 if self loop.
+    // (level_fast may list the hits of repeated centroids once, under a pseudo-centroid code: GroupTables::share_tail.)
     int cur = 0;
     int base = 0;
     for (int c = 0; c < n_c; c++) {
@@ -170,9 +171,15 @@ __device__ void level(const float* px, const float* py, const float* pz, int n_d
 //   * the 32-neighbour cap is tested once per centroid (uniform) instead of once per point;
 //   * the lane's farthest point is found with max() and located only afterwards (lowest j that equals the wave maximum:
 //     the first point a strict '>' scan would have kept).
-template <int PPL>
+// SHARE (GroupTables::share_tail, SA level 2): once FPS picks point 0 again (cur == 0 at c > 0) every distinct position
+// has been taken - all running minima are 0, the tie goes to index 0, and measuring against point 0 again changes nothing, so
+// every later centroid is point 0 too.  These TAIL centroids stand at centroid 0's position: same hits, same edge rows.  The
+// first of them lists its hits once under the pseudo-centroid code `tail_code`; each tail centroid adds only its self-loop row,
+// and the later ones skip the distance pass altogether.  fps_idx and the centroid positions come out as without SHARE.
+template <int PPL, bool SHARE = false>
 __device__ void level_fast(const float* px, const float* py, const float* pz, int n_c, float r2, uint8_t* sel, float* qx,
-                           float* qy, float* qz, uint16_t* __restrict__ rows_out, int self_loops, int* n_rows_out) {
+                           float* qy, float* qz, uint16_t* __restrict__ rows_out, int self_loops, int* n_rows_out,
+                           int tail_code = 0) {
     const int lane = threadIdx.x;
     const int i0 = lane * PPL;
     float x[PPL], y[PPL], z[PPL];
@@ -186,6 +193,7 @@ __device__ void level_fast(const float* px, const float* py, const float* pz, in
     }
     int cur = 0;
     int base = 0;
+    [[maybe_unused]] bool tail_open = false;   // SHARE: the tail's hits are in the list
     for (int c = 0; c < n_c; c++) {
         const float cx = px[cur], cy = py[cur], cz = pz[cur];
         if (lane == 0) {
@@ -193,6 +201,16 @@ __device__ void level_fast(const float* px, const float* py, const float* pz, in
             qx[c] = cx;
             qy[c] = cy;
             qz[c] = cz;
+        }
+        bool tail = false;   // (uniform)
+        if constexpr (SHARE) {
+            tail = c > 0 && cur == 0;
+            if (tail && tail_open) {   // a later tail centroid: its self-loop row only; cur stays 0
+                if (self_loops && lane == 0) rows_out[(uint32_t)base] = (uint16_t)(((c | 0x80) << 8) | c);
+                base += self_loops ? 1 : 0;
+                continue;
+            }
+            tail_open = tail;
         }
         float d[PPL];
         unsigned long long m[PPL];
@@ -231,7 +249,7 @@ __device__ void level_fast(const float* px, const float* py, const float* pz, in
             lower = __builtin_amdgcn_mbcnt_hi((uint32_t)(m[j] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m[j], lower));
             count += __popcll(m[j]);
         }
-        const uint32_t tag = (uint32_t)c << 8;
+        const uint32_t tag = (uint32_t)(tail ? tail_code : c) << 8;
         // (unsigned 32-bit row positions from the object's uniform base: the stores then take their address as SGPR base +
         // 32-bit lane offset instead of a 64-bit address built on the VALU - 8 of this loop's ~85 VALU instructions)
         char* const rows_b = (char*)rows_out;   // byte offsets: SGPR base + 32-bit lane offset, no shift per store
@@ -409,6 +427,9 @@ __global__ __launch_bounds__(64, T2P_SG_WAVES) void k_sample_group(const float* 
                 if (l == 0)
                     level_fast<4>(pin[l][0], pin[l][1], pin[l][2], n_c, rr[l], sel_lds, pin[l + 1][0], pin[l + 1][1],
                                   pin[l + 1][2], g_rows16, gt.self_loops, &n_rows);
+                else if (l == 1 && gt.share_tail[1])
+                    level_fast<2, true>(pin[l][0], pin[l][1], pin[l][2], n_c, rr[l], sel_lds, pin[l + 1][0], pin[l + 1][1],
+                                        pin[l + 1][2], g_rows16, gt.self_loops, &n_rows, kSaTailCode);
                 else if (l == 1)
                     level_fast<2>(pin[l][0], pin[l][1], pin[l][2], n_c, rr[l], sel_lds, pin[l + 1][0], pin[l + 1][1],
                                   pin[l + 1][2], g_rows16, gt.self_loops, &n_rows);

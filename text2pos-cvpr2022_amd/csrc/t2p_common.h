@@ -194,6 +194,14 @@ struct GroupTables {
     uint16_t* rows[3];    // [n_obj, n_cent[l]*33]  (centroid | self-loop flag 0x80) << 8 | source index, sorted by centroid
     uint16_t* n_rows[3];  // [n_obj] rows in the list (ball-query hits + one self loop per centroid when self_loops)
     int self_loops;
+    // share_tail[l] != 0 (level index 1 = SA level 2 of the 256-point fast path only; level_fast): the object's TAIL centroids - c > 0 with
+    // fps_idx[c] == 0: FPS has run out of distinct positions and picks point 0 again, for the rest of the level - share one copy of
+    // their ball-query hits.  A tail centroid stands at centroid 0's position, so its hits are centroid 0's hits and each of its
+    // edge rows relu(A_j - B_c) is centroid 0's, bit for bit; only its self-loop row (dense row `c` of the cell's batch) is its
+    // own.  The first tail centroid's hits are listed ONCE under the pseudo-centroid code kSaTailCode (a shared
+    // accumulator slot whose B row is centroid 0's), every tail centroid keeps its self-loop row, and the consumer's drain takes
+    // max(acc[c], acc[code]) for tail centroids.  The list is then no longer sorted by centroid.
+    int share_tail[3];
     int n_dense[3];
     int n_cent[3];
     // Optional layer-1 tables written by the same kernel (it is VALU-bound and leaves the memory pipes idle; as separate
@@ -336,6 +344,9 @@ int launch_ws_sa(int H, int C, const SaParams& p, hipStream_t st);
 // sa_x3.hip: f16x3 kernel of any level shape (runtime n_dense / n_cent, n_cent * C <= 8192), centroid table B from HBM (Bc)
 int launch_sa_x3(int H, int C, const SaParams& p, hipStream_t st);
 int sa_x3_launch_shape(int H, int C, int64_t n_obj, int* tile_rows, int* n_wg);
+// Pseudo-centroid code of the shared tail rows (GroupTables::share_tail) in the centroid byte of a row of SA level 2: 64, the
+// first free value of the 7-bit field behind its 64 centroids; 64 * C * 4 fits the u16 accumulator offsets of k_sa_rows.
+constexpr int kSaTailCode = 64;
 // sa_rows.hip: row-owning f16x3 kernel of SA level 2 (H = C = 128, LDS centroid table): true when launch_ws_sa routes p there
 bool sa_rows_selected(int H, int C, const SaParams& p);
 int launch_sa_rows(int H, int C, const SaParams& p, hipStream_t st);
@@ -348,6 +359,12 @@ int sa_points_launch_shape(int64_t n_obj, int* tile_rows, int* n_wg);
 bool sa3_selected(int H, int C, const SaParams& p);
 int launch_sa3(const SaParams& p, hipStream_t st);
 int sa3_launch_shape(int64_t n_obj, int* tile_rows, int* n_wg);
+// Whether level l's row lists may share the rows of repeated (tail) centroids: only k_sa_rows (level index 1) owns the extra
+// accumulator slot, only the 256-point fast path of k_sample_group writes the shared form, and tuning bit 0x4 keeps the full
+// lists.  p: the level's SaParams as launch_ws_sa will see them (W_x3, wp, n_dense, n_cent).
+inline bool sa_shares_tail_rows(int l, int H, int C, const SaParams& p, int n_pts, int tuning) {
+    return l == 1 && n_pts == 256 && !(tuning & 4) && p.n_dense == 128 && p.n_cent == 64 && sa_rows_selected(H, C, p);
+}
 // One launch that balances all three levels (their row counts are known once k_sample_group has run); fills
 // prefix_ws / bounds_ws of every p[l] for the launch shape launch_ws_sa(H[l], C[l], p[l]) will use.
 int launch_sa_balance_levels(const SaParams p[3], const int H[3], const int C[3], hipStream_t st);

@@ -230,6 +230,30 @@ def group_edges(xyz: torch.Tensor, first_obj: torch.Tensor, radius=(0.2, 0.3, 0.
     return out
 
 
+def group_rows(xyz: torch.Tensor, radius=(0.2, 0.3, 0.4), self_loops: bool = True, share_mask: int = 0):
+    """k_sample_group's compact edge-row lists of the three SA levels (t2p_group_rows_shared).  xyz [n_obj, n_pts, 3] fp32.
+    share_mask: bit 1 = SA level 2 in the shared form its f16x3 kernel consumes (the hits of the centroids that repeat
+    centroid 0 once, under the pseudo-centroid code 64: include/t2p.h); 0 = full lists, any n_pts.
+    Returns dict(fps_idx=[3 x uint8 [n_obj, n_c]], rows=[3 x int16 [n_obj, n_c * 33]] (uint16 bits), n_rows=[3 x int16 [n_obj]])."""
+    _need(xyz, "xyz", torch.float32, 3)
+    dev = xyz.device
+    n_obj, n_pts, three = xyz.shape
+    if three != 3:
+        raise RuntimeError(f"xyz: last dimension must be 3, got {three}")
+    nd, out = n_pts, dict(fps_idx=[], rows=[], n_rows=[])
+    for _ in range(3):
+        nc = (nd + 1) // 2
+        out["fps_idx"].append(torch.empty((n_obj, nc), dtype=torch.uint8, device=dev))
+        out["rows"].append(torch.empty((n_obj, nc * 33), dtype=torch.int16, device=dev))
+        out["n_rows"].append(torch.empty((n_obj,), dtype=torch.int16, device=dev))
+        nd = nc
+    arr = lambda ts: (C.c_void_p * 3)(*[t.data_ptr() for t in ts])
+    r = (C.c_float * 3)(*[float(v) for v in radius])
+    L.check(L.lib().t2p_group_rows_shared(_ptr(xyz), n_obj, n_pts, r, int(bool(self_loops)), int(share_mask), arr(out["fps_idx"]),
+                                          arr(out["rows"]), arr(out["n_rows"]), _stream(dev)), "t2p_group_rows_shared")
+    return out
+
+
 def dedup_rows(xyz: torch.Tensor, rgb: torch.Tensor, rows: torch.Tensor, n_rows: torch.Tensor):
     """In-place t2p_dedup_rows: rows uint16 [n_obj, (n_pts / 2) * 33] (as int16 storage), n_rows uint16 [n_obj] (int16)."""
     _need(xyz, "xyz", torch.float32, 3)

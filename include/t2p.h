@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define T2P_ABI_VERSION 30
+#define T2P_ABI_VERSION 31
 #define T2P_DEFAULT_CHUNK_OBJECTS 65000 /* t2p_cell_config.chunk_objects == 0 */
 #define T2P_MAX_CHUNK_OBJECTS 65535     /* 32-bit table offsets / 16-bit local indices: chunk_objects and the largest single
                                            cell may not exceed it (T2P_E_ARG otherwise).  The caller-provided workspace holds
@@ -325,6 +325,38 @@ int t2p_match(const float* desc0, const float* desc1, int64_t batch, int32_t n_o
               const t2p_match_weights* w, int32_t sinkhorn_iters, float match_threshold, float* P, int64_t* matches0,
               int64_t* matches1, float* mscores0, float* mscores1, float* offsets, void* workspace,
               size_t workspace_bytes, t2p_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Fine stage in train() mode (csrc/match_train.hip): what SuperGlueMatch.forward needs besides row GEMMs and batch-statistics
+ * BatchNorm, and the two loss values of training/fine.py:56-59.  BatchNorm takes its statistics over all object tokens of the
+ * batch, then over all hint tokens (models/superglue.py:119-129 called twice per layer, :139-146), so the token rows are
+ * SET-major here: rows [0, B n_obj) the object tokens (row b n_obj + i), rows [B n_obj, B (n_obj + n_hints)) the hint tokens
+ * (row B n_obj + b n_hints + j).  1 <= n_obj, n_hints <= 63 (T2P_E_ARG otherwise), embed_dim in {64, 128, 256}
+ * (T2P_E_UNSUPPORTED otherwise); refused before any launch.  fp32 in and out; deterministic (no atomics).
+ * ---------------------------------------------------------------------------------------------------------- */
+/* MultiHeadedAttention of one GNN layer without its projections (models/superglue.py:90-116: attention, the head split of
+ * :107-109 - channel c belongs to head c % 4 - and the merge of the heads' outputs into one row; the Conv1d projections and
+ * `merge` are row GEMMs of the caller).  qkv [B (n_obj + n_hints)][3 D]: q | k | v of every token; cross = 0: a token attends to
+ * its own set, 1: to the other set of its sample (models/superglue.py:139-143).  msg [B (n_obj + n_hints)][D]. */
+int t2p_match_attention(const float* qkv, int64_t batch, int32_t n_obj, int32_t n_hints, int32_t embed_dim, int32_t cross,
+                        float* msg, t2p_stream_t stream);
+/* The optimal-transport head of SuperGlue.forward (models/superglue.py:283-322 with log_optimal_transport :149-177) on
+ * mdesc [B (n_obj + n_hints)][D] = final_proj of the token rows: scores m0 m1^T / sqrt(D), dustbin row and column bin_score,
+ * sinkhorn_iters log-space iterations (carried in float64), P = exp(Z) [B][n_obj + 1][n_hints + 1], mutual nearest neighbours
+ * of the inner block with match_threshold: matches0 [B][n_obj], matches1 [B][n_hints] int64 (-1 = none), matching scores fp32.
+ * The offset MLP (models/superglue_matcher.py:116) is two row GEMMs of the caller. */
+int t2p_match_head(const float* mdesc, int64_t batch, int32_t n_obj, int32_t n_hints, int32_t embed_dim, float bin_score,
+                   int32_t sinkhorn_iters, float match_threshold, float* P, int64_t* matches0, int64_t* matches1, float* mscores0,
+                   float* mscores1, t2p_stream_t stream);
+/* MatchingLoss.forward (training/losses.py:20-30) in one launch.  P [B][n_obj + 1][n_hints + 1]; idx int32 [n_entries][2]: the
+ * (object, hint) pairs of all samples back to back, entry_ptr int32 [B + 1] their CSR over the samples.
+ * sample_loss [B] = mean over the sample's entries of -log P[b, i, j]; loss [1] = mean of sample_loss; terms accumulated in
+ * float64 in a fixed order.  An entry outside [0, n_obj] x [0, n_hints], an empty sample or a row pointer outside
+ * [0, n_entries] gives NaN in that sample's loss (and so in loss); nothing is read through it. */
+int t2p_matching_loss(const float* P, int64_t batch, int32_t n_obj, int32_t n_hints, const int32_t* idx, const int32_t* entry_ptr,
+                      int64_t n_entries, float* sample_loss, float* loss, t2p_stream_t stream);
+/* nn.MSELoss() (mean reduction; training/fine.py:36, :57-59) of a, b [n] fp32 -> loss [1]; float64 accumulation in a fixed order. */
+int t2p_mse_loss(const float* a, const float* b, int64_t n, float* loss, t2p_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Text branch: CellRetrievalNetwork.encode_text (models/cell_retrieval.py:69-75) on token ids produced by the

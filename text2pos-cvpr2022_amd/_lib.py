@@ -11,7 +11,7 @@ import torch  # noqa: F401  (must precede CDLL: shares torch's libamdhip64)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("T2P_LIB") or os.path.join(_HERE, "libt2p_hip.so")  # T2P_LIB: A/B builds of the same ABI
-ABI_VERSION = 30
+ABI_VERSION = 31
 
 c_float_p = C.POINTER(C.c_float)
 c_void = C.c_void_p
@@ -111,6 +111,11 @@ SYMBOLS = {
     "t2p_match": (C.c_int, [c_void, c_void, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(MatchWeights),
                             C.c_int32, C.c_float, c_void, c_void, c_void, c_void, c_void, c_void, c_void, C.c_size_t,
                             c_void]),
+    "t2p_match_attention": (C.c_int, [c_void, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_void, c_void]),
+    "t2p_match_head": (C.c_int, [c_void, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_float, c_void, c_void,
+                                 c_void, c_void, c_void, c_void]),
+    "t2p_matching_loss": (C.c_int, [c_void, C.c_int64, C.c_int32, C.c_int32, c_void, c_void, C.c_int64, c_void, c_void, c_void]),
+    "t2p_mse_loss": (C.c_int, [c_void, c_void, C.c_int64, c_void, c_void]),
     "t2p_profile_enable": (None, [C.c_int]),
     "t2p_profile_report": (C.c_int, [C.c_char_p, C.c_size_t]),
     "t2p_profile_repeat": (None, [C.c_char_p, C.c_int32]),

@@ -860,6 +860,71 @@ def lstm_cell_backward(dh_gemm, dh_carry_in, dc_in, gates, c_prev, c, lengths, s
                                            _ptr(dc_out), _ptr(dh_carry_out), _stream(dev)), "t2p_lstm_cell_backward")
 
 
+# ---- fine stage in train() mode (csrc/match_train.hip): token rows set-major, see include/t2p.h -----------------------------
+def match_attention(qkv: torch.Tensor, batch: int, n_obj: int, n_hints: int, cross: bool) -> torch.Tensor:
+    """qkv [B (n_obj + n_hints), 3 D] (q | k | v of the set-major token rows) -> the heads' messages [B (n_obj + n_hints), D] of
+    one GNN layer (t2p_match_attention); cross: a token attends to the other set of its sample."""
+    _need(qkv, "qkv", torch.float32, 2)
+    rows = int(batch) * (int(n_obj) + int(n_hints))
+    if qkv.shape[0] != rows or qkv.shape[1] % 3:
+        raise RuntimeError(f"match_attention: qkv is {tuple(qkv.shape)}, expected [{rows}, 3 D]")
+    d = qkv.shape[1] // 3
+    msg = torch.empty((rows, d), dtype=torch.float32, device=qkv.device)
+    L.check(L.lib().t2p_match_attention(_ptr(qkv), int(batch), int(n_obj), int(n_hints), d, int(bool(cross)), _ptr(msg),
+                                        _stream(qkv.device)), "t2p_match_attention")
+    return msg
+
+
+def match_head(mdesc: torch.Tensor, batch: int, n_obj: int, n_hints: int, bin_score: float, sinkhorn_iters: int,
+               threshold: float = 0.2):
+    """mdesc [B (n_obj + n_hints), D] (final_proj of the set-major token rows) -> dict(P [B, n_obj + 1, n_hints + 1],
+    matches0 [B, n_obj] / matches1 [B, n_hints] int64, matching_scores0/1) of t2p_match_head."""
+    _need(mdesc, "mdesc", torch.float32, 2)
+    dev = mdesc.device
+    b, m, n = int(batch), int(n_obj), int(n_hints)
+    if mdesc.shape[0] != b * (m + n):
+        raise RuntimeError(f"match_head: mdesc is {tuple(mdesc.shape)}, expected [{b * (m + n)}, D]")
+    out = dict(P=torch.empty((b, m + 1, n + 1), dtype=torch.float32, device=dev),
+               matches0=torch.empty((b, m), dtype=torch.int64, device=dev),
+               matches1=torch.empty((b, n), dtype=torch.int64, device=dev),
+               matching_scores0=torch.empty((b, m), dtype=torch.float32, device=dev),
+               matching_scores1=torch.empty((b, n), dtype=torch.float32, device=dev))
+    L.check(L.lib().t2p_match_head(_ptr(mdesc), b, m, n, mdesc.shape[1], float(bin_score), int(sinkhorn_iters), float(threshold),
+                                   _ptr(out["P"]), _ptr(out["matches0"]), _ptr(out["matches1"]), _ptr(out["matching_scores0"]),
+                                   _ptr(out["matching_scores1"]), _stream(dev)), "t2p_match_head")
+    return out
+
+
+def matching_loss(P: torch.Tensor, idx: torch.Tensor, entry_ptr: torch.Tensor):
+    """P [B, n_obj + 1, n_hints + 1] fp32, idx int32 [n_entries, 2], entry_ptr int32 [B + 1] (CSR of the entries over the
+    samples) -> (loss [1], sample_loss [B]) of t2p_matching_loss; a bad entry or an empty sample shows as NaN."""
+    _need(P, "P", torch.float32, 3)
+    dev = P.device
+    _need(idx, "idx", torch.int32, 2, dev)
+    _need(entry_ptr, "entry_ptr", torch.int32, 1, dev)
+    b = P.shape[0]
+    if idx.shape[1] != 2 or entry_ptr.numel() != b + 1:
+        raise RuntimeError(f"matching_loss: idx {tuple(idx.shape)} must be [n_entries, 2] and entry_ptr [{b + 1}]")
+    if b < 1 or P.shape[1] < 2 or P.shape[2] < 2:
+        raise RuntimeError(f"matching_loss: P {tuple(P.shape)} must be [B >= 1, n_obj + 1, n_hints + 1]")
+    sample_loss = torch.empty((b,), dtype=torch.float32, device=dev)
+    loss = torch.empty((1,), dtype=torch.float32, device=dev)
+    L.check(L.lib().t2p_matching_loss(_ptr(P), b, P.shape[1] - 1, P.shape[2] - 1, _ptr(idx), _ptr(entry_ptr), idx.shape[0],
+                                      _ptr(sample_loss), _ptr(loss), _stream(dev)), "t2p_matching_loss")
+    return loss, sample_loss
+
+
+def mse_loss(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """mean((a - b)^2) of two equal-shaped fp32 tensors -> [1] (t2p_mse_loss)."""
+    _need(a, "input", torch.float32)
+    _need(b, "target", torch.float32, None, a.device)
+    if a.shape != b.shape:
+        raise RuntimeError(f"mse_loss: shapes {tuple(a.shape)} and {tuple(b.shape)} differ")
+    loss = torch.empty((1,), dtype=torch.float32, device=a.device)
+    L.check(L.lib().t2p_mse_loss(_ptr(a), _ptr(b), a.numel(), _ptr(loss), _stream(a.device)), "t2p_mse_loss")
+    return loss
+
+
 # ---------------------------------------------------------------------------------------------------------------
 def profile_enable(on: bool):
     """Bracket every kernel launch with hipEvents on its launch stream (bench.py's live per-kernel timing)."""

@@ -7,7 +7,8 @@ checkpoints load with strict=True), with the arithmetic executed by libt2p_hip.s
   SuperGlue.forward + mlp_offsets (models/superglue.py:239-330, models/superglue_matcher.py:116) -> t2p_match (csrc/match.hip)
 
 Callers that drop in unchanged: evaluation/pipeline.py:189-191 (run_fine) and training/fine.py's eval loop.
-Forward-only, eval mode (SURVEY.md 8(f) #4 is the training row).
+In train() mode (under no_grad: training/fine.py validates without calling eval()) the same outputs come from the unfolded,
+batch-statistics path of train_cell.py / train_match.py.  Forward-only: the backward of the matcher is not built.
 """
 from copy import deepcopy
 from typing import List
@@ -138,9 +139,11 @@ class SuperGlueMatch(PicklableModule):
         return self._mpack[2]
 
     def _check_forward_only(self):
-        if self.training:
-            raise NotImplementedError("training-mode forward (batch-statistics BatchNorm) is not built; call .eval()")
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            if self.training:
+                raise NotImplementedError("the backward of the matcher is not built (multi-head attention, the optimal-"
+                                          "transport head and the two fine losses are forward-only): run the training-mode "
+                                          "forward under torch.no_grad()")
             raise NotImplementedError("the HIP path is forward-only; call it under torch.no_grad()")
 
     # ---- forward ----------------------------------------------------------------------------------------------------
@@ -182,6 +185,8 @@ class SuperGlueMatch(PicklableModule):
                                    radius=self.object_encoder.pointnet.radii, precision=self.precision,
                                    class_idx=class_idx, color_idx=color_idx, objects_only=True)
         dev = self.device
+        if self.training:
+            return self._forward_train(xyz, rgb, center, mean_rgb, cp, hints, b, n_obj, n_hints, class_idx, color_idx)
         if self.precision == "f16x3":
             if self._overflow is None or self._overflow.device != dev:
                 self._overflow = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -208,6 +213,26 @@ class SuperGlueMatch(PicklableModule):
         if check_overflow and self.overflow_detected():
             raise FloatingPointError("f16x3 path: an object-encoder activation left fp16's range; construct the model "
                                      "with precision=\"fp32\"")
+        return MatchOutputs(P=out["P"], matches0=out["matches0"], matches1=out["matches1"], offsets=out["offsets"],
+                            matching_scores0=out["matching_scores0"], matching_scores1=out["matching_scores1"],
+                            object_encodings=obj, hint_encodings=hint)
+
+    def _forward_train(self, xyz, rgb, center, mean_rgb, cp, hints, b, n_obj, n_hints, class_idx, color_idx):
+        """train() mode under no_grad (training/fine.py:119-208 validates in this mode): batch statistics in every BatchNorm - per
+        sample inside the PointNet++, which the reference runs once per sample, over the batch elsewhere, over all object tokens and
+        then all hint tokens in the GNN - and the running estimates move as the reference's module calls move them.  Exact fp32
+        (train_cell.py / train_match.py); the hint LSTM, which has no BatchNorm, is the eval() one at the model's precision."""
+        from . import train_match as TM
+        d = self.embed_dim
+        TM.check_token_sets(b, n_obj, n_hints, 2 * d)       # before any launch
+        if isinstance(hints, torch.Tensor):
+            hint = hints.contiguous()
+        elif isinstance(hints, tuple):
+            hint = self.language_encoder.encode_tokens(hints[0], hints[1], normalize=True).view(b, n_hints, d)
+        else:
+            hint = self.language_encoder([s for h in hints for s in h], normalize=True).view(b, n_hints, d)   # :94-97
+        obj = TM.encode_objects_fine_train(self, xyz, rgb, center, mean_rgb, cp, class_idx, color_idx).view(b, n_obj, d)
+        out = TM.match_train_forward(self, obj, hint.contiguous())
         return MatchOutputs(P=out["P"], matches0=out["matches0"], matches1=out["matches1"], offsets=out["offsets"],
                             matching_scores0=out["matching_scores0"], matching_scores1=out["matching_scores1"],
                             object_encodings=obj, hint_encodings=hint)

@@ -196,3 +196,67 @@ def make_texts(seed: int, q_lo: int, q_hi: int, n_hints: int = 6):
     d, c, l = pick(10, len(DIRECTIONS)), pick(11, len(COLOR_NAMES)), pick(12, len(LABELS))
     return [" ".join(f"The pose is {DIRECTIONS[d[i, j]]} of a {COLOR_NAMES[c[i, j]]} {LABELS[l[i, j]]}."
                      for j in range(n_hints)) for i in range(q_hi - q_lo)]
+
+
+def make_fine_batch(seed: int, batch: int, n_obj: int = 16, n_hints: int = 6, n_pts: int = 256):
+    """One batch of the fine stage as Kitti360FineDataset.collate_fn builds it (dataloading/kitti360pose/poses.py:160-174, lists
+    over the samples), on the synthetic cells make_cells(seed, batch, fixed_n=n_obj, n_pts=n_pts):
+      objects            B lists of n_obj data.Object3d (centre and colour = the cell's packed means, exactly)
+      object_points      B data.Batch of n_obj * n_pts points (already FixedPoints + NormalizeScale, as the dataset's transform leaves them)
+      hint_descriptions  B lists of n_hints sentences
+      matches            B int64 [k, 2] arrays of (object, hint): the k matched hints of a sample, k ~ U{1 .. min(n_obj, n_hints)} by a hash
+                         of (seed, sample); as in poses.py:82-97 the matched objects come FIRST in the sample's object list, in the order
+                         of their hints - so the objects of a sample are a permutation of the cell's
+      all_matches        B int64 [n_obj + n_hints - k, 2]: matches, then every unmatched hint h as (n_obj, h), then every unmatched object o
+                         as (o, n_hints) (poses.py:114-137)
+      offsets            B float64 [n_hints, 2]: pose - centre of the matched object (x, y); for an unmatched hint pose - cell middle
+      poses              B data.Pose, pose in cell coordinates ~ U[0, 1]^2 by a hash of (seed, sample)
+      packed             (xyz, rgb, center, mean_rgb, cell_ptr) of the SAME objects in the same order: what data.pack_cells makes of
+                         `objects` / `object_points`, for callers of forward_packed
+    A matched hint describes its object (describe_object); an unmatched one is a random sentence (make_texts)."""
+    import torch
+    from .data import Batch, Object3d, Pose
+    if not 1 <= n_hints or not 1 <= n_obj:
+        raise ValueError("make_fine_batch: need n_obj, n_hints >= 1")
+    xyz, rgb, center, mean_rgb, cell_ptr = make_cells(seed, batch, fixed_n=n_obj, n_pts=n_pts)
+    shape, color_id, _ = object_attributes(seed, 0, batch * n_obj)
+    filler = make_texts(seed, 0, batch * n_hints, n_hints=1)
+    sid = np.arange(batch, dtype=np.uint64)
+    kmax = min(n_obj, n_hints)
+    k_of = 1 + (_u01(_key(seed, sid, 21)) * kmax).astype(np.int64)
+    pose_xy = _u01(_key(seed, sid[:, None], 22, np.arange(2)[None, :]))
+    order = np.empty(batch * n_obj, dtype=np.int64)
+    out = dict(objects=[], object_points=[], hint_descriptions=[], matches=[], all_matches=[], offsets=[], poses=[])
+    for b in range(batch):
+        lo, k = b * n_obj, int(min(k_of[b], kmax))
+        obj_rank = np.argsort(_key(seed, np.arange(lo, lo + n_obj, dtype=np.uint64), 23), kind="stable")   # cell-local object order
+        hint_rank = np.argsort(_key(seed, np.uint64(b), 24, np.arange(n_hints, dtype=np.uint64)), kind="stable")
+        matched_hints = np.sort(hint_rank[:k])
+        perm = lo + obj_rank                          # the first k are the matched objects, in the order of their hints
+        order[lo: lo + n_obj] = perm
+        hints = [filler[b * n_hints + h] for h in range(n_hints)]
+        off = np.tile(pose_xy[b] - 0.5, (n_hints, 1))
+        for o, h in enumerate(matched_hints):
+            g = int(perm[o])
+            hints[int(h)] = describe_object(shape[g], color_id[g], center[g])
+            off[int(h)] = pose_xy[b] - center[g, 0:2].astype(np.float64)
+        matches = np.array([(o, int(h)) for o, h in enumerate(matched_hints)], dtype=np.int64).reshape(-1, 2)
+        binned_hints = [(n_obj, h) for h in range(n_hints) if h not in set(matched_hints.tolist())]
+        binned_objects = [(o, n_hints) for o in range(k, n_obj)]
+        objs = []
+        for slot, g in enumerate(perm):
+            g = int(g)
+            label = LABEL_GROUPS[int(shape[g])][min(6, int(float(center[g, 2]) / 0.3 * 7.0))]
+            objs.append(Object3d(slot, g, np.tile(center[g].astype(np.float64), (2, 1)), np.tile(mean_rgb[g].astype(np.float64), (2, 1)),
+                                 label))
+        out["objects"].append(objs)
+        out["object_points"].append(Batch(x=torch.from_numpy(rgb[perm].reshape(-1, 3).copy()),
+                                          pos=torch.from_numpy(xyz[perm].reshape(-1, 3).copy()),
+                                          batch=torch.arange(n_obj).repeat_interleave(n_pts)))
+        out["hint_descriptions"].append(hints)
+        out["matches"].append(matches)
+        out["all_matches"].append(np.array(matches.tolist() + binned_hints + binned_objects, dtype=np.int64).reshape(-1, 2))
+        out["offsets"].append(off)
+        out["poses"].append(Pose(np.array([pose_xy[b, 0], pose_xy[b, 1], 0.0]), np.zeros(3), f"synthetic_{b:05d}", "synthetic"))
+    out["packed"] = (xyz[order], rgb[order], center[order], mean_rgb[order], cell_ptr)
+    return out

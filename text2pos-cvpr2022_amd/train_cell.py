@@ -63,15 +63,18 @@ def _host_plan(cp: np.ndarray, k: int, dev):
         views.append(d[a: a + p_.shape[0]])
         a += p_.shape[0]
     return dict(first_obj=views[0], cell_ptr=views[1], knn_ptr=views[2], knn_tgt=views[3], knn_slot=views[4],
-                seg={n: v for n, v in zip(segs, views[5:])}, _host=host)   # (the pinned buffer outlives the copy with the plan)
+                seg={n: v for n, v in zip(segs, views[5:])}, min_size=int(sizes.min()) if n_cells else 1, _host=host)   # (the pinned buffer outlives the copy with the plan)
 
 
-def pointnet_trunk_train(pn, xyz, rgb, first_obj, cell_ptr_dev, add_self_loops=True, zero_color=False):
+def pointnet_trunk_train(pn, xyz, rgb, first_obj, cell_ptr_dev, add_self_loops=True, zero_color=False, min_cell_objects=1):
     """PointNet2.forward up to features2 in train() mode (models/pointcloud/pointnet2.py:83-90): three set-abstraction levels,
     global abstraction, lin1, lin2; every BatchNorm takes its statistics per CELL (one row segment per cell and layer).  Shared by
     the coarse cell branch (encode_objects_train: the reference runs the PointNet++ once per cell) and by the stand-alone
     classifier (pointnet2.PointNet2 in train(): the whole batch is one cell, cell_ptr = [0, n]).
     pn: PointNet2; xyz / rgb [n_obj, P, 3]; first_obj [n_obj], cell_ptr_dev [B + 1] int32 on the device.
+    min_cell_objects: the smallest cell's object count when the caller knows it on the host - a BatchNorm segment then has at least
+    that many times the level's centroid count rows (at 8 points the last level has ONE centroid per object: only a one-object cell
+    is a single-row segment, which nn.BatchNorm1d refuses).
     Returns (features0 [n_obj, 1024], features1 [n_obj, 512], features2 [n_obj, 256]) with a grad_fn."""
     dev = xyz.device
     n_obj, n_pts = xyz.shape[0], xyz.shape[1]
@@ -92,29 +95,26 @@ def pointnet_trunk_train(pn, xyz, rgb, first_obj, cell_ptr_dev, add_self_loops=T
         cent_ptr = g["cent_ptr"]
         cell_edge_ptr = cent_ptr[cell_ptr_dev.long() * nc].contiguous()      # edges per cell = BatchNorm's row segments
         msg = TO.edge_features(x, pos, pos_c, g["src"], g["dst"])
-        h = _mlp_train(msg, sa.point_conv.local_nn, cell_edge_ptr, nc)    # >= one self loop / hit per centroid
+        h = _mlp_train(msg, sa.point_conv.local_nn, cell_edge_ptr, nc * min_cell_objects)    # >= one self loop / hit per centroid
         x, pos, nd = TO.segment_max(h, cent_ptr, covers_all_rows=True), pos_c, nc    # (cent_ptr is the CSR over ALL edge rows)
-    h = _mlp_train(torch.cat([x, pos], dim=1), pn.ga.mlp, _i32(cell_ptr_dev.long() * nd), nd)
+    h = _mlp_train(torch.cat([x, pos], dim=1), pn.ga.mlp, _i32(cell_ptr_dev.long() * nd), nd * min_cell_objects)
     f0 = TO.segment_max(h, _i32(torch.arange(n_obj + 1, device=dev) * nd), covers_all_rows=True)
     f1 = torch.relu(TO.linear(f0, pn.lin1))
     f2 = torch.relu(TO.linear(f1, pn.lin2))
     return f0, f1, f2
 
 
-def encode_objects_train(model, xyz, rgb, center, mean_rgb, cell_ptr, class_idx=None, color_idx=None):
-    """model: CellRetrievalNetwork in train(); packed device inputs as encode_objects_packed.  Returns [B, D] unit rows with
-    a grad_fn; BatchNorm running estimates are updated as the reference's per-cell / per-batch module calls would."""
+def object_rows_train(model, xyz, rgb, center, mean_rgb, plan, class_idx=None, color_idx=None):
+    """ObjectEncoder.forward in train() mode (models/object_encoder.py:61-142): the PointNet++ once per cell / sample (its
+    BatchNorms take their statistics per cell, in cell order), mlp_pointnet, the colour and position encoders and mlp_merge once
+    over all objects, F.normalize.  model: the owner of `object_encoder`, `args` and `add_self_loops` (CellRetrievalNetwork, or
+    SuperGlueMatch whose samples are the cells); plan: _host_plan of the cell sizes.  Returns [n_obj, D] unit rows."""
     a = model.args
     class_embed, color_embed = bool(getattr(a, "class_embed", False)), bool(getattr(a, "color_embed", False))
     if class_embed != (class_idx is not None) or color_embed != (color_idx is not None):
         raise RuntimeError("args.class_embed / args.color_embed need the per-object class / colour indices")
-    dev = xyz.device
     oe, pn = model.object_encoder, model.object_encoder.pointnet
-    n_obj, n_pts = xyz.shape[0], xyz.shape[1]
-    cp = np.ascontiguousarray(np.asarray(cell_ptr), dtype=np.int64)
-    n_cells = cp.shape[0] - 1
-    k = model.graph1.k
-    plan = _host_plan(cp, k, dev)
+    n_obj = xyz.shape[0]
     first_obj, cell_ptr_dev = plan["first_obj"], plan["cell_ptr"]
     one = lambda n: plan["seg"][n]
 
@@ -123,7 +123,8 @@ def encode_objects_train(model, xyz, rgb, center, mean_rgb, cell_ptr, class_idx=
     def pointnet_branch():
         """models/object_encoder.py:86-98: the PointNet++ (one call per cell) + mlp_pointnet."""
         feats = pointnet_trunk_train(pn, xyz, rgb, first_obj, cell_ptr_dev, model.add_self_loops,
-                                     zero_color="color" not in a.use_features)[a.pointnet_features]   # models/object_encoder.py:87-90
+                                     zero_color="color" not in a.use_features,                        # models/object_encoder.py:87-90
+                                     min_cell_objects=max(1, plan["min_size"]))[a.pointnet_features]
         return _mlp_train(feats, oe.mlp_pointnet, one(n_obj), n_obj)
 
     if "class" in a.use_features and class_embed:               # models/object_encoder.py:103-109: no PointNet++ at all
@@ -142,7 +143,20 @@ def encode_objects_train(model, xyz, rgb, center, mean_rgb, cell_ptr, class_idx=
     if "position" in a.use_features:
         parts.append(TO.normalize(_mlp_train(center.float(), oe.pos_encoder, one(n_obj), n_obj)))
     emb = _mlp_train(torch.cat(parts, dim=-1), oe.mlp_merge, one(n_obj), n_obj) if len(parts) > 1 else parts[0]
-    emb = TO.normalize(emb)
+    return TO.normalize(emb)
+
+
+def encode_objects_train(model, xyz, rgb, center, mean_rgb, cell_ptr, class_idx=None, color_idx=None):
+    """model: CellRetrievalNetwork in train(); packed device inputs as encode_objects_packed.  Returns [B, D] unit rows with
+    a grad_fn; BatchNorm running estimates are updated as the reference's per-cell / per-batch module calls would."""
+    dev = xyz.device
+    cp = np.ascontiguousarray(np.asarray(cell_ptr), dtype=np.int64)
+    n_cells = cp.shape[0] - 1
+    k = model.graph1.k
+    plan = _host_plan(cp, k, dev)
+    cell_ptr_dev = plan["cell_ptr"]
+    one = lambda n: plan["seg"][n]
+    emb = object_rows_train(model, xyz, rgb, center, mean_rgb, plan, class_idx, color_idx)
 
     # DynamicEdgeConv(k = 8, max) inside each cell (models/cell_retrieval.py:46-48, :97), pool, lin, normalize (:98-106).
     # t2p_knn lists an object's min(k, cell size) neighbours first and pads with -1, so which of its slots are edges is known from

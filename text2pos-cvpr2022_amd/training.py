@@ -1,14 +1,15 @@
 """Host loops of the reference's PointNet++ pre-training (training/pointcloud/pointnet2.py:24-67, `train_epoch` / `val_epoch`:
 train_pointnet_epoch, val_pointnet_epoch below) and of the reference's coarse training (training/coarse.py:31-62, `train_epoch`) on the HIP path: same batch
 dictionary (`texts`, `objects`, `object_points` as the reference's Kitti360CoarseDataset.collate_fn yields them), same
-order of calls; the arithmetic is docs/notebook.md 4.8.  The data side (datasets, augmentation, plotting) stays with the caller."""
+order of calls; the arithmetic is docs/notebook.md 4.8.  val_fine_epoch is the validation pass of the fine stage
+(training/fine.py:119-170, `eval_epoch`), which the reference runs in train() mode.  The data side (datasets, augmentation, plotting) stays with the caller."""
 from typing import Iterable, Optional
 
 import numpy as np
 import torch
 
 from . import ops
-from .losses import HardestRankingLoss, PairwiseRankingLoss
+from .losses import HardestRankingLoss, PairwiseRankingLoss, calc_pose_error, calc_recall_precision
 
 
 def make_criterion(args) -> torch.nn.Module:
@@ -107,3 +108,35 @@ def val_pointnet_epoch(model, dataloader: Iterable):
     model.eval()
     epoch_accs = [_hits(model(batch), batch) for batch in dataloader]
     return float(np.mean(epoch_accs)) if epoch_accs else float("nan")
+
+
+FINE_VAL_KEYS = ("recall", "precision", "pose_mid", "pose_mean", "pose_offsets")
+
+
+def fine_batch_stats(batch: dict, output) -> dict:
+    """The five figures training/fine.py:134-166 takes from one batch and the model's output for it: recall / precision of the
+    matches against batch["matches"], and the pose error with the cell's middle as the estimate (pose_mid), with the mean of the
+    matched objects' centres (pose_mean) and with the regressed offsets added (pose_offsets)."""
+    m0 = output.matches0.detach().cpu().numpy()
+    m1 = output.matches1.detach().cpu().numpy()
+    off = output.offsets.detach().cpu().numpy()
+    recall, precision = calc_recall_precision(batch["matches"], m0, m1)
+    return dict(recall=recall, precision=precision,
+                pose_mid=calc_pose_error(batch["objects"], m0, batch["poses"], offsets=off, use_mid_pred=True),
+                pose_mean=calc_pose_error(batch["objects"], m0, batch["poses"], offsets=None),
+                pose_offsets=calc_pose_error(batch["objects"], m0, batch["poses"], offsets=off))
+
+
+@torch.no_grad()
+def val_fine_epoch(model, dataloader: Iterable[dict]) -> dict:
+    """training/fine.py:119-170 (`eval_epoch`): one pass over `dataloader` (batches as Kitti360FineDataset.collate_fn builds them:
+    objects, hint_descriptions, object_points, matches, poses) WITHOUT touching the model's mode - the reference leaves its
+    `model.eval()` commented out, so after a training epoch the validation runs in train() mode, with batch statistics in every
+    BatchNorm and moving running estimates; the figures in the released checkpoint names come from that mode.  Returns the means
+    over the batches of recall, precision, pose_mid, pose_mean, pose_offsets."""
+    stats = {k: [] for k in FINE_VAL_KEYS}
+    for batch in dataloader:
+        output = model(batch["objects"], batch["hint_descriptions"], batch["object_points"])
+        for k, v in fine_batch_stats(batch, output).items():
+            stats[k].append(v)
+    return {k: float(np.mean(v)) if v else float("nan") for k, v in stats.items()}

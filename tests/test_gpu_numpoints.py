@@ -1,8 +1,8 @@
 """args.pointnet_numpoints other than 256 (8 to 256 points per object; training/args.py:53): every layer of the cell encoder at the
 object sizes a model may be trained with, on both arithmetic paths, against the CPU oracle (which is generic in the point count).
 
-At 256 points the specialised f16x3 SA kernels run; every other size takes the generic f16x3 SA kernel (csrc/sa_x3.hip) for the
-level shapes that are not the 256-point ones, and the GA max runs over groups of gp = next power of two >= the level-3 centroid
+At 256 points the specialised f16x3 SA kernels run; every other size takes the generic f16x3 SA kernel (the stream kernel of
+csrc/ws_sa.hip) for the level shapes that are not the 256-point ones, and the GA max runs over groups of gp = next power of two >= the level-3 centroid
 count (SA level 3 pads each object to gp rows with copies of its last centroid).
 """
 import re

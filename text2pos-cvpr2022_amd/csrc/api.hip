@@ -273,8 +273,8 @@ int encode_chunk(const float* xyz, const float* rgb, const float* center, const 
     gbounds.ga1_l1 = W.ga_w1_l1;
     gbounds.ga1_bmax = W.ga_b1_absmax;
     // f16x3: the SA kernels of the level shapes of 256 points build their centroid tables B_i = W1p pos_i in LDS (sa_points.hip,
-    // sa_rows.hip, sa3.hip); the HBM tables B_l are then neither written nor read.  The fp32 kernels (ws_sa.hip) and the f16x3
-    // kernel of the other shapes (sa_x3.hip) gather theirs from HBM.
+    // sa_rows.hip, sa3.hip); the HBM tables B_l are then neither written nor read.  The stream kernel (ws_sa.hip: fp32, and f16x3 at
+    // the other shapes) gathers its table from HBM.
     bool lds_btab[3];
     for (int l = 0; l < 3; l++) lds_btab[l] = cfg.precision == 1 && g.specialised(l);
     // level 0 runs on sa_points.hip, which computes layer 1 per edge from the points themselves: no point table A_1 either

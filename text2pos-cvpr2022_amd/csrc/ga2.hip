@@ -20,7 +20,6 @@
 namespace t2p {
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 
 constexpr int K = 512, NW = 128, NT = 512;
 constexpr int KH = K / 2;            // k range of one wave

@@ -157,7 +157,6 @@ __global__ __launch_bounds__(256, 1) void k_bilstm(const float* __restrict__ gat
 // planes.  The product runs tile by tile (gate x 32 units), so that a tile's MFMAs wait for their own 16 table values only:
 // measured on the first form of this kernel (k-step-major, all 128 table values in front of the first MFMA), the gate-table
 // gather was the largest single cost of a time step (9 of 28 us; the weight stream 6, the gate functions 2).
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 
 // Gate functions on the hardware exponential / reciprocal (v_exp_f32, v_rcp_f32: ~1 ulp each; absolute error of the gate
 // values <= 2e-7).  The library expf / tanhf of the fp32 kernel cost ~35 instructions per value: 160 values per lane and time

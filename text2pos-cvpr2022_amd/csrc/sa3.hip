@@ -30,9 +30,6 @@
 // feeds both column blocks), but the smaller shape sustains 3-4 % more at the power cap (profiles/microbench/mfma_shapes.hip), and here:
 // 26.45-26.64 -> 25.40-25.68 ms per step in three interleaved A/B pairs (round 5).  Lane = 16 q + i holds row 16 rb + i of the A
 // operand, column 16 cb + i of the B operand, k = 64 q + 8 s + e of step s (s < 8), and rows 16 rb + 4 q + v of a result block.
-#ifndef T2P_SA3_SPLIT_ASM
-#define T2P_SA3_SPLIT_ASM 1
-#endif
 #define SB() __builtin_amdgcn_sched_barrier(0)
 #define AS4 __attribute__((address_space(4)))
 
@@ -56,8 +53,6 @@ constexpr int OFF_DST = OFF_BIAS + N * 4;                // [4 batches][TR] u16 
 constexpr int LDS_BYTES = OFF_DST + 4 * TR * 2;
 static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef t2p_fp16x2 fp16x2;
 #define MFMA32(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0)
 
 template <typename T>
@@ -67,17 +62,6 @@ __device__ __forceinline__ const AS4 T* as_const(const T* p) {
 __device__ __forceinline__ void lds_fmax(float* p, float v) {
     (void)__hip_atomic_fetch_max(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
-template <int SEL>
-__device__ __forceinline__ float sub_half(float v, fp16x2 h) {   // v - (float)h[SEL] in one VOP3P mixed-precision FMA
-    float r;
-    if constexpr (SEL == 0)
-        asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(r) : "v"(h), "v"(v));
-    else
-        asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r) : "v"(h), "v"(v));
-    return r;
-}
-// LDS-only workgroup barrier (no vmcnt wait: the drain's global stores need not have landed)
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 struct It {      // one pipeline stage's position in the workgroup's object range; every member is wave-uniform (SGPRs)
     int g;       // object
@@ -270,15 +254,8 @@ __global__ __launch_bounds__(NT, 2) void k_sa3(SaParams p) {
             pl.x = __float_as_uint(vv[2]);
             pl.y = __float_as_uint(vv[3]);
         } else {
-#if T2P_SA3_SPLIT_ASM
             pl.x = split_lo_pk(vh01, vv[0], vv[1]);     // (one asm statement per pair: no s_nop between the pieces, t2p_common.h)
             pl.y = split_lo_pk(vh23, vv[2], vv[3]);
-#else
-            const fp16x2 l01 = cvt_pk_f16(sub_half<0>(vv[0], vh01), sub_half<1>(vv[1], vh01));
-            const fp16x2 l23 = cvt_pk_f16(sub_half<0>(vv[2], vh23), sub_half<1>(vv[3], vh23));
-            pl.x = __builtin_bit_cast(uint32_t, l01);
-            pl.y = __builtin_bit_cast(uint32_t, l23);
-#endif
         }
         if constexpr (T2P_SA3_ABL & 4) asm volatile("" ::"v"(pl.x), "v"(pl.y));
         else *(uint2*)(dsth + PLANE + (4 * wave + k) * LDHH + c4 * 4) = pl;

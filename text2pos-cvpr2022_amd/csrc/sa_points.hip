@@ -22,20 +22,11 @@
 #ifndef T2P_PABL
 #define T2P_PABL 0
 #endif
-// T2P_PPROF = w + 1: wave w of block 0 sums s_memtime differences of its phases over the launch (t2p_debug_pprof reads them)
-#ifndef T2P_PPROF
-#define T2P_PPROF 0
-#endif
 #include "t2p_common.h"
 
 namespace t2p {
-int launch_sa_balance(const SaParams& p, int tile_rows, int n_wg, hipStream_t st);  // ws_sa.hip
-
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-typedef __fp16 fp16x2 __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -61,15 +52,6 @@ struct PtsCfg {
     static constexpr size_t lds_bytes() { return (size_t)NW * WAVE_BYTES + 16 + N * 4; }   // + the object counter, the bias
 };
 
-template <int SEL>
-__device__ __forceinline__ float sub_half_p(float v, fp16x2 h) {   // v - (float)h[SEL] in one VALU op (exact)
-    float r;
-    if constexpr (SEL == 0)
-        asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(r) : "v"(h), "v"(v));
-    else
-        asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r) : "v"(h), "v"(v));
-    return r;
-}
 // max(v, 0) in one instruction: fmaxf() puts a canonicalising v_max v, v in front of the maximum (the operand is an MFMA result
 // of unknown NaN class).  As SIGNED INTEGERS the bit patterns of the non-negative floats order like the floats and every
 // negative float (and -0) is below 0: one v_max_i32.  (Not inline asm: hipcc places the MFMA -> VALU wait states only in front
@@ -81,26 +63,10 @@ __device__ __forceinline__ float relu1(float v) {
 // (v0, v1) -> fp16 pair hi (round to nearest) and the fp16 pair of the exact residuals
 __device__ __forceinline__ void split2(float v0, float v1, uint32_t& hi, uint32_t& lo) {
     const fp16x2 hh = cvt_pk_f16(v0, v1);
-    const fp16x2 ll = cvt_pk_f16(sub_half_p<0>(v0, hh), sub_half_p<1>(v1, hh));
+    const fp16x2 ll = cvt_pk_f16(sub_half<0>(v0, hh), sub_half<1>(v1, hh));
     hi = __builtin_bit_cast(uint32_t, hh);
     lo = __builtin_bit_cast(uint32_t, ll);
 }
-
-#if T2P_PPROF
-__device__ unsigned long long t2p_pprof_sums[16];
-#define PPROF_DECL unsigned long long pp_t = __builtin_amdgcn_s_memtime(), pp_sum[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; const unsigned long long pp_begin = pp_t
-#define PPROF_MARK(i)                                                  \
-    do {                                                               \
-        const unsigned long long n_ = __builtin_amdgcn_s_memtime();    \
-        pp_sum[i] += n_ - pp_t;                                        \
-        pp_t = n_;                                                     \
-    } while (0)
-#define PPROF_COUNT(i) pp_sum[i] += 1
-#else
-#define PPROF_DECL
-#define PPROF_MARK(i)
-#define PPROF_COUNT(i)
-#endif
 
 // PARTS = 1: a wave owns whole objects.  PARTS = 4 (calls of a few hundred objects - the reference's 64-cell batches -, where a
 // wave per object leaves most of the chip idle and the call waits for one object's ~130 tiles): a wave owns a QUARTER of an
@@ -177,7 +143,6 @@ __global__ __launch_bounds__(64 * NW, (NW + 3) / 4) void k_sa_points(SaParams p)
 
     int gtop = 0;         // fp16-range guard: this lane's maximum (bit pattern, before out_scale) of the drained outputs; reduced
                           // over the wave once, at the end
-    PPROF_DECL;
     const int g_begin = p.bounds_ws[blockIdx.x], g_end = p.bounds_ws[blockIdx.x + 1];
     int* ctr = (int*)(lds + NW * C::WAVE_BYTES);
     if (tid == 0) *ctr = 0;
@@ -195,8 +160,6 @@ __global__ __launch_bounds__(64 * NW, (NW + 3) / 4) void k_sa_points(SaParams p)
         constexpr int HP = C::NH / PARTS;                        // halves per part
         const int hs = PARTS > 1 ? (gi % PARTS) * HP : 0;        // this wave's halves: [hs, hend)
         const int hend = hs + HP;
-        PPROF_MARK(0);      // drawing an object
-        PPROF_COUNT(9);
         int n = __builtin_amdgcn_readfirstlane((int)p.n_rows[g]);
         const uint16_t* list = p.rows + (int64_t)g * C::MAXR;
         if constexpr (PARTS > 1) {
@@ -275,7 +238,6 @@ __global__ __launch_bounds__(64 * NW, (NW + 3) / 4) void k_sa_points(SaParams p)
         }
         ring_write(0, win0);
         ring_write(1, win1);
-        PPROF_MARK(1);      // points, list windows -> LDS
 
         // The accumulator is a WINDOW of 16 centroid slots (slot = centroid & 15) in two halves of 8.  A tile may hold rows of the
         // half of its first row and the next one, so tiles are full (32 rows) wherever the list goes on; a half is drained (relu(max
@@ -339,7 +301,6 @@ __global__ __launch_bounds__(64 * NW, (NW + 3) / 4) void k_sa_points(SaParams p)
         int r0 = 0;
         uint32_t e_cur = n > 0 ? ring_read(0) : 0u;
         while (r0 < n) {
-            PPROF_COUNT(10);
             // ---- this tile: rows r0 .. r0 + c - 1, all in halves h0 and h0 + 1 (the list is sorted by centroid) -----------------------
             const uint32_t key = r0 + rr < n ? ((e_cur >> 8) & 127u) : 255u;
             const int h0 = __builtin_amdgcn_readfirstlane((int)key) >> 3;
@@ -364,7 +325,6 @@ __global__ __launch_bounds__(64 * NW, (NW + 3) / 4) void k_sa_points(SaParams p)
                         hf = ho;
                     }
                 }
-                PPROF_MARK(3);  // window move
             }
             // list ring: one more window into LDS whenever less than 96 entries lie ahead (every other tile); behind its wait the
             // pending output rows leave, then the next window's load
@@ -405,7 +365,6 @@ __global__ __launch_bounds__(64 * NW, (NW + 3) / 4) void k_sa_points(SaParams p)
                 hid = MFMA8(w1_lo, x_hi, hid);
                 hid = MFMA8(w1_hi, x_lo, hid);
             }
-            PPROF_MARK(4);  // look-ahead, point reads, layer 1
             uint2 four[4];   // accumulator-row byte offsets of this lane's 16 result rows 8 q + 4 h + {0..3}
             {
                 const uint2* f4 = (const uint2*)(lds + dst_off + h * 8);
@@ -435,7 +394,6 @@ __global__ __launch_bounds__(64 * NW, (NW + 3) / 4) void k_sa_points(SaParams p)
 #pragma unroll
                 for (int nt = 0; nt < C::NTW; nt++) acc[nt] = MFMA16(a_lo, w_hi[nt][s], acc[nt]);
             }
-            PPROF_MARK(5);  // ReLU, split, layer 2
             // float max into the wave's accumulator (nobody else touches it)
             {
                 uint32_t ad[16];
@@ -456,11 +414,7 @@ __global__ __launch_bounds__(64 * NW, (NW + 3) / 4) void k_sa_points(SaParams p)
                             asm volatile("ds_max_f32 %0, %1 offset:%2" ::"v"(ad[e]), "v"(acc[nt][e]), "n"(nt * 128) : "memory");
                         else
                             asm volatile("; %0 %1" ::"v"(ad[e]), "v"(acc[nt][e]));
-                PPROF_MARK(6);  // atomics
             }
-#if T2P_PPROF
-            pp_sum[8] += c;
-#endif
             r0 += c;
             e_cur = e_nxt;
         }
@@ -468,14 +422,7 @@ __global__ __launch_bounds__(64 * NW, (NW + 3) / 4) void k_sa_points(SaParams p)
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         for (; hd < hend; hd++) drain(hd, hd < ho);
         flush_out();
-        PPROF_MARK(7);      // last drains
     }
-#if T2P_PPROF
-    if (blockIdx.x == 0 && wave == T2P_PPROF - 1 && lane == 0) {
-        for (int i = 0; i < 11; i++) atomicAdd(&t2p_pprof_sums[i], pp_sum[i]);
-        atomicAdd(&t2p_pprof_sums[11], __builtin_amdgcn_s_memtime() - pp_begin);
-    }
-#endif
     uint32_t gbits = 0;
     guard_track_bits(gbits, gtop);
     if (p.amax_out != nullptr && lane == 0 && gbits != 0u)
@@ -530,10 +477,3 @@ int launch_sa_points(int H, int Cout, const SaParams& p, hipStream_t st) {
 }
 
 }  // namespace t2p
-
-#if T2P_PPROF
-extern "C" void t2p_debug_pprof(unsigned long long* out) {
-    (void)hipDeviceSynchronize();
-    (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(t2p::t2p_pprof_sums), sizeof(unsigned long long) * 16);
-}
-#endif

@@ -1,29 +1,28 @@
 // Set-abstraction edge kernel, f16x3 path, ROW-OWNING waves (SA level 2: H = C = 128).
 // (reference: gnn.PointConv(local_nn)(x, (pos, pos[idx]), edge_index), models/pointcloud/pointnet2.py:31-35).
 //
-// ws_sa2.hip gives every wave a 32-column slice of the layer-2 weights and lets all waves of the workgroup share one
+// A column-slice kernel gives every wave a 32-column slice of the layer-2 weights and lets all waves of the workgroup share one
 // staged row batch (gather -> registers -> ReLU(A_j - B_i) -> fp16 split -> LDS planes -> barrier -> operand reads): a wave
 // then issues ~500 instructions around 24 MFMAs per batch at K = 128 and the matrix pipe idles two thirds of the time.
-// Here a wave owns ROWS instead: it holds the WHOLE 128 x 128 weight matrix (hi + lo fp16 planes: 256 registers; one wave
-// per SIMD, 512-register budget), fetches its own 32-row tiles with LDS-DMA (global_load_lds, no staging registers, no
-// ds_write pass), reads each row piece straight into the MFMA A-operand layout, forms ReLU(A_j - B_i) and its fp16 hi / lo
-// split in registers and multiplies 32 rows by all 128 columns: 96 MFMAs per tile and wave, no workgroup barrier inside an
-// object, ~5 other instructions per MFMA instead of ~20.
+// Here a wave owns ROWS instead: it holds the WHOLE 128 x 128 weight matrix (hi + lo fp16 planes: 256 registers, most of them in
+// AGPRs; one wave per SIMD, 512-register budget), loads the MFMA A-operand bytes of its own 32-row tiles straight into registers
+// (no staging pass, no LDS round trip), forms ReLU(A_j - B_i) and its fp16 hi / lo split in registers and multiplies 32 rows by all
+// 128 columns: 96 MFMAs per tile and wave, no workgroup barrier inside an object, ~5 other instructions per MFMA instead of ~20.
 //
 //   * one workgroup (4 waves) per CU walks a balanced contiguous object range; the tiles of an object go round-robin to
 //     the waves, the object's max-accumulator [n_cent][C] and centroid table B_i = W1p pos_i [n_cent][H] live in LDS;
-//   * (rounds 3-5; still built with -DT2P_ROWS_DIRECT=0) ring of 4 slots x 4 KB per wave = one whole tile of prefetch: slot u holds
-//     the 128-byte pieces (k = 32 u .. 32 u + 31) of the tile's 32 rows, 8 rows x 128 B per DMA instruction, XOR-swizzled on the SOURCE
-//     address so that the lane-linear LDS image is read conflict-free with ds_read_b128; counted s_waitcnt vmcnt(8), never vmcnt(0)
-//     inside the stream.  Round 6 (default): every lane loads its own operand bytes straight into registers - T2P_ROWS_DIRECT below;
+//   * lane (h, rr) reads bytes [64 s + 32 h, + 32) of ITS OWN row rr per MFMA step s with two global_load_dwordx4, five steps ahead
+//     of their use (the load schedule is described at rows_load_slot below);
 //   * the row lists and centroid positions of the objects ahead travel by LDS-DMA;
 //   * the rows of repeated centroids arrive once (GroupTables::share_tail): centroid code NC names one more accumulator row, whose B row
 //     is centroid 0's (table row = code & (NC - 1)); the drain folds it into every tail centroid's row first (max is idempotent: the
 //     same bits as the full list).  The tile loop is the same for both list forms; an object without a tail pays one ballot;
 //   * natural k order (lane half h owns k = 16 s + 8 h .. + 7 of MFMA step s): the host's register-order weight image is
-//     re-indexed at load time; every fp32 accumulation runs hi.hi, hi.lo, lo.hi per step like ws_sa2.hip, with another
-//     grouping of the k's (results agree to fp32 rounding, not bit for bit).
-// T2P_RABL (development only, results are wrong): 1 = no ring DMA, 2 = no atomics, 4 = no drain stores / table build,
+//     re-indexed at load time; every fp32 accumulation runs hi.hi, hi.lo, lo.hi per step like the stream kernel of ws_sa.hip, with
+//     another grouping of the k's (results agree to fp32 rounding, not bit for bit).
+// Earlier builds fetched the tiles through a per-wave LDS ring of global_load_lds pieces and kept the weights in VGPRs only; the commit
+// "One SA stream kernel for fp32 and f16x3; drop superseded kernel builds" removed them (git log -S T2P_ROWS_DIRECT).
+// T2P_RABL (development only, results are wrong): 1 = no row loads, 2 = no atomics, 4 = no drain stores / table build,
 // 8 = no MFMAs (first and last of a step kept), 16 = no object barriers.  An ablation that leaves ZEROS where data was also lowers the
 // matrix pipe's power and with it the time of this kernel and of those behind it: read the table with that in mind.
 #ifndef T2P_RABL
@@ -32,45 +31,29 @@
 #include "t2p_common.h"
 
 namespace t2p {
-int launch_sa_balance(const SaParams& p, int tile_rows, int n_wg, hipStream_t st);  // ws_sa.hip
-
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef __fp16 fp16x2 __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) void lds_void;
 typedef const __attribute__((address_space(1))) void gl_void;
 
-#define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0)
-// T2P_ROWS_AGPR (round 6): the weight matrix does not fit the 256 architectural VGPRs next to the loop's working set, and hipcc parks
+// AGPR operands: the weight matrix does not fit the 256 architectural VGPRs next to the loop's working set, and hipcc parks
 // what does not fit (39 of the 64 half8 operands) in AGPRs as SPILL space: 96 v_accvgpr_read_b32 per tile copy them back, operand by
 // operand, in front of their MFMAs (ISA census: 96 of the loop's 859 non-MFMA instructions - with one wave per SIMD every one of
-// them comes out of the MFMA stream).  gfx950's MFMA reads its B operand from an AGPR just as well: here the MFMAs are inline asm whose
+// them comes out of the MFMA stream).  gfx950's MFMA reads its B operand from an AGPR just as well: the MFMAs are inline asm whose
 // weight operand is constrained to the register file the operand LIVES in - the whole lo plane and the first WA_HI_STEPS steps of
 // the hi plane in AGPRs (moved there once, at kernel start), the rest in VGPRs - and the accumulators stay in AGPRs, where
-// ds_max_f32 reads them.  Same instructions, same order of accumulation: same bits.
-#ifndef T2P_ROWS_AGPR
-#define T2P_ROWS_AGPR 1
-#endif
-// T2P_ROWS_DIRECT (round 6): the tile's rows no longer travel through an LDS ring.  The ring (global_load_lds pieces of 8 rows x
-// 128 B, read back with ds_read_b128) cost ~60 cycles of issue per piece among the MFMAs of a one-wave SIMD - 16 pieces per tile, 2.1 ms
-// of SA2's 19.2 ms per step by ablation (profiles/r06_d_sa2_ablation.txt), 4.5 ms of the step through the power cap.  The MFMA A operand
-// of lane (h, rr) is 32 contiguous bytes of ITS OWN row rr per step (k = 16 s + 8 h .. + 7): each lane now fetches exactly those with two
-// global_load_dwordx4 per step from `row base + 64 s + 32 h` into a window of registers (the registers the AGPR-resident weights
-// freed).  No ring slots, no ds_bpermute address shuffle, no M0 writes, and the 64 KB of ring leave LDS.
+// ds_max_f32 reads them.
+// Row loads: the MFMA A operand of lane (h, rr) is 32 contiguous bytes of ITS OWN row rr per step (k = 16 s + 8 h .. + 7): each lane
+// fetches exactly those with two global_load_dwordx4 per step from `row base + 64 s + 32 h` into a window of registers (the registers
+// the AGPR-resident weights freed).
 // The loads are ordinary loads, so hipcc places the waits - and across the tile loop's back edge it only ever waits for ALL outstanding
 // loads (vmcnt(0)) at the first use of a batch.  The schedule is built around that: two bursts of eight loads per tile, each issued
 // right BEHIND a wait and used three to four steps (>= 2,000 cycles) later, so that a wait never finds a young load outstanding:
 //   burst Y(t)   = steps 5, 6, 7 of tile t and step 0 of tile t + 1, issued in steps 0 - 1 of tile t, first used in step 4
 //   burst X(t+1) = steps 1 - 4 of tile t + 1,                        issued in steps 4 - 5 of tile t, first used in step 0 of tile t + 1
 // (the conversion of step s + 1 runs inside step s; step 0 of a tile inside its predecessor's last step).
-// Measured (three interleaved A/B pairs, profiles/r06_f_ab_direct.txt): 19.2-19.3 ms per step against 19.6-19.8 with the ring (-2 %) for
-// 630 instead of 818 instructions per tile - and exactly as much with the same loads as inline asm under the ring's counted waits
-// (vmcnt(8), 6-7 steps of prefetch): neither instruction issue nor prefetch depth is what the rows cost, the bytes are.  (The
-// "no ring DMA" ablation's 2.1 ms was mostly its all-zero operands: zeros cost the matrix pipe less power.)
-#ifndef T2P_ROWS_DIRECT
-#define T2P_ROWS_DIRECT 1
-#endif
+// Measured (profiles/r06_f_ab_direct.txt): the same loads as inline asm under counted waits (vmcnt(8), 6-7 steps of prefetch) take
+// exactly as long: neither instruction issue nor prefetch depth is what the rows cost, the bytes are.
 // load issued behind conversion chunk c of step s (S16 = 8 steps): 2 L + j = piece j of logical step L (L >= 8: next tile), or -1
 __device__ __forceinline__ constexpr int rows_load_slot(int s, int c) {
     if (s == 0) return c == 0 || c == 4 ? -1 : 10 + (c < 4 ? c - 1 : c - 2);      // c = 1,2,3,5,6,7 -> steps 5, 6, 7
@@ -91,7 +74,6 @@ __device__ __forceinline__ constexpr bool w_in_agpr(bool lo_plane, int s) { retu
 // when the tile does not chain, so it opens with an explicit s_nop 1.  tests/test_host.py compiles this file and checks the distance
 // in the generated code.
 __device__ __forceinline__ void mfma_w(f32x16& c, const half8& a, const half8& w, bool agpr, bool zero) {
-#if T2P_ROWS_AGPR
     if (zero) {
         if (agpr) asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, 0" : "=a"(c) : "v"(a), "a"(w));
         else asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, 0" : "=a"(c) : "v"(a), "v"(w));
@@ -99,10 +81,6 @@ __device__ __forceinline__ void mfma_w(f32x16& c, const half8& a, const half8& w
         if (agpr) asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+a"(c) : "v"(a), "a"(w));
         else asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+a"(c) : "v"(a), "v"(w));
     }
-#else
-    constexpr f32x16 z = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    c = MFMA16(a, w, zero ? z : c);
-#endif
 }
 #define SB() __builtin_amdgcn_sched_barrier(0)
 #if T2P_RABL & 2
@@ -118,9 +96,6 @@ struct RowsCfg {
     static constexpr int NT = 64 * NW;
     static constexpr int ND = 2 * NC;
     static constexpr int S16 = K / 16, NTW = N / 32;
-    static constexpr int SLOTS = K / 32;                 // 128-byte row pieces (two MFMA steps each) = ring slots per tile
-    static constexpr int SLOT_BYTES = 32 * 128;
-    static constexpr int RING_BYTES = SLOTS * SLOT_BYTES;   // one tile per wave
     static constexpr int MAXR = NC * 33;
     static constexpr int ROWS_CHUNKS = (MAXR * 2 + 1023) / 1024;
     static constexpr int ROWS_BUF = ROWS_CHUNKS * 1024;  // the row list arrives in whole 1 KB DMA pieces
@@ -135,29 +110,13 @@ struct RowsCfg {
     static constexpr int NR_OFF = CPOS_OFF + 2 * CPOS_BUF;
     static constexpr int SB_OFF = NR_OFF + kSubR * 2;
     static constexpr int DSTL_OFF = SB_OFF + kSubR * 4;
-    static constexpr int RING_OFF = (DSTL_OFF + NW * 64 + 1023) / 1024 * 1024;
-    static constexpr size_t lds_bytes() { return (size_t)RING_OFF + (T2P_ROWS_DIRECT ? (size_t)0 : (size_t)NW * RING_BYTES); }
+    static constexpr size_t lds_bytes() { return (size_t)(DSTL_OFF + NW * 64 + 1023) / 1024 * 1024; }
     static_assert(K % 32 == 0 && N % 32 == 0 && NC % 64 == 0 && (NC * N / 4) % NT == 0, "shape");
-    static_assert(SLOTS == 4, "the counted waits below assume four ring slots per tile (K = 128)");
+    static_assert(K == 128, "rows_load_slot schedules the loads of eight MFMA steps per tile");
     // the tail code is accumulator row NC (its B row is row XROW & (NC - 1) = 0 of the table); its byte offset fits the u16 entries
     static_assert(XROW == NC && (NC & (NC - 1)) == 0 && XROW * N * 4 <= 0xFFFF && XROW < 128, "shared tail slot");
 };
 
-template <int SEL>
-__device__ __forceinline__ float sub_half_r(float v, fp16x2 h) {   // v - (float)h[SEL] in one VALU op (exact)
-    float r;
-    if constexpr (SEL == 0)
-        asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(r) : "v"(h), "v"(v));
-    else
-        asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r) : "v"(h), "v"(v));
-    return r;
-}
-
-// workgroup barrier that orders LDS traffic only (no vmcnt: outstanding LDS-DMA pieces of the ring must survive it)
-__device__ __forceinline__ void lds_barrier_r() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-// counted wait for the ring: the 8 youngest DMA instructions (two slots) may stay in flight; the slot the wait retires is
-// read right away, the slot emptied one step earlier is refilled BEHIND the wait in the same step
-__device__ __forceinline__ void wait_ring() { asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); }
 __device__ __forceinline__ void wait_all_vm() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
 struct TileRef {   // a tile of this wave: object (index inside the cached sub-range), first row, rows of the object
@@ -175,7 +134,6 @@ __global__ __launch_bounds__(64 * NW, 1) void k_sa_rows(SaParams p) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int h = lane >> 5, rr = lane & 31;
-    const uint32_t ringb = (uint32_t)(C::RING_OFF + wave * C::RING_BYTES);
     const uint32_t dstl_addr = (uint32_t)(C::DSTL_OFF + wave * 64);   // [32] u16: accumulator-row byte offset of every tile row
 
     // ---- stationary weights: the whole [K][N] matrix as hi / lo fp16 planes, natural k order ---------------------------
@@ -194,11 +152,9 @@ __global__ __launch_bounds__(64 * NW, 1) void k_sa_rows(SaParams p) {
                 const int idx = (((nt * C::S16 + step_) * 2 + half_) * 32) + rr;
                 w_hi[nt][s] = __builtin_bit_cast(half8, wp[idx]);
                 w_lo[nt][s] = __builtin_bit_cast(half8, wp[PLANE_U4 + idx]);
-#if T2P_ROWS_AGPR
                 // into the AGPR file, once (an empty asm whose AGPR output is tied to the loaded value)
                 if (w_in_agpr(false, s)) asm volatile("" : "=a"(w_hi[nt][s]) : "0"(w_hi[nt][s]));
                 asm volatile("" : "=a"(w_lo[nt][s]) : "0"(w_lo[nt][s]));
-#endif
             }
     }
     // The bias is NOT part of the accumulation: a tile's first MFMAs start from 0, the LDS accumulator takes a FLOAT max of the
@@ -217,23 +173,6 @@ __global__ __launch_bounds__(64 * NW, 1) void k_sa_rows(SaParams p) {
     const int cq = tid % QPR, cg = tid / QPR;
     const f32x4 wq0 = *(const f32x4*)(p.wp + cq * 4), wq1 = *(const f32x4*)(p.wp + K + cq * 4),
                 wq2 = *(const f32x4*)(p.wp + 2 * K + cq * 4);
-
-    // ---- per-lane constants --------------------------------------------------------------------------------------------
-    // ring reads: row rr of a slot is 128 B = 8 chunks of 16 B; chunk c sits at position c ^ ((rr >> 1) & 7)
-    uint32_t rd[2][2];
-#pragma unroll
-    for (int par = 0; par < 2; par++)
-#pragma unroll
-        for (int j = 0; j < 2; j++)
-            rd[par][j] = ringb + (uint32_t)(rr * 128 + (((4 * par + 2 * h + j) ^ ((rr >> 1) & 7)) * 16));
-    // DMA instruction q of a slot: lane i fetches row 8 q + (i >> 3), LDS position i & 7 <- source chunk (i & 7) ^ swizzle(row)
-    uint32_t dma_sel[4], dma_chunk[4];
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-        const int r = 8 * q + (lane >> 3);
-        dma_sel[q] = (uint32_t)(r * 4);
-        dma_chunk[q] = (uint32_t)((((lane & 7) ^ ((r >> 1) & 7))) * 16);
-    }
 
     for (int i = tid; i < (NC + 1) * N; i += C::NT) acc_lds[i] = (int)0xFF800000;   // -inf (row NC: the shared tail rows)
     int gtop = 0;         // fp16-range guard: this lane's maximum (bit pattern, before out_scale) of the drained outputs; reduced over
@@ -306,22 +245,7 @@ __global__ __launch_bounds__(64 * NW, 1) void k_sa_rows(SaParams p) {
             const uint32_t srow = (d & 0x80u) ? (sb0 + src) : (g * (uint32_t)C::ND + src);
             return srow * (uint32_t)(K * 4);
         };
-        // ... and of the rows each DMA instruction of a slot fetches
-        [[maybe_unused]] auto tile_voff = [&](uint32_t rowbyte, uint32_t (&voff)[4]) {   // (ring build only: -DT2P_ROWS_DIRECT=0)
-#pragma unroll
-            for (int q = 0; q < 4; q++)
-                voff[q] = (uint32_t)__builtin_amdgcn_ds_bpermute((int)dma_sel[q], (int)rowbyte) + dma_chunk[q];
-        };
-        auto dma_piece = [&](const uint32_t (&voff)[4], int u, int q) {
-            if constexpr (!(T2P_RABL & 1))
-                dma16(p.A, voff[q] + (uint32_t)(u * 128), ringb + (uint32_t)(u * C::SLOT_BYTES + q * 1024));
-        };
-        [[maybe_unused]] auto issue_slot = [&](const uint32_t (&voff)[4], int u) {
-#pragma unroll
-            for (int q = 0; q < 4; q++) dma_piece(voff, u, q);
-        };
-#if T2P_ROWS_DIRECT
-        // direct operand loads: lane (h, rr) reads bytes [64 s + 32 h, + 32) of its own row rr
+        // operand loads: lane (h, rr) reads bytes [64 s + 32 h, + 32) of its own row rr
         constexpr int AHEAD = 5;                       // steps between a load and its use (the window holds AHEAD x 8 registers)
         const uint32_t hoff = (uint32_t)(h * 32);
         auto load_half = [&](uint32_t roff, int s_, int j, f32x4 (&x)[2]) {
@@ -331,7 +255,6 @@ __global__ __launch_bounds__(64 * NW, 1) void k_sa_rows(SaParams p) {
             load_half(roff, s_, 0, x);
             load_half(roff, s_, 1, x);
         };
-#endif
 
         // ---- per-object phases --------------------------------------------------------------------------------------------
         // t0 (uniform): the object's first tail centroid (NC: none).  The tail centroids c >= t0 share the rows accumulated in row
@@ -352,7 +275,7 @@ __global__ __launch_bounds__(64 * NW, 1) void k_sa_rows(SaParams p) {
                     for (int e = 0; e < 4; e++) r[e] = fmaxf(r[e], xq[e]);
                     *a = r;
                 }
-                lds_barrier_r();   // every thread has read row XROW: back to -inf (barrier B stands before the next object's atomics)
+                lds_barrier();   // every thread has read row XROW: back to -inf (barrier B stands before the next object's atomics)
                 typedef int i32x4 __attribute__((ext_vector_type(4)));
                 if (tid < N / 4) *(i32x4*)ax = i32x4{(int)0xFF800000, (int)0xFF800000, (int)0xFF800000, (int)0xFF800000};
             }
@@ -398,16 +321,14 @@ __global__ __launch_bounds__(64 * NW, 1) void k_sa_rows(SaParams p) {
         build_b(ga);
         if (cnt > 2) dma_rows(ga + 2);
         if (cnt > 1) dma_cpos(ga + 1);
-        lds_barrier_r();
+        lds_barrier();
 
-        bool cur_fetched = false;        // the four slots of this wave's next tile (first of object gi) are in flight / landed
+        bool cur_fetched = false;        // the first AHEAD steps of this wave's next tile (first of object gi) are in flight / landed
         uint32_t m_cur = 0;              // ... and this is the metadata of the lane's row of it
-#if T2P_ROWS_DIRECT
         uint32_t roff_cur = 0;           // ... its byte offset in p.A (+ the lane half's 32 bytes)
         f32x4 xw[C::S16][2];             // rolling window of operand pieces: xw[s] = step s of the tile that needs it next
 #pragma unroll
         for (int s0 = 0; s0 < C::S16; s0++) xw[s0][0] = xw[s0][1] = f32x4{0.f, 0.f, 0.f, 0.f};
-#endif
 
         for (int gi = 0; gi < cnt; gi++) {
             // ---- tiles of object gi that belong to this wave -------------------------------------------------------------
@@ -436,20 +357,11 @@ __global__ __launch_bounds__(64 * NW, 1) void k_sa_rows(SaParams p) {
             // is converted here.  (Both used to sit inside the tile loop behind `!cur_fetched` / `!prepped`; they are first-iteration-only,
             // and with ordinary loads in flight hipcc's waitcnt pass merged their register state into every iteration.)
             auto read_step = [&](int s, uint32_t brow_, f32x4 (&x)[2], f32x4 (&b)[2]) {
-#if T2P_ROWS_DIRECT
 #pragma unroll
                 for (int j = 0; j < 2; j++) {
                     x[j] = xw[s][j];                      // fetched AHEAD steps ago (a register rename: the loops are unrolled)
                     b[j] = *(const f32x4*)(lds + brow_ + s * 64 + j * 16);
                 }
-#else
-                const int u = s >> 1, par = s & 1;
-#pragma unroll
-                for (int j = 0; j < 2; j++) {
-                    x[j] = *(const f32x4*)(lds + rd[par][j] + u * C::SLOT_BYTES);
-                    b[j] = *(const f32x4*)(lds + brow_ + s * 64 + j * 16);
-                }
-#endif
             };
             // conversion of one step's 8 values in 8 half-chunks of 4 VALU operations (pair pr = values 2 pr, 2 pr + 1):
             // first half v = relu(x - b), second half hi = fp16(v) to nearest, lo = fp16(v - hi)
@@ -461,12 +373,7 @@ __global__ __launch_bounds__(64 * NW, 1) void k_sa_rows(SaParams p) {
             auto prep_b = [&](const float (&v)[2], uint32_t& wh, uint32_t& wl) {
                 const fp16x2 hh = cvt_pk_f16(v[0], v[1]);
                 wh = __builtin_bit_cast(uint32_t, hh);
-#if T2P_ROWS_AGPR
                 wl = split_lo_pk(hh, v[0], v[1]);      // (one asm statement: t2p_common.h)
-#else
-                const fp16x2 ll = cvt_pk_f16(sub_half_r<0>(v[0], hh), sub_half_r<1>(v[1], hh));
-                wl = __builtin_bit_cast(uint32_t, ll);
-#endif
             };
             typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
             auto row_addr = [&](const uint2 (&f4)[4], int e) -> uint32_t {
@@ -477,19 +384,11 @@ __global__ __launch_bounds__(64 * NW, 1) void k_sa_rows(SaParams p) {
             if (have) {
                 if (!cur_fetched) {
                     m_cur = tile_meta(gi, r0, n_g);
-#if T2P_ROWS_DIRECT
                     roff_cur = row_byte(gi, sb_g, m_cur) + hoff;
 #pragma unroll
                     for (int s0 = 0; s0 < AHEAD; s0++) load_step(roff_cur, s0, xw[s0]);
-#else
-                    uint32_t v0[4];
-                    tile_voff(row_byte(gi, sb_g, m_cur), v0);
-#pragma unroll
-                    for (int u = 0; u < C::SLOTS; u++) issue_slot(v0, u);
-#endif
                 }
                 {   // step 0 of the wave's first tile in this object: converted here, every later tile's step 0 inside its predecessor's last step
-                    if constexpr (!T2P_ROWS_DIRECT) wait_ring();
                     f32x4 x[2], b[2];
                     read_step(0, (uint32_t)C::BT_OFF + ((m_cur >> 8) & (uint32_t)(NC - 1)) * (uint32_t)C::BT_STRIDE + (uint32_t)(h * 32), x, b);
                     uint32_t nh[4], nl[4];
@@ -505,8 +404,7 @@ __global__ __launch_bounds__(64 * NW, 1) void k_sa_rows(SaParams p) {
             }
             while (have) {
                 // look ahead: the next tile is prefetched while this one is multiplied, if its row list is in LDS already
-                // (same object or the next one); otherwise the same addresses are fetched again to keep the DMA count of the
-                // counted waits (the slot is dead by then)
+                // (same object or the next one); otherwise this tile's rows are fetched again (their registers are dead by then)
                 const bool chain = r0 + NW * 32 < n_g;                              // next tile in the same object
                 const bool nxt_ok = chain || (gi + 1 < cnt && wave * 32 < n_g1);
                 const int gi_n = chain ? gi : (nxt_ok ? gi + 1 : gi);
@@ -515,16 +413,12 @@ __global__ __launch_bounds__(64 * NW, 1) void k_sa_rows(SaParams p) {
                 const uint32_t sb_n = (chain || !nxt_ok) ? sb_g : sb_g1;
                 // its metadata: the LDS read is issued here, decoded inside step 0
                 uint32_t m_nxt = tile_meta(gi_n, r0_n, n_n);
-                uint32_t vn[4];
-#if T2P_ROWS_DIRECT
                 uint32_t roff_n = roff_cur;
-                (void)vn;
-#endif
                 // this tile: centroid of the lane's row -> table row, accumulator row
                 const uint32_t dl = (m_cur >> 8) & 127u;     // accumulator row: a centroid, or XROW = NC for the shared tail rows ...
                 const uint32_t brow = (uint32_t)C::BT_OFF + (dl & (uint32_t)(NC - 1)) * (uint32_t)C::BT_STRIDE + (uint32_t)(h * 32);   // ... whose B row is centroid 0's
                 // (inline asm: hipcc puts s_waitcnt vmcnt(0) in front of an ordinary LDS access it cannot separate from the
-                // outstanding LDS-DMA pieces, which would drain the ring once per tile)
+                // outstanding LDS-DMA pieces, which would wait for the row loads in flight once per tile)
                 asm volatile("ds_write_b16 %0, %1" ::"v"(dstl_addr + (uint32_t)(rr * 2)), "v"(dl * (uint32_t)(N * 4)) : "memory");
                 uint2 four[4];   // accumulator-row byte offsets of this lane's 16 result rows 8 q + 4 h + {0..3} (fetched in step 6)
 
@@ -533,11 +427,10 @@ __global__ __launch_bounds__(64 * NW, 1) void k_sa_rows(SaParams p) {
                 // ---- steps 0 .. S16-2: [reads of step s+1] [4 MFMAs hi.hi] [8 x (half-chunk of the conversion, 1 MFMA)] --------
                 // One wave per SIMD: the instruction order IS the schedule, so it is pinned with sched_barrier fences: the LDS
                 // round trip of the reads hides behind the first four MFMAs, every later MFMA carries ~4 VALU operations.  Step 0
-                // also decodes the next tile (row offsets -> DMA addresses), odd steps refill the slot the previous step emptied.
+                // also decodes the next tile (its row offset and table row); steps 0, 1, 4 and 5 issue the row loads (rows_load_slot).
 #pragma unroll
                 for (int s = 0; s < C::S16 - 1; s++) {
                     f32x4 x[2], b[2];
-                    if (!T2P_ROWS_DIRECT && ((s + 1) & 1) == 0) wait_ring();      // first step of the next slot
                     read_step(s + 1, brow, x, b);
                     if (s == C::S16 - 2) {
                         const uint32_t a4 = dstl_addr + (uint32_t)(h * 8);
@@ -567,23 +460,15 @@ __global__ __launch_bounds__(64 * NW, 1) void k_sa_rows(SaParams p) {
                     for (int c = 0; c < 8; c++) {
                         if ((c & 1) == 0) prep_a(c >> 1, x, b, v);
                         else prep_b(v, nh[c >> 1], nl[c >> 1]);
-                        if (s == 0) {          // next tile: row offset of the lane's row, the rows of every DMA lane, table row
+                        if (s == 0) {          // next tile: row offset of the lane's row, table row
                             if (c == 2) rowbyte_n = row_byte(gi_n, sb_n, m_nxt);
-#if T2P_ROWS_DIRECT
                             if (c == 4) roff_n = rowbyte_n + hoff;
-#else
-                            if (c == 4) tile_voff(rowbyte_n, vn);
-#endif
                             if (c == 6) brow_n = (uint32_t)C::BT_OFF + ((m_nxt >> 8) & (uint32_t)(NC - 1)) * (uint32_t)C::BT_STRIDE + (uint32_t)(h * 32);
                         }
-#if T2P_ROWS_DIRECT
                         {   // this chunk's load, if the schedule has one (rows_load_slot): at most one per MFMA gap
                             const int ld = rows_load_slot(s, c);
                             if (ld >= 0) load_half(ld < 2 * C::S16 ? roff_cur : roff_n, (ld >> 1) % C::S16, ld & 1, xw[(ld >> 1) % C::S16]);
                         }
-#else
-                        if ((s & 1) && (c & 1)) dma_piece(vn, s >> 1, c >> 1);   // refill of slot (s - 1) / 2, emptied in step s - 1
-#endif
                         if (c < 4) mfma_w(acc[c], a_hi, w_lo[c][s], w_in_agpr(true, s), false);
                         else mfma_w(acc[c - 4], a_lo, w_hi[c - 4][s], w_in_agpr(false, s), false);
                         SB();
@@ -595,10 +480,7 @@ __global__ __launch_bounds__(64 * NW, 1) void k_sa_rows(SaParams p) {
                 {
                     constexpr int s = C::S16 - 1;
                     f32x4 x[2], b[2];
-                    if (chain) {
-                        if constexpr (!T2P_ROWS_DIRECT) wait_ring();     // slot 0 of the next tile
-                        read_step(0, brow_n, x, b);
-                    }
+                    if (chain) read_step(0, brow_n, x, b);
                     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_nop 1" : "+v"(four[0]), "+v"(four[1]), "+v"(four[2]), "+v"(four[3])::"memory");
                     SB();
                     uint32_t ad[16];
@@ -618,9 +500,6 @@ __global__ __launch_bounds__(64 * NW, 1) void k_sa_rows(SaParams p) {
                             if ((i & 1) == 0) prep_a(i >> 1, x, b, v);
                             else prep_b(v, nh[i >> 1], nl[i >> 1]);
                         }
-#if !T2P_ROWS_DIRECT
-                        if (i < 8 && (i & 1)) dma_piece(vn, s >> 1, i >> 1);      // refill of the last slot
-#endif
                         // block nb = (i - 4) / 3 is complete two MFMAs before chunk i = 3 nb + 4: 8 atomics here, 8 in the next chunk
                         if (i >= 4 && ((i - 4) % 3) < 2 && (i - 4) / 3 < C::NTW - 1) {
                             const int nb = (i - 4) / 3, e0 = ((i - 4) % 3) * 8;
@@ -648,23 +527,21 @@ __global__ __launch_bounds__(64 * NW, 1) void k_sa_rows(SaParams p) {
                 r0 = r0_n;
                 cur_fetched = nxt_ok;
                 m_cur = m_nxt;
-#if T2P_ROWS_DIRECT
                 roff_cur = roff_n;
-#endif
             }
             if (!did_tile) cur_fetched = false;
             // ---- object gi is complete for this wave ------------------------------------------------------------------------
-            // the DMA pieces this wave issued for later objects (row lists, positions) are older than any ring piece a
-            // counted wait has since retired - unless the wave had no tile here
+            // the DMA pieces this wave issued for later objects (row lists, positions) are older than the row loads its tiles
+            // have since waited for - unless the wave had no tile here
             if (!did_tile) wait_all_vm();
-            if constexpr (!(T2P_RABL & 16)) lds_barrier_r();    // A: all atomics of object gi are in the accumulator
+            if constexpr (!(T2P_RABL & 16)) lds_barrier();    // A: all atomics of object gi are in the accumulator
             if constexpr (!(T2P_RABL & 4)) flush(ga + gi, t0);
             if (gi + 1 < cnt) {
                 if constexpr (!(T2P_RABL & 4)) build_b(ga + gi + 1);
                 if (gi + 3 < cnt) dma_rows(ga + gi + 3);
                 if (gi + 2 < cnt) dma_cpos(ga + gi + 2);
             }
-            if constexpr (!(T2P_RABL & 16)) lds_barrier_r();    // B: accumulator cleared, next table in place
+            if constexpr (!(T2P_RABL & 16)) lds_barrier();    // B: accumulator cleared, next table in place
         }
     }
     wait_all_vm();

@@ -40,21 +40,26 @@ void set_error(const char* fmt, ...);
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
+typedef _Float16 half8 __attribute__((ext_vector_type(8)));
+typedef _Float16 half4 __attribute__((ext_vector_type(4)));
+typedef __fp16 fp16x2 __attribute__((ext_vector_type(2)));
+
 // fp32 pair -> packed fp16 pair, round to NEAREST even (gfx950's v_cvt_pk_f16_f32; the f16x3 split x = hi + lo then carries
 // |error| <= 2^-22 |x| - v_cvt_pkrtz_f16_f32, round toward zero, leaves 2^-20 and a bias that adds up along k).
-// T2P_SPLIT_RTZ=1 rebuilds round 3's split for A/B measurements.
-#ifndef T2P_SPLIT_RTZ
-#define T2P_SPLIT_RTZ 0
-#endif
-typedef __fp16 t2p_fp16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ t2p_fp16x2 cvt_pk_f16(float a, float b) {
-#if T2P_SPLIT_RTZ
-    return __builtin_amdgcn_cvt_pkrtz(a, b);
-#else
+__device__ __forceinline__ fp16x2 cvt_pk_f16(float a, float b) {
     typedef float f32x2_ __attribute__((ext_vector_type(2)));
     typedef _Float16 h16x2_ __attribute__((ext_vector_type(2)));
-    return __builtin_bit_cast(t2p_fp16x2, __builtin_convertvector((f32x2_){a, b}, h16x2_));
-#endif
+    return __builtin_bit_cast(fp16x2, __builtin_convertvector((f32x2_){a, b}, h16x2_));
+}
+// v - (float)h[SEL] in one VALU op (exact): the fp32 difference behind the low piece of the f16x3 split, as a stand-alone statement
+template <int SEL>
+__device__ __forceinline__ float sub_half(float v, fp16x2 h) {
+    float r;
+    if constexpr (SEL == 0)
+        asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(r) : "v"(h), "v"(v));
+    else
+        asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r) : "v"(h), "v"(v));
+    return r;
 }
 // Low piece of the f16x3 split of a pair: fp16(v0 - hi[0]) | fp16(v1 - hi[1]) << 16, the two differences formed exactly in fp32
 // by v_fma_mix_f32 (hi half extended, times -1, plus v).  ONE asm statement: behind a stand-alone inline-asm v_fma_mix hipcc puts an
@@ -68,7 +73,7 @@ __device__ __forceinline__ t2p_fp16x2 cvt_pk_f16(float a, float b) {
 // global store (k_sa3) or is provably far away (k_sa_rows: the pieces of step s + 1 are converted during step s and first multiplied in
 // step s + 1, behind an explicit s_nop - see mfma_w there); k_sa_points and k_gemm_x3 keep the separate statements, behind which
 // hipcc's own v_cvt_pk -> MFMA spacing applies.  (`lo` is an early-clobber output as well: it then never shares a register with an input.)
-__device__ __forceinline__ uint32_t split_lo_pk(t2p_fp16x2 hi, float v0, float v1) {
+__device__ __forceinline__ uint32_t split_lo_pk(fp16x2 hi, float v0, float v1) {
     uint32_t lo;
     float t0, t1;
     asm("v_fma_mix_f32 %1, %3, -1.0, %4 op_sel:[0,0,0] op_sel_hi:[1,0,0]\n\t"
@@ -77,6 +82,8 @@ __device__ __forceinline__ uint32_t split_lo_pk(t2p_fp16x2 hi, float v0, float v
         : "=&v"(lo), "=&v"(t0), "=&v"(t1) : "v"(hi), "v"(v0), "v"(v1));
     return lo;
 }
+// workgroup barrier that orders LDS traffic only (no vmcnt: loads and LDS-DMA pieces in flight survive it)
+__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 typedef double f64x4 __attribute__((ext_vector_type(4)));
 
 int num_cus();  // cached multiProcessorCount of the current device
@@ -338,12 +345,11 @@ struct SaParams {
     int32_t* bounds_ws;      // [n_workgroups+1] scratch (balanced contiguous object ranges)
     int balanced;            // 1: bounds_ws was filled by launch_sa_balance_levels for this level's launch shape
     uint32_t* amax_out;      // f16x3 guard (nullable): largest output magnitude (the next dense kernel splits these rows)
-    int out_rows;            // output rows per object (0 = n_cent); rows past n_cent repeat centroid n_cent - 1 (ws_sa.hip, sa_x3.hip)
+    int out_rows;            // output rows per object (0 = n_cent); rows past n_cent repeat centroid n_cent - 1 (the stream kernel of ws_sa.hip)
 };
 int launch_ws_sa(int H, int C, const SaParams& p, hipStream_t st);
-// sa_x3.hip: f16x3 kernel of any level shape (runtime n_dense / n_cent, n_cent * C <= 8192), centroid table B from HBM (Bc)
-int launch_sa_x3(int H, int C, const SaParams& p, hipStream_t st);
-int sa_x3_launch_shape(int H, int C, int64_t n_obj, int* tile_rows, int* n_wg);
+// k_balance alone, for a kernel launched outside launch_sa_balance_levels (p.balanced == 0)
+int launch_sa_balance(const SaParams& p, int tile_rows, int n_wg, hipStream_t st);
 // Pseudo-centroid code of the shared tail rows (GroupTables::share_tail) in the centroid byte of a row of SA level 2: 64, the
 // first free value of the 7-bit field behind its 64 centroids; 64 * C * 4 fits the u16 accumulator offsets of k_sa_rows.
 constexpr int kSaTailCode = 64;

@@ -13,9 +13,6 @@
 namespace t2p {
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-typedef __fp16 fp16x2 __attribute__((ext_vector_type(2)));
 
 constexpr int BK = 32;
 constexpr int LDT = BK + 8;               // halves per LDS row: 80 B keeps ds_read_b128 conflict-free
@@ -31,16 +28,6 @@ struct X3Cfg {
     static constexpr int KPT = BK / TPR;            // k per thread and tile (16 / 8)
     static constexpr int MI = TS / 64;              // 32 x 32 blocks per wave and dimension (2 / 1)
 };
-
-template <int SEL>
-__device__ __forceinline__ float sub_half(float v, fp16x2 h) {
-    float r;
-    if constexpr (SEL == 0)
-        asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(r) : "v"(h), "v"(v));
-    else
-        asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r) : "v"(h), "v"(v));
-    return r;
-}
 
 template <int TS>
 __global__ __launch_bounds__(256, 2) void k_gemm_x3(const float* __restrict__ A, int lda, const _Float16* __restrict__ Wx,

@@ -25,18 +25,12 @@
 #ifndef T2P_GABL   // development only (results wrong): 1 = GA layer 1 stores into a 4 MB window (no HBM write traffic)
 #define T2P_GABL 0
 #endif
-#ifndef T2P_GA2_V1
-#define T2P_GA2_V1 0
-#endif
 #include <type_traits>
 
 #include "t2p_common.h"
 
 namespace t2p {
 namespace {
-
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef __fp16 fp16x2 __attribute__((ext_vector_type(2)));
 
 constexpr int kMaxRows = 32 * 33;   // kNN group: 32 destination rows x up to 32 neighbours (+ slack)
 constexpr int kAccFloats = 8192;    // 32 x 256
@@ -145,7 +139,7 @@ __global__ __launch_bounds__((WN > 4 || W8) ? 512 : 256, (WN > 4 || W8) ? 2 : 1)
             const int r = r0 + lr;
             sa[it] = f32x4{0.f, 0.f, 0.f, 0.f};
             if constexpr (C::EDGE) sb[it] = f32x4{0.f, 0.f, 0.f, 0.f};
-            if (((C::TOTAL_F4 % C::NTH) == 0 || q < C::TOTAL_F4) && (r < n_rows || SPLIT_IO == 1)) {
+            if (((C::TOTAL_F4 % C::NTH) == 0 || q < C::TOTAL_F4) && r < n_rows) {
                 if constexpr (C::EDGE) {
                     const int src = rows_src[r];
                     const int dl = rows_dst[r];
@@ -153,14 +147,6 @@ __global__ __launch_bounds__((WN > 4 || W8) ? 512 : 256, (WN > 4 || W8) ? 2 : 1)
                         sa[it] = *(const f32x4*)(p.A + (int64_t)src * p.lda + c4 * 4);
                         sb[it] = *(const f32x4*)(p.Bc + (g * knn_group + dl) * K + c4 * 4);
                     }
-                } else if constexpr (SPLIT_IO == 1) {
-                    // A arrives as fp16 hi / lo planes: thread chunk q = 16 bytes = 8 halves of one plane row
-                    constexpr int CH_PER_PLANE = C::TR * (K / 8);
-                    const int pl = q / CH_PER_PLANE, idx = q % CH_PER_PLANE;
-                    const int prow = idx / (K / 8), c8 = idx % (K / 8);
-                    const _Float16* base = (const _Float16*)(pl ? p.A_lo : p.A_hi);
-                    sa[it] = f32x4{0.f, 0.f, 0.f, 0.f};
-                    if (prow < n_rows) sa[it] = *(const f32x4*)(base + (g * C::TR + prow) * (int64_t)p.lda + c8 * 8);
                 } else {
                     if (SPLIT_IO == 2 || c4 * 4 < k_live)   // (GA layer 1, split output: at its register limit, reads whole rows)
                         sa[it] = *(const f32x4*)(p.A + (g * C::TR + r) * (int64_t)p.lda + c4 * 4);
@@ -182,12 +168,7 @@ __global__ __launch_bounds__((WN > 4 || W8) ? 512 : 256, (WN > 4 || W8) ? 2 : 1)
 #pragma unroll
                 for (int e = 0; e < 4; e++) v[e] = fmaxf(t[e], 0.f);
             }
-            if constexpr (X3 && SPLIT_IO == 1) {
-                constexpr int CH_PER_PLANE = C::TR * (K / 8);
-                const int pl = q / CH_PER_PLANE, idx = q % CH_PER_PLANE;
-                const int prow = idx / (K / 8), c8 = idx % (K / 8);
-                *(f32x4*)(hidh + buf * 2 * C::PLANE + pl * C::PLANE + prow * C::LDHH + c8 * 8) = sa[it];
-            } else if constexpr (X3) {
+            if constexpr (X3) {
                 _Float16* dsth = hidh + buf * 2 * C::PLANE;
                 if constexpr (C::EDGE)   // fp16-range guard: the kNN edge rows relu(P_i + Q_j) are split here
                     gmax_edge = fmaxf(fmaxf(gmax_edge, fmaxf(v[0], v[1])), fmaxf(v[2], v[3]));
@@ -536,7 +517,7 @@ int launch_ws(int mode, int K, int N, const WsParams& p, hipStream_t st) {
     if (mode == WS_DENSE_GROUPMAX)
         T2P_CHECK_ARG(gp <= 32 && (gp & (gp - 1)) == 0 && p.M % gp == 0, "ws_gemm: groupmax needs group_rows in {1, 2, 4, 8, 16, 32} "
                       "and M %% group_rows == 0 (group_rows=%d M=%lld)", p.group_rows, (long long)p.M);
-    // split_io: 0 = fp32 in / fp32 out, 1 = fp16 hi/lo planes in, 2 = fp16 hi/lo planes out (f16x3 only)
+    // split_io: 0 = fp32 in / fp32 out, 1 = fp16 hi/lo planes in (ga2.hip), 2 = fp16 hi/lo planes out (f16x3 only)
     const int split_io = p.A_hi != nullptr ? 1 : (p.out_hi != nullptr ? 2 : 0);
     T2P_CHECK_ARG(split_io == 0 || x3 == 1, "ws_gemm: split fp16 activations need the f16x3 path");
     T2P_CHECK_ARG(p.k_live == 0 || (split_io == 0 && mode == WS_DENSE_STORE && p.k_live % 4 == 0),
@@ -573,11 +554,8 @@ int launch_ws(int mode, int K, int N, const WsParams& p, hipStream_t st) {
             case 1: return launch_cfg<512, 128, 4, 1, WS_DENSE_GROUPMAX, 0, 0, 0, 1>(p, 8, st);
         }
     }
-#if !T2P_GA2_V1
     if (mode == WS_DENSE_GROUPMAX && K == 512 && N == 1024 && x3 == 1 && split_io == 1) return launch_ga2(p, st);
-#endif
     T2P_CHECK_ARG(mode != WS_DENSE_GROUPMAX || gp == 32, "ws_gemm: group_rows=%d is built for the fp32 and the ga2.hip paths", gp);
-    WS_CASE(WS_DENSE_GROUPMAX, 512, 1024, 128, 4, 1, 1, 1)
 #undef WS_CASE
     set_error("ws_gemm: no instantiation for mode=%d K=%d N=%d x3=%d split_io=%d", mode, K, N, x3, split_io);
     return T2P_E_UNSUPPORTED;

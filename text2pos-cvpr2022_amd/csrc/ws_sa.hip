@@ -1,6 +1,13 @@
-// Set-abstraction edge kernel, exact-fp32 path (precision = "fp32": v_mfma_f32_32x32x2_f32 fma chains): per-edge
-// ReLU(A_j - B_i) -> layer-2 GEMM -> max per centroid, for sa1/sa2/sa3.  The f16x3 path runs on sa_points.hip / sa_rows.hip / sa3.hip (levels 1 / 2 / 3 of 256 points) and on sa_x3.hip (every other object size); this file keeps the exact fp32 MFMA kernels, the range balancing and the kernel selection.
+// Set-abstraction edge kernel for sa1/sa2/sa3, one stream kernel for both arithmetic paths: per-edge
+// ReLU(A_j - B_i) -> layer-2 GEMM -> max per centroid, at runtime n_dense / n_cent (n_cent * C <= 8192), for the three levels
+// (H, C) = (32, 64), (128, 128), (256, 256).
 // (reference: gnn.PointConv(local_nn)(x, (pos, pos[idx]), edge_index), models/pointcloud/pointnet2.py:31-35).
+//
+// k_sa_stream<..., X3 = false> is the exact-fp32 path (precision = "fp32": v_mfma_f32_32x32x2_f32 fma chains), for every object size.
+// k_sa_stream<..., X3 = true> is the f16x3 path of every level whose shape is NOT one of the 256-point ones (pointnet_numpoints != 256):
+// those run on the specialised kernels sa_points.hip / sa_rows.hip / sa3.hip (levels 1 / 2 / 3), which build their centroid tables in
+// LDS; here the centroid table B comes from HBM (k_sample_group writes B_l when the LDS centroid table is off).  This file also keeps
+// the range balancing and the kernel selection.
 //
 // Same arithmetic and register-resident weights as ws_gemm.hip (see the design notes there); this variant removes
 // every per-object bubble of the generic edge path:
@@ -13,30 +20,46 @@
 //     with double-buffered LDS staging tiles and one barrier per batch;
 //   * the per-object max accumulator is double-buffered in LDS too, so the finished object's [n_cent][C] block is
 //     written to HBM (and re-zeroed) underneath the MFMAs of the next object's first batch.
+// The two paths share all of that and differ at four places (if constexpr (X3) below):
+//   * stationary weights: fp32 keeps a [K/2][32-column] slice of W per lane half; f16x3 keeps a 32-column slice of the scaled layer-2
+//     image sa_w2_x3 as hi / lo planes (packing.py::pack_f16x3_scaled, register order: lane half u of MFMA step s holds
+//     k = u K/2 + 8 s .. + 7);
+//   * staging: fp32 writes the tile h = relu(A_j - B_i); f16x3 splits it into fp16 hi = fp16(h) and lo = fp16(h - hi) (both to
+//     nearest) and writes two fp16 planes;
+//   * MFMA block: fp32 chains; f16x3 runs hi.hi, hi.lo, lo.hi per step on v_mfma_f32_32x32x16_f16 into ONE fp32 accumulator that
+//     starts at the scaled bias;
+//   * f16x3 publishes the level's exact output maximum (guard slot G_F1 + l), as the specialised kernels do.
+// The drain multiplies by out_scale (f16x3: 1 / scale of the weight image) and writes out_rows rows per object
+// (SaParams::out_rows; rows past n_cent repeat centroid n_cent - 1: the padding that lets the GA max run over power-of-two groups).
+#include <type_traits>
+
 #include "t2p_common.h"
 
 namespace t2p {
 namespace {
 
-constexpr int kSub = 512;
-constexpr int NT = 512;   // threads per workgroup: 8 waves = 2 per SIMD, so one wave's VALU/LDS phases overlap the other's MFMAs  // objects whose row counts / self-loop bases are cached in LDS at a time
+constexpr int kSub = 512;   // objects whose row counts / self-loop bases are cached in LDS at a time
+constexpr int NT = 512;     // threads per workgroup: 8 waves = 2 per SIMD, so one wave's VALU/LDS phases overlap the other's MFMAs
 
-template <int K, int N, int WN, int RT>
+template <int K, int N, int WN, int RT, bool X3>
 struct SaCfg {
     static constexpr int WM = 8 / WN;
     static constexpr int NTW = N / (32 * WN);
-    static constexpr int KS = K / 2;
-    static constexpr int TR = WM * RT * 32;
-    static constexpr int LDH = K + 4;
-    static constexpr int HID_FLOATS = TR * LDH;
+    static constexpr int TR = WM * RT * 32;     // rows per batch
+    static constexpr int KS = K / 2;            // fp32: k-steps per lane half
+    static constexpr int S16 = K / 16;          // f16x3: MFMA steps
+    static constexpr int WPLANES = X3 ? 2 : 1;  // stationary weight registers w[plane][n-tile][step]: f16x3 hi / lo half8, fp32 floats
+    static constexpr int WSTEPS = X3 ? S16 : KS;
+    // staging tile: fp32 one plane of floats, f16x3 a hi and a lo plane of halves; rows padded by 16 bytes.  Both are PLANE * 4 bytes.
+    static constexpr int LD = X3 ? K + 8 : K + 4;   // elements per plane row
+    static constexpr int PLANE = TR * LD;           // elements per plane
     static constexpr int ACC_INTS = 8192 + N;  // n_cent * N (128x64, 64x128, 32x256) + one dummy row for padding rows
     static constexpr int F4_PER_ROW = K / 4;
-    static constexpr int TOTAL_F4 = TR * F4_PER_ROW;
-    static constexpr int ITERS = TOTAL_F4 / NT;
-    static_assert(TOTAL_F4 % NT == 0, "staging must divide evenly over the workgroup");
+    static constexpr int ITERS = TR * F4_PER_ROW / NT;
+    static_assert(TR * F4_PER_ROW % NT == 0, "staging must divide evenly over the workgroup");
+    static_assert(ITERS == 2 || ITERS == 4, "metadata vector is 4 or 8 bytes");
     static constexpr size_t lds_bytes() {
-        const size_t tile = (size_t)HID_FLOATS * 4;
-        return 2 * tile + (size_t)2 * ACC_INTS * 4 + 2 * TR + kSub * 2 + kSub * 4;
+        return (size_t)2 * PLANE * 4 + (size_t)2 * ACC_INTS * 4 + 2 * TR + kSub * 2 + kSub * 4;
     }
 };
 
@@ -100,16 +123,18 @@ struct BatchIt {  // position in the flattened batch stream of a sub-range
     int n;        // rows of the object
 };
 
-template <int K, int N, int WN, int RT>
-__global__ __launch_bounds__(NT, 2) void k_ws_sa(SaParams p) {
-    using C = SaCfg<K, N, WN, RT>;
+template <int K, int N, int WN, int RT, bool X3>
+__global__ __launch_bounds__(NT, 2) void k_sa_stream(SaParams p) {
+    using C = SaCfg<K, N, WN, RT, X3>;
+    using TileT = std::conditional_t<X3, _Float16, float>;
+    using WReg = std::conditional_t<X3, half8, float>;
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    float* hid = lds;                                       // fp32: [2][HID_FLOATS]
-    constexpr int TILE_FLOATS = C::HID_FLOATS;
-    int* acc_lds = (int*)(lds + 2 * TILE_FLOATS);           // [2][ACC_INTS]
+    TileT* tile = (TileT*)lds;                              // [2 buffers][fp32: PLANE floats | f16x3: hi plane, lo plane]
+    int* acc_lds = (int*)(lds + 2 * C::PLANE);              // [2][ACC_INTS]
     uint8_t* dstl = (uint8_t*)(acc_lds + 2 * C::ACC_INTS);  // [2][TR] destination (centroid) of every staged row
     uint16_t* nr = (uint16_t*)(dstl + 2 * C::TR);           // [kSub] rows per object
     int* sbase = (int*)(nr + kSub);                         // [kSub] source row of centroid 0's self loop
+    constexpr int TILE_ELEMS = C::WPLANES * C::PLANE;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wn = wave % WN, wm = wave / WN, h = lane >> 5, l31 = lane & 31;
@@ -117,18 +142,32 @@ __global__ __launch_bounds__(NT, 2) void k_ws_sa(SaParams p) {
     const int maxr = nc * 33;
     const int rows_out = p.out_rows > 0 ? p.out_rows : nc;
 
-    float w[C::NTW][C::KS];
-    #pragma unroll
+    // stationary weights: the wave's NTW column tiles, all K
+    WReg w[C::WPLANES][C::NTW][C::WSTEPS];
+    if constexpr (X3) {
+        const uint4* wp = (const uint4*)p.W_x3;
+        constexpr int PLANE_U4 = (N / 32) * C::S16 * 64;
+#pragma unroll
+        for (int nt = 0; nt < C::NTW; nt++)
+#pragma unroll
+            for (int s = 0; s < C::S16; s++) {
+                const int idx = (((wn * C::NTW + nt) * C::S16 + s) * 2 + h) * 32 + l31;
+                w[0][nt][s] = __builtin_bit_cast(half8, wp[idx]);
+                w[1][nt][s] = __builtin_bit_cast(half8, wp[PLANE_U4 + idx]);
+            }
+    } else {
+#pragma unroll
         for (int nt = 0; nt < C::NTW; nt++)
 #pragma unroll
             for (int s = 0; s < C::KS; s++)
-                w[nt][s] = p.W[(int64_t)(h * C::KS + s) * N + wn * C::NTW * 32 + nt * 32 + l31];
-    
+                w[0][nt][s] = p.W[(int64_t)(h * C::KS + s) * N + wn * C::NTW * 32 + nt * 32 + l31];
+    }
     float bias[C::NTW];
 #pragma unroll
     for (int nt = 0; nt < C::NTW; nt++) bias[nt] = p.bias[wn * C::NTW * 32 + nt * 32 + l31];
 
     for (int i = tid; i < 2 * C::ACC_INTS; i += NT) acc_lds[i] = 0;
+    [[maybe_unused]] float gmax = 0.f;   // f16x3: fp16-range guard, largest output this thread drained
 
     const int g_begin = p.bounds_ws[blockIdx.x], g_end = p.bounds_ws[blockIdx.x + 1];
 
@@ -156,7 +195,6 @@ __global__ __launch_bounds__(NT, 2) void k_ws_sa(SaParams p) {
 
         // Each thread stages ITERS consecutive rows (lr = (tid / F4_PER_ROW) * ITERS + k) at a fixed column quad, so its
         // row metadata is ONE aligned vector load of ITERS u16.
-        static_assert(C::ITERS == 2 || C::ITERS == 4, "metadata vector is 4 or 8 bytes");
         const int rgrp = (tid / C::F4_PER_ROW) * C::ITERS;   // first staged row of this thread inside the batch
         const int c4 = tid % C::F4_PER_ROW;
         typedef uint16_t metav __attribute__((ext_vector_type(C::ITERS)));
@@ -201,9 +239,9 @@ __global__ __launch_bounds__(NT, 2) void k_ws_sa(SaParams p) {
                 }
             }
         };
-        // W: h = relu(A_j - B_i) -> LDS tile, plus the destination byte of every row
+        // W: h = relu(A_j - B_i) -> LDS tile (f16x3: as fp16 hi / lo planes), plus the destination byte of every row
         auto write_tile = [&](int buf, const metav& m) {
-            float* dst = hid + buf * C::HID_FLOATS;
+            TileT* dst = tile + buf * TILE_ELEMS;
 #pragma unroll
             for (int k = 0; k < C::ITERS; k++) {
                 const int lr = rgrp + k;
@@ -211,8 +249,14 @@ __global__ __launch_bounds__(NT, 2) void k_ws_sa(SaParams p) {
                 f32x4 v;
 #pragma unroll
                 for (int e = 0; e < 4; e++) v[e] = fmaxf(t[e], 0.f);
-                                    *(f32x4*)(dst + lr * C::LDH + c4 * 4) = v;
-                
+                if constexpr (X3) {
+                    const half4 hv = __builtin_convertvector(v, half4);
+                    const half4 lv = __builtin_convertvector(v - __builtin_convertvector(hv, f32x4), half4);
+                    *(half4*)(dst + lr * C::LD + c4 * 4) = hv;
+                    *(half4*)(dst + C::PLANE + lr * C::LD + c4 * 4) = lv;
+                } else {
+                    *(f32x4*)(dst + lr * C::LD + c4 * 4) = v;
+                }
                 // destination of the row; padding rows go to the accumulator's dummy row n_cent
                 if (c4 == 0) dstl[buf * C::TR + lr] = m[k] == 0xFFFF ? (uint8_t)nc : (uint8_t)((m[k] >> 8) & 127);
             }
@@ -226,6 +270,7 @@ __global__ __launch_bounds__(NT, 2) void k_ws_sa(SaParams p) {
             for (int i = tid; i < nc * N; i += NT) {
                 const int c = i / N, col = i % N;
                 const float v = __int_as_float(a[i]) * p.out_scale;
+                if constexpr (X3) gmax = fmaxf(gmax, v);
                 o[c * (int64_t)p.ldo + col] = v;
                 if (c == nc - 1)
                     for (int r = nc; r < rows_out; r++) o[r * (int64_t)p.ldo + col] = v;
@@ -264,11 +309,28 @@ __global__ __launch_bounds__(NT, 2) void k_ws_sa(SaParams p) {
 #pragma unroll
                 for (int nt = 0; nt < C::NTW; nt++)
 #pragma unroll
-                    for (int e = 0; e < 16; e++) {
-                        acc[rt][nt][e] = bias[nt];  // bias rides in the accumulator
-                    }
+                    for (int e = 0; e < 16; e++) acc[rt][nt][e] = bias[nt];  // bias rides in the accumulator
             const int buf = t & 1;
-                            const float* hrow = hid + buf * C::HID_FLOATS + ((wm * RT) * 32 + l31) * C::LDH + h * C::KS;
+            const TileT* hrow = tile + buf * TILE_ELEMS + ((wm * RT) * 32 + l31) * C::LD + h * (K / 2);
+            if constexpr (X3) {
+#pragma unroll
+                for (int s = 0; s < C::S16; s++) {
+                    half8 a_hi[RT], a_lo[RT];
+#pragma unroll
+                    for (int rt = 0; rt < RT; rt++) {
+                        a_hi[rt] = *(const half8*)(hrow + rt * 32 * C::LD + 8 * s);
+                        a_lo[rt] = *(const half8*)(hrow + C::PLANE + rt * 32 * C::LD + 8 * s);
+                    }
+#pragma unroll
+                    for (int rt = 0; rt < RT; rt++)
+#pragma unroll
+                        for (int nt = 0; nt < C::NTW; nt++) {
+                            acc[rt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_hi[rt], w[0][nt][s], acc[rt][nt], 0, 0, 0);
+                            acc[rt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_hi[rt], w[1][nt][s], acc[rt][nt], 0, 0, 0);
+                            acc[rt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_lo[rt], w[0][nt][s], acc[rt][nt], 0, 0, 0);
+                        }
+                }
+            } else {
                 constexpr int QC = 4;                 // k-quads (16 k-steps) fetched per LDS round
                 constexpr int NCH = C::KS / 4 / QC;   // chunks
                 static_assert((C::KS / 4) % QC == 0, "K/8 must be a multiple of the LDS prefetch chunk");
@@ -276,7 +338,7 @@ __global__ __launch_bounds__(NT, 2) void k_ws_sa(SaParams p) {
 #pragma unroll
                 for (int rt = 0; rt < RT; rt++)
 #pragma unroll
-                    for (int qi = 0; qi < QC; qi++) a_cur[rt][qi] = *(const f32x4*)(hrow + rt * 32 * C::LDH + qi * 4);
+                    for (int qi = 0; qi < QC; qi++) a_cur[rt][qi] = *(const f32x4*)(hrow + rt * 32 * C::LD + qi * 4);
 #pragma unroll
                 for (int ch = 0; ch < NCH; ch++) {
                     if (ch + 1 < NCH) {
@@ -284,7 +346,7 @@ __global__ __launch_bounds__(NT, 2) void k_ws_sa(SaParams p) {
                         for (int rt = 0; rt < RT; rt++)
 #pragma unroll
                             for (int qi = 0; qi < QC; qi++)
-                                a_nxt[rt][qi] = *(const f32x4*)(hrow + rt * 32 * C::LDH + ((ch + 1) * QC + qi) * 4);
+                                a_nxt[rt][qi] = *(const f32x4*)(hrow + rt * 32 * C::LD + ((ch + 1) * QC + qi) * 4);
                     }
 #pragma unroll
                     for (int qi = 0; qi < QC; qi++)
@@ -295,16 +357,17 @@ __global__ __launch_bounds__(NT, 2) void k_ws_sa(SaParams p) {
 #pragma unroll
                                 for (int nt = 0; nt < C::NTW; nt++)
                                     acc[rt][nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(
-                                        a_cur[rt][qi][j], w[nt][(ch * QC + qi) * 4 + j], acc[rt][nt], 0, 0, 0);
+                                        a_cur[rt][qi][j], w[0][nt][(ch * QC + qi) * 4 + j], acc[rt][nt], 0, 0, 0);
 #pragma unroll
                     for (int rt = 0; rt < RT; rt++)
 #pragma unroll
                         for (int qi = 0; qi < QC; qi++) a_cur[rt][qi] = a_nxt[rt][qi];
                 }
-            
+            }
+
             // max-aggregation: every accumulator row goes straight to its destination's LDS slot with an integer atomic
-            // max (non-returning; the signed-int max against +0 is also the ReLU).  No run detection, no branches:
-            // padding rows carry destination n_cent = the accumulator's dummy row.
+            // max (non-returning; the signed-int max against +0 is also the ReLU - the f16x3 scale is a positive power of two).
+            // No run detection, no branches: padding rows carry destination n_cent = the accumulator's dummy row.
             const int abuf = it_c.gi & 1;
             int* accb = acc_lds + abuf * C::ACC_INTS;
             const uint8_t* dl = dstl + buf * C::TR;
@@ -340,32 +403,11 @@ __global__ __launch_bounds__(NT, 2) void k_ws_sa(SaParams p) {
         }
         if (flush_g >= 0) flush(flush_g, flush_buf);
     }
-}
-
-template <int K, int N, int WN, int RT>
-int launch_sa_cfg(const SaParams& p_in, hipStream_t st, const char* name) {
-    using C = SaCfg<K, N, WN, RT>;
-    auto kern = k_ws_sa<K, N, WN, RT>;
-    T2P_TRY(reserve_lds((const void*)kern, C::lds_bytes(), "ws_sa"));
-    if (p_in.n_obj <= 0) return 0;
-    T2P_CHECK_ARG(p_in.n_obj < (1 << 30) && p_in.n_obj * p_in.n_dense < 0x7fffffffLL, "ws_sa: chunk too large for 32-bit rows");
-    int n_wg = num_cus();
-    if (n_wg > p_in.n_obj) n_wg = (int)p_in.n_obj;
-    const SaParams& p = p_in;
-    if (!p.balanced) {
-        ProfScope ps_("sa_balance", st);
-        hipLaunchKernelGGL(k_balance, dim3(1), dim3(1024), 0, st, p.n_rows, (int)p.n_obj, C::TR, n_wg, p.prefix_ws,
-                           p.bounds_ws);
-        T2P_CHECK_LAUNCH("sa_balance");
-    }
-    ProfScope ps_(name, st);
-    hipLaunchKernelGGL(kern, dim3(n_wg), dim3(NT), C::lds_bytes(), st, p);
-    T2P_CHECK_LAUNCH("ws_sa");
-    return 0;
+    // f16x3: the level's exact output maximum (high and low side of the guard), once per wave
+    if constexpr (X3) guard_publish_exact(p.amax_out, gmax);
 }
 
 }  // namespace
-
 
 int launch_sa_balance(const SaParams& p, int tile_rows, int n_wg, hipStream_t st) {
     ProfScope ps_("sa_balance", st);
@@ -375,11 +417,73 @@ int launch_sa_balance(const SaParams& p, int tile_rows, int n_wg, hipStream_t st
     return 0;
 }
 
+namespace {
+
+// The stream kernel's instantiations (K = H, N = C, WN, RT), both arithmetic paths: launch and launch shape go through this one list
+#define SA_STREAM_CASES(X) X(32, 64, 2, 2) X(128, 128, 4, 1) X(256, 256, 8, 1)
+
+// tile rows / workgroup count (bounds_ws holds 1,025 entries) of the stream kernel for (H, Cout)
+int sa_stream_shape(int H, int Cout, bool x3, int64_t n_obj, int* tile_rows, int* n_wg) {
+    int n = num_cus();
+    if (n > 1024) n = 1024;
+    if (n > n_obj) n = (int)n_obj;
+    *n_wg = n;
+#define SA_CASE(K_, N_, WN_, RT_)                           \
+    if (H == K_ && Cout == N_) {                            \
+        *tile_rows = SaCfg<K_, N_, WN_, RT_, false>::TR;    \
+        return 0;                                           \
+    }
+    SA_STREAM_CASES(SA_CASE)
+#undef SA_CASE
+    if (x3) set_error("sa_x3: no instantiation for H=%d C=%d (built: 32/64, 128/128, 256/256)", H, Cout);
+    else set_error("ws_sa: no instantiation for H=%d C=%d", H, Cout);
+    return T2P_E_UNSUPPORTED;
+}
+
+template <int K, int N, int WN, int RT, bool X3>
+int launch_sa_cfg(const SaParams& p, hipStream_t st, const char* name) {
+    using C = SaCfg<K, N, WN, RT, X3>;
+    static_assert(C::TR == SaCfg<K, N, WN, RT, !X3>::TR, "one launch shape for both paths");
+    constexpr const char* who = X3 ? "sa_x3" : "ws_sa";
+    auto kern = k_sa_stream<K, N, WN, RT, X3>;
+    T2P_TRY(reserve_lds((const void*)kern, C::lds_bytes(), who));
+    if (p.n_obj <= 0) return 0;
+    // the kernel forms srow * K in 32 bits
+    T2P_CHECK_ARG(p.n_obj < (1 << 30) && p.n_obj * p.n_dense * (int64_t)K < 0xffffffffLL,
+                  X3 ? "sa_x3: chunk too large for 32-bit table offsets" : "ws_sa: chunk too large for 32-bit rows");
+    int tr = 0, n_wg = 0;
+    T2P_TRY(sa_stream_shape(K, N, X3, p.n_obj, &tr, &n_wg));
+    if (!p.balanced) T2P_TRY(launch_sa_balance(p, tr, n_wg, st));
+    ProfScope ps_(name, st);
+    T2P_REPEAT(ps_) hipLaunchKernelGGL(kern, dim3(n_wg), dim3(NT), C::lds_bytes(), st, p);
+    T2P_CHECK_LAUNCH(who);
+    return 0;
+}
+
+int launch_sa_stream(int H, int Cout, const SaParams& p, hipStream_t st) {
+    const bool x3 = p.W_x3 != nullptr;
+    if (x3) {
+        T2P_CHECK_ARG(p.Bc != nullptr && p.wp == nullptr, "sa_x3: reads the centroid table B from HBM (Bc set, wp unset)");
+        T2P_CHECK_ARG(p.n_cent >= 1 && p.n_cent <= 128 && p.n_dense >= p.n_cent && p.n_dense <= 256 && (int64_t)p.n_cent * Cout <= 8192,
+                      "sa_x3: n_dense=%d n_cent=%d C=%d outside the accumulator (n_cent * C <= 8192)", p.n_dense, p.n_cent, Cout);
+        T2P_CHECK_ARG(p.out_rows == 0 || p.out_rows >= p.n_cent, "sa_x3: out_rows=%d < n_cent=%d", p.out_rows, p.n_cent);
+        T2P_CHECK_ARG((((uintptr_t)p.A | (uintptr_t)p.Bc | (uintptr_t)p.W_x3 | (uintptr_t)p.rows) & 15) == 0,
+                      "sa_x3: tables and weights must be 16-byte aligned");
+    }
+#define SA_CASE(K_, N_, WN_, RT_)                                                                                  \
+    if (H == K_ && Cout == N_)                                                                                     \
+        return x3 ? launch_sa_cfg<K_, N_, WN_, RT_, true>(p, st, "sa_x3_k" #K_ "_n" #N_)                           \
+                  : launch_sa_cfg<K_, N_, WN_, RT_, false>(p, st, "ws_edge_sa_k" #K_ "_n" #N_);
+    SA_STREAM_CASES(SA_CASE)
+#undef SA_CASE
+    int tr, n_wg;
+    return sa_stream_shape(H, Cout, x3, 1, &tr, &n_wg);   // no such instantiation: its error
+}
 
 // f16x3: the specialised kernels take exactly the level shape of 256 points per object they are built for (with the LDS centroid
-// table); every other shape runs on sa_x3.hip, which gathers the centroid table from HBM
+// table); every other shape runs on the stream kernel, which gathers the centroid table from HBM
 enum SaKernel { SA_FP32, SA_POINTS, SA_ROWS, SA_3, SA_X3, SA_NONE };
-static SaKernel sa_pick(int H, int Cout, const SaParams& p) {
+SaKernel sa_pick(int H, int Cout, const SaParams& p) {
     if (p.W_x3 == nullptr) return SA_FP32;
     if (p.n_dense == 128 && p.n_cent == 64 && sa_rows_selected(H, Cout, p)) return SA_ROWS;
     if (p.n_dense == 256 && p.n_cent == 128 && sa_points_selected(H, Cout, p)) return SA_POINTS;
@@ -391,24 +495,19 @@ static SaKernel sa_pick(int H, int Cout, const SaParams& p) {
 }
 
 // tile rows / workgroup count of the kernel launch_ws_sa will pick for (H, Cout)
-static int sa_launch_shape(int H, int Cout, const SaParams& p, int64_t n_obj, int* tile_rows, int* n_wg) {
+int sa_launch_shape(int H, int Cout, const SaParams& p, int64_t n_obj, int* tile_rows, int* n_wg) {
     switch (sa_pick(H, Cout, p)) {
         case SA_ROWS: return sa_rows_launch_shape(n_obj, tile_rows, n_wg);
         case SA_POINTS: return sa_points_launch_shape(n_obj, tile_rows, n_wg);
         case SA_3: return sa3_launch_shape(n_obj, tile_rows, n_wg);
-        case SA_X3: return sa_x3_launch_shape(H, Cout, n_obj, tile_rows, n_wg);
-        case SA_NONE: return T2P_E_UNSUPPORTED;
-        case SA_FP32: break;
+        case SA_X3: return sa_stream_shape(H, Cout, true, n_obj, tile_rows, n_wg);
+        case SA_FP32: return sa_stream_shape(H, Cout, false, n_obj, tile_rows, n_wg);
+        case SA_NONE: break;
     }
-    int n = num_cus();
-    if (n > n_obj) n = (int)n_obj;
-    *n_wg = n;
-    if (H == 32 && Cout == 64) { *tile_rows = SaCfg<32, 64, 2, 2>::TR; return 0; }
-    if (H == 128 && Cout == 128) { *tile_rows = SaCfg<128, 128, 4, 1>::TR; return 0; }
-    if (H == 256 && Cout == 256) { *tile_rows = SaCfg<256, 256, 8, 1>::TR; return 0; }
-    set_error("ws_sa: no instantiation for H=%d C=%d", H, Cout);
     return T2P_E_UNSUPPORTED;
 }
+
+}  // namespace
 
 int launch_sa_balance_levels(const SaParams p[3], const int H[3], const int C[3], hipStream_t st) {
     if (p[0].n_obj <= 0) return 0;
@@ -428,21 +527,15 @@ int launch_sa_balance_levels(const SaParams p[3], const int H[3], const int C[3]
 
 int launch_ws_sa(int H, int Cout, const SaParams& p, hipStream_t st) {
     T2P_CHECK_ARG((((uintptr_t)p.A | (uintptr_t)p.Bc) & 15) == 0, "ws_sa: tables must be 16-byte aligned");
-    if (p.W_x3 != nullptr) {  // f16x3 split-precision path: one kernel per level
-        T2P_CHECK_ARG(((uintptr_t)p.W_x3 & 15) == 0, "ws_sa: packed f16x3 weights must be 16-byte aligned");
-        switch (sa_pick(H, Cout, p)) {
-            case SA_ROWS: return launch_sa_rows(H, Cout, p, st);
-            case SA_POINTS: return launch_sa_points(H, Cout, p, st);
-            case SA_3: return launch_sa3(p, st);
-            case SA_X3: return launch_sa_x3(H, Cout, p, st);
-            default: return T2P_E_UNSUPPORTED;
-        }
-    } else {
-        if (H == 32 && Cout == 64) return launch_sa_cfg<32, 64, 2, 2>(p, st, "ws_edge_sa_k32_n64");
-        if (H == 128 && Cout == 128) return launch_sa_cfg<128, 128, 4, 1>(p, st, "ws_edge_sa_k128_n128");
-        if (H == 256 && Cout == 256) return launch_sa_cfg<256, 256, 8, 1>(p, st, "ws_edge_sa_k256_n256");
+    if (p.W_x3 != nullptr) T2P_CHECK_ARG(((uintptr_t)p.W_x3 & 15) == 0, "ws_sa: packed f16x3 weights must be 16-byte aligned");
+    switch (sa_pick(H, Cout, p)) {   // f16x3: one kernel per level
+        case SA_ROWS: return launch_sa_rows(H, Cout, p, st);
+        case SA_POINTS: return launch_sa_points(H, Cout, p, st);
+        case SA_3: return launch_sa3(p, st);
+        case SA_X3:
+        case SA_FP32: return launch_sa_stream(H, Cout, p, st);
+        case SA_NONE: break;
     }
-    set_error("ws_sa: no instantiation for H=%d C=%d", H, Cout);
     return T2P_E_UNSUPPORTED;
 }
 

@@ -388,7 +388,28 @@ int t2p_encode_text(const int32_t* tokens, const int32_t* lengths, int64_t batch
  * (float64 `cell_encodings @ text_encodings[q]`, `argsort(-scores)[:k]`).
  * queries [nq][dim], cells [nc][dim] fp32; out_idx [nq][k] int64 (= cell row + index_offset, ties -> lower index,
  * -1 when nc < k), out_score [nq][k] float64.
+ *
+ * 1 <= k <= T2P_SIM_TOPK_MAX_K (T2P_E_ARG otherwise, nothing launched); dim 128, 256 or 384.  The float64 score of a
+ * (query, cell) pair, and the order (score descending, ties and -0.0 / +0.0 to the lower cell index), do not depend on k:
+ * the first j columns of a k-result are the j-result, bit for bit.  A NaN score is never retrieved; when fewer than k
+ * cells qualify the tail is -1 / -inf.
+ *   k <= T2P_SIM_TOPK_REG_K: per-lane candidate lists in registers, scores never leave the chip.  Workspace:
+ *     nq * splits * 4 * 16 * 12 + 256 bytes, splits = the cell ranges the launch divides the database into (it depends on
+ *     nq, nc and the device's CU count, not on k).
+ *   k >  T2P_SIM_TOPK_REG_K: the call walks the queries in chunks; per chunk one kernel writes the chunk's float64 scores
+ *     into the workspace and one workgroup per query selects its k exactly (radix selection on order-preserving keys,
+ *     lowest-index ties by an ascending sweep, sort in LDS).  Workspace = one chunk's score tile, never more than
+ *     T2P_SIM_TOPK_TILE_BYTES whatever nq, nc and k:
+ *         ld    = ceil(nc / 16) * 16                       doubles per query row
+ *         cap   = floor((T2P_SIM_TOPK_TILE_BYTES - 256) / (8 * ld)), rounded down to a multiple of 128 when >= 128
+ *         chunk = min(nq, cap)                             queries per chunk
+ *         bytes = chunk * 8 * ld + 256
+ *     cap == 0, i.e. one query's scores (8 * nc bytes, nc > 33,554,400) exceed the tile: T2P_E_ARG with a message that
+ *     says so (the k <= T2P_SIM_TOPK_REG_K path has no such limit besides nc < 2^31).  The workspace must be 16-byte aligned.
  * ---------------------------------------------------------------------------------------------------------- */
+#define T2P_SIM_TOPK_MAX_K 1024
+#define T2P_SIM_TOPK_REG_K 16
+#define T2P_SIM_TOPK_TILE_BYTES ((size_t)256 << 20) /* the MI355X's Infinity Cache: the selection re-reads the tile from it */
 size_t t2p_sim_topk_workspace_bytes(int64_t nq, int64_t nc, int32_t k);
 int t2p_sim_topk(const float* queries, const float* cells, int64_t nq, int64_t nc, int32_t dim, int32_t k,
                  int64_t index_offset, int64_t* out_idx, double* out_score, void* workspace, size_t workspace_bytes,

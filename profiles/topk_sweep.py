@@ -1,0 +1,74 @@
+# Time of one retrieval call (text2pos_amd.retrieve_topk = t2p_sim_topk) over k, beside torch's float64 GEMM + topk on the same
+# tensors: one JSON line per (shape, k).  Device events around `--calls` back-to-back calls, median over `--steps` such windows
+# after `--warmup` of them; the per-kernel split comes from a separate profiled call (ops.profile_report), outside the timed windows.
+#   python profiles/topk_sweep.py [--shapes 1000x12000,1250x100000] [--ks 10,16,17,32,100,256,1024] [--steps 9] [--warmup 3]
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import text2pos_amd as t2p  # noqa: E402
+from text2pos_amd import ops  # noqa: E402
+
+
+def timed(fn, steps, warmup, calls):
+    """median / min / max milliseconds per call over `steps` windows of `calls` calls each"""
+    ms = []
+    for i in range(warmup + steps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(calls):
+            fn()
+        e1.record()
+        e1.synchronize()
+        if i >= warmup:
+            ms.append(e0.elapsed_time(e1) / calls)
+    return float(np.median(ms)), min(ms), max(ms)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--shapes", default="1000x12000,1250x100000")
+    ap.add_argument("--ks", default="10,16,17,32,100,256,1024")
+    ap.add_argument("--dim", type=int, default=256)
+    ap.add_argument("--steps", type=int, default=9)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--calls", type=int, default=0, help="calls per timed window (0: 20 for the small shape, 3 above 10^8 scores)")
+    a = ap.parse_args()
+    assert torch.cuda.is_available(), "topk_sweep needs cuda:0: there is no CPU path to time"
+    dev = torch.device("cuda:0")
+    for shape in a.shapes.split(","):
+        nq, nc = (int(x) for x in shape.split("x"))
+        g = torch.Generator().manual_seed(nq * 31 + nc)
+        c = torch.nn.functional.normalize(torch.randn(nc, a.dim, generator=g), dim=-1).to(dev)
+        q = torch.nn.functional.normalize(torch.randn(nq, a.dim, generator=g), dim=-1).to(dev)
+        calls = a.calls or (20 if nq * nc <= 10 ** 8 else 3)
+        cd, qd = c.double(), q.double()      # (the yardstick's conversion is not in its time)
+        for k in (int(x) for x in a.ks.split(",")):
+            med, lo, hi = timed(lambda: t2p.retrieve_topk(c, q, k), a.steps, a.warmup, calls)
+            t_med, t_lo, t_hi = timed(lambda: (qd @ cd.T).topk(k), a.steps, a.warmup, calls)
+            idx, score = t2p.retrieve_topk(c, q, k)
+            want = (qd @ cd.T).topk(k)
+            torch.cuda.synchronize()
+            ops.profile_report()
+            ops.profile_enable(True)
+            try:
+                t2p.retrieve_topk(c, q, k)
+            finally:
+                ops.profile_enable(False)
+            kernels = {n: dict(launches=cnt, ms=round(ms, 4)) for n, (cnt, ms) in ops.profile_report().items()}
+            print(json.dumps(dict(nq=nq, nc=nc, dim=a.dim, k=k, calls_per_window=calls, steps=a.steps,
+                                  ms=round(med, 4), ms_min=round(lo, 4), ms_max=round(hi, 4),
+                                  torch_f64_gemm_topk_ms=round(t_med, 4), torch_min=round(t_lo, 4), torch_max=round(t_hi, 4),
+                                  kernels=kernels, workspace_bytes=int(ops.L.lib().t2p_sim_topk_workspace_bytes(nq, nc, k)),
+                                  max_score_diff_vs_torch=float((score - want.values).abs().max()))), flush=True)
+        del c, q, cd, qd
+
+
+if __name__ == "__main__":
+    main()

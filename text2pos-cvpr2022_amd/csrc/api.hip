@@ -1019,9 +1019,11 @@ size_t t2p_sim_topk_workspace_bytes(int64_t nq, int64_t nc, int32_t k) { return 
 int t2p_sim_topk(const float* queries, const float* cells, int64_t nq, int64_t nc, int32_t dim, int32_t k,
                  int64_t index_offset, int64_t* out_idx, double* out_score, void* workspace, size_t workspace_bytes,
                  t2p_stream_t stream) {
-    T2P_CHECK_ARG(queries != nullptr && cells != nullptr && out_idx != nullptr && out_score != nullptr,
-                  "sim_topk: NULL argument");
     T2P_CHECK_ARG(nq >= 0 && nc >= 0, "sim_topk: negative size");
+    // an empty side has no storage to point to (nq == 0 launches nothing; k < 1 is refused below, by its range)
+    T2P_CHECK_ARG((queries != nullptr || nq == 0) && (cells != nullptr || nc == 0) &&
+                      ((out_idx != nullptr && out_score != nullptr) || nq == 0 || k < 1),
+                  "sim_topk: NULL argument");
     return launch_sim_topk(queries, cells, nq, nc, dim, k, index_offset, out_idx, out_score, workspace, workspace_bytes,
                            (hipStream_t)stream);
 }

@@ -1,4 +1,4 @@
-// All-pairs cosine scores in float64 + ordered top-k, scores never materialised in HBM.
+// All-pairs cosine scores in float64 + ordered top-k; up to k = 16 the scores never leave the chip.
 //
 // Replaces the host loop of training/coarse.py:134-140 (per query: `scores = cell_encodings[:] @ text_encodings[q]`
 // on float64 arrays, `np.argsort(-scores)[0:max(top_k)]`).  The reference ranks in float64 (np.zeros arrays,
@@ -6,18 +6,29 @@
 // fly and every score is an fp64 fma chain -- ranking ties are then only exact duplicates, which are ordered by
 // ascending cell index (the pinned stable order, oracle/model.py::retrieve_topk_f64).
 //
+// k <= KREG:
 // Pass 1  (grid = query blocks x cell splits): a workgroup keeps 128 queries as MFMA B operands in registers
 //         (fp32, widened at use), streams its cell range through LDS in 32-row blocks (register-prefetched) and
 //         every lane maintains a private sorted top-KCAP list per query in registers.
 // Pass 2  (one wave per query): k-round ordered selection over the 4 x splits partial lists.
+//
+// k > KREG (up to KMAX) cannot keep a list per lane.  The same product loop (sim_product_loop: the score bits of a pair do
+// not depend on k) then writes a chunk of queries' float64 scores to the workspace (k_sim_scores), and one workgroup per
+// query selects exactly (k_topk_select): MSB-first radix passes over order-preserving 64-bit keys find the k-th key and
+// the number of keys above it, an ascending-index sweep with a scan collects everything above and the lowest-index ties,
+// and a bitonic sort in LDS puts the k candidates into better() order.  Queries go through in chunks whose score tile
+// stays within 256 MiB (the Infinity Cache: the select passes re-read what the score kernel just wrote).
 #include "t2p_common.h"
 
 namespace t2p {
 namespace {
 
-constexpr int KCAP = 16;     // per-lane list capacity == largest supported k
+constexpr int KREG = 16;     // per-lane list capacity == largest k of the register-list path
+constexpr int KCAP = KREG;
+constexpr int KMAX = 1024;   // largest supported k (the select kernel's LDS candidate array)
 constexpr int QB = 128;      // queries per workgroup (4 waves x 2 tiles x 16)
 constexpr int CB = 32;       // cells staged per iteration
+typedef double f64x2 __attribute__((ext_vector_type(2)));
 
 struct Cand {
     double s;
@@ -25,19 +36,22 @@ struct Cand {
 };
 __device__ __forceinline__ bool better(double s, int i, double s2, int i2) { return s > s2 || (s == s2 && i < i2); }
 
-template <int DIM>
-__global__ __launch_bounds__(256, 1) void k_sim_partial(const float* __restrict__ Q, const float* __restrict__ Cm,
-                                                         int64_t nq, int64_t nc, int cells_per_split,
-                                                         double* __restrict__ ps, int* __restrict__ pi, int n_split) {
+// D layout of v_mfma_f64_16x16x4_f64: column (query) = lane & 15, row (cell) = (lane >> 4) + 4 * reg
+__device__ __forceinline__ int d_row(int lane, int reg) { return (lane >> 4) + 4 * reg; }
+
+// The product loop of both paths: a workgroup of 4 waves keeps queries [q0_wg, q0_wg + QB) as MFMA B operands in registers
+// (wave w: two 16-query tiles from q0_wg + 32 w), streams cells [c_begin, c_end) through c_lds in CB-row blocks
+// (register-prefetched) and hands every finished 16 x 16 tile to epi(t, cell0, acc): lane `lane` holds, for query
+// q0_wg + 32 w + 16 t + (lane & 15), the scores of cells cell0 + d_row(lane, r) in acc[r], r = 0..3 (cells >= c_end are
+// products with zero rows; the epilogue drops them).  One fp64 fma chain over dim per pair, the same whatever the epilogue.
+template <int DIM, class Epi>
+__device__ __forceinline__ void sim_product_loop(const float* __restrict__ Q, const float* __restrict__ Cm, int64_t nq,
+                                                 int64_t q0_wg, int64_t c_begin, int64_t c_end, float* c_lds, Epi&& epi) {
     constexpr int LDC = DIM + 4;
     constexpr int KQ = DIM / 4;   // k per lane group (lane>>4 owns k in [g*KQ, (g+1)*KQ))
     constexpr int F4 = CB * DIM / 4 / 256;
-    __shared__ __attribute__((aligned(16))) float c_lds[CB * LDC];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g4 = lane >> 4, l15 = lane & 15;
-    const int64_t q0 = (int64_t)blockIdx.x * QB + wave * 32;
-    const int split = blockIdx.y;
-    const int64_t c_begin = (int64_t)split * cells_per_split;
-    const int64_t c_end = (c_begin + cells_per_split) < nc ? (c_begin + cells_per_split) : nc;
+    const int64_t q0 = q0_wg + wave * 32;
 
     // B operands: this wave's 2 query tiles, fp32 in registers
     float qreg[2][KQ];
@@ -52,12 +66,6 @@ __global__ __launch_bounds__(256, 1) void k_sim_partial(const float* __restrict_
             for (int e = 0; e < 4; e++) qreg[t][s4 * 4 + e] = v[e];
         }
     }
-    double ls[2][KCAP];
-    int li[2][KCAP];
-#pragma unroll
-    for (int t = 0; t < 2; t++)
-#pragma unroll
-        for (int j = 0; j < KCAP; j++) { ls[t][j] = -INFINITY; li[t][j] = 0x7fffffff; }
 
     f32x4 stage[F4];
     auto load_block = [&](int64_t cb) {
@@ -100,33 +108,53 @@ __global__ __launch_bounds__(256, 1) void k_sim_partial(const float* __restrict_
                         acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(ad, (double)qreg[t][s4 * 4 + e], acc[t], 0, 0, 0);
                 }
             }
-            // D layout (f64 16x16x4): column (query) = lane&15, row (cell) = (lane>>4) + 4*reg
 #pragma unroll
-            for (int t = 0; t < 2; t++) {
-#pragma unroll
-                for (int r = 0; r < 4; r++) {
-                    const int64_t cell = cb + ct * 16 + g4 + 4 * r;
-                    const double s = acc[t][r];
-                    const int ci = (int)cell;
-                    if (cell < c_end && better(s, ci, ls[t][KCAP - 1], li[t][KCAP - 1])) {
-                        ls[t][KCAP - 1] = s;
-                        li[t][KCAP - 1] = ci;
-#pragma unroll
-                        for (int j = KCAP - 1; j > 0; j--) {
-                            const bool sw = better(ls[t][j], li[t][j], ls[t][j - 1], li[t][j - 1]);
-                            const double ts = ls[t][j];
-                            const int ti = li[t][j];
-                            ls[t][j] = sw ? ls[t][j - 1] : ts;
-                            li[t][j] = sw ? li[t][j - 1] : ti;
-                            ls[t][j - 1] = sw ? ts : ls[t][j - 1];
-                            li[t][j - 1] = sw ? ti : li[t][j - 1];
-                        }
-                    }
-                }
-            }
+            for (int t = 0; t < 2; t++) epi(t, cb + ct * 16, acc[t]);
         }
         __syncthreads();
     }
+}
+
+template <int DIM>
+__global__ __launch_bounds__(256, 1) void k_sim_partial(const float* __restrict__ Q, const float* __restrict__ Cm,
+                                                         int64_t nq, int64_t nc, int cells_per_split,
+                                                         double* __restrict__ ps, int* __restrict__ pi, int n_split) {
+    __shared__ __attribute__((aligned(16))) float c_lds[CB * (DIM + 4)];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g4 = lane >> 4, l15 = lane & 15;
+    const int64_t q0 = (int64_t)blockIdx.x * QB + wave * 32;
+    const int split = blockIdx.y;
+    const int64_t c_begin = (int64_t)split * cells_per_split;
+    const int64_t c_end = (c_begin + cells_per_split) < nc ? (c_begin + cells_per_split) : nc;
+
+    double ls[2][KCAP];
+    int li[2][KCAP];
+#pragma unroll
+    for (int t = 0; t < 2; t++)
+#pragma unroll
+        for (int j = 0; j < KCAP; j++) { ls[t][j] = -INFINITY; li[t][j] = 0x7fffffff; }
+
+    sim_product_loop<DIM>(Q, Cm, nq, (int64_t)blockIdx.x * QB, c_begin, c_end, c_lds, [&](int t, int64_t cell0, const f64x4& acc) {
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            const int64_t cell = cell0 + d_row(lane, r);
+            const double s = acc[r];
+            const int ci = (int)cell;
+            if (cell < c_end && better(s, ci, ls[t][KCAP - 1], li[t][KCAP - 1])) {
+                ls[t][KCAP - 1] = s;
+                li[t][KCAP - 1] = ci;
+#pragma unroll
+                for (int j = KCAP - 1; j > 0; j--) {
+                    const bool sw = better(ls[t][j], li[t][j], ls[t][j - 1], li[t][j - 1]);
+                    const double ts = ls[t][j];
+                    const int ti = li[t][j];
+                    ls[t][j] = sw ? ls[t][j - 1] : ts;
+                    li[t][j] = sw ? li[t][j - 1] : ti;
+                    ls[t][j - 1] = sw ? ts : ls[t][j - 1];
+                    li[t][j - 1] = sw ? ti : li[t][j - 1];
+                }
+            }
+        }
+    });
     // partial lists: [q][split][g4][KCAP]
 #pragma unroll
     for (int t = 0; t < 2; t++) {
@@ -176,8 +204,240 @@ __global__ __launch_bounds__(256) void k_topk_merge(const double* __restrict__ p
     }
 }
 
+// ---- k in (KREG, KMAX]: score tile + exact selection ---------------------------------------------------------------------
+// Score tile of a query chunk: row q holds ld_s (a multiple of 16) doubles.  A lane of the product loop owns cells
+// cell0 + (lane >> 4) + 4 r of a 16-cell tile; it stores its four scores side by side, so cell c of a row sits at
+// tile_pos(c) = (c & ~15) | (c & 3) << 2 | (c >> 2) & 3 (the two 2-bit fields swapped; its own inverse) and the four lane
+// groups of a query fill one 128-byte line.
+__device__ __forceinline__ int tile_pos(int c) { return (c & ~15) | ((c & 3) << 2) | ((c >> 2) & 3); }
+
+template <int DIM>
+__global__ __launch_bounds__(256, 1) void k_sim_scores(const float* __restrict__ Q, const float* __restrict__ Cm,
+                                                        int64_t nq, int64_t nc, int cells_per_split,
+                                                        double* __restrict__ S, int64_t ld_s) {
+    __shared__ __attribute__((aligned(16))) float c_lds[CB * (DIM + 4)];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g4 = lane >> 4, l15 = lane & 15;
+    const int64_t q0 = (int64_t)blockIdx.x * QB + wave * 32;
+    const int64_t c_begin = (int64_t)blockIdx.y * cells_per_split;
+    const int64_t c_end = (c_begin + cells_per_split) < nc ? (c_begin + cells_per_split) : nc;
+    sim_product_loop<DIM>(Q, Cm, nq, (int64_t)blockIdx.x * QB, c_begin, c_end, c_lds, [&](int t, int64_t cell0, const f64x4& acc) {
+        const int64_t q = q0 + t * 16 + l15;
+        // whole 16-cell tiles: cell0 < c_end <= nc keeps cell0 + 15 < ld_s; the cells past nc in the last one are never read
+        if (q < nq && cell0 < c_end) {
+            double* dst = S + q * ld_s + cell0 + g4 * 4;   // == tile_pos(cell0 + d_row(lane, r)) for r = 0..3
+            *(f64x2*)dst = f64x2{acc[0], acc[1]};
+            *(f64x2*)(dst + 2) = f64x2{acc[2], acc[3]};
+        }
+    });
+}
+
+// Order-preserving key of a score: a > b as doubles <=> key(a) > key(b); -0.0 and +0.0 share a key; every NaN maps to 0,
+// below -inf (whose key is 0x000f'ffff'ffff'ffff), so "key > 0" is "may be retrieved".
+__device__ __forceinline__ uint64_t score_key(double s) {
+    uint64_t u = (uint64_t)__double_as_longlong(s);
+    if (s != s) return 0;
+    if (s == 0.0) u = 0;
+    return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+}
+
+constexpr int SEL_T = 1024;       // threads of the select workgroup: a pass is a chain of dependent L2 / Infinity Cache reads per
+constexpr int SEL_W = SEL_T / 64; // thread, and a chunk of a large database has only a few hundred queries (= workgroups) to hide them
+constexpr int SEL_U = 4;          // loads in flight per thread in the passes over the scores
+constexpr int RBITS = 11;         // radix bits per pass: 2048 bins = 8 KB of LDS, 2 bins per thread in the suffix scan
+constexpr int RBINS = 1 << RBITS;
+
+// exclusive prefix sum over the workgroup's threads; wsum: SEL_W ints of LDS.  Every thread must call it.
+__device__ __forceinline__ int block_excl_scan(int v, int* wsum) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int inc = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int up = __shfl_up(inc, o, 64);
+        if (lane >= o) inc += up;
+    }
+    __syncthreads();   // (wsum may still be read from the previous call)
+    if (lane == 63) wsum[wave] = inc;
+    __syncthreads();
+    int base = 0;
+    for (int w = 0; w < wave; w++) base += wsum[w];
+    return base + inc - v;
+}
+
+// One workgroup per query of the chunk.  kk = min(k, cells whose score is not NaN) entries are real, the rest -1 / -inf.
+__global__ __launch_bounds__(SEL_T) void k_topk_select(const double* __restrict__ S, int64_t ld_s, int nc, int k,
+                                                       int64_t index_offset, int64_t* __restrict__ out_idx,
+                                                       double* __restrict__ out_score) {
+    __shared__ int hist[RBINS];
+    __shared__ double cand_s[KMAX];
+    __shared__ int cand_i[KMAX];
+    __shared__ int wsum[SEL_W];
+    __shared__ int seg_gt[SEL_W], seg_eq[SEL_W];
+    __shared__ int sh_nan, sh_bin, sh_above, sh_count;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const double* row = S + (int64_t)blockIdx.x * ld_s;
+    out_idx += (int64_t)blockIdx.x * k;
+    out_score += (int64_t)blockIdx.x * k;
+
+    // ---- radix descent: T = the kk-th largest key, n_gt = keys above it ----------------------------------------------------
+    uint64_t prefix = 0;   // the bits of T found so far (the top 64 - shift bits)
+    int shift = 64;
+    int need = 0, kk = 0;  // need: rank of T among the keys that share its prefix
+    bool take_all = false; // early stop: every key with this prefix is wanted, T = the smallest such key - 1
+    if (tid == 0) sh_nan = 0;
+    for (int pass = 0; shift > 0; pass++) {
+        const int width = shift >= RBITS ? RBITS : shift;
+        const int hi_shift = shift;   // keys taking part: key >> hi_shift == prefix (pass 0: all)
+        shift -= width;
+        for (int b = tid; b < RBINS; b += SEL_T) hist[b] = 0;
+        __syncthreads();
+        int n_nan = 0;
+        for (int c0 = 0; c0 < nc; c0 += SEL_T * SEL_U) {
+            double sv[SEL_U];
+#pragma unroll
+            for (int u = 0; u < SEL_U; u++) {
+                const int c = c0 + u * SEL_T + tid;
+                sv[u] = c < nc ? row[tile_pos(c)] : 0.0;
+            }
+#pragma unroll
+            for (int u = 0; u < SEL_U; u++) {
+                const int c = c0 + u * SEL_T + tid;
+                bool act = false;
+                int bin = 0;
+                if (c < nc) {
+                    const uint64_t key = score_key(sv[u]);
+                    if (pass == 0) { act = true; n_nan += key == 0; }
+                    else act = (key >> hi_shift) == prefix;
+                    bin = (int)((key >> shift) & (uint64_t)((1 << width) - 1));
+                }
+                // cosine scores share their leading bits: the first passes send most of a wave to a few bins.  Up to 4 of a wave's
+                // bins are counted with one atomic each; what is left (spread bins) goes one atomic per lane.
+                for (int it = 0; it < 4; it++) {
+                    const uint64_t m = __ballot(act);
+                    if (m == 0) break;
+                    const int leader = __ffsll((unsigned long long)m) - 1;
+                    const int b = __shfl(bin, leader, 64);
+                    const bool same = act && bin == b;
+                    const uint64_t ms = __ballot(same);
+                    if (lane == leader) atomicAdd(&hist[b], __popcll(ms));
+                    act = act && !same;
+                }
+                if (act) atomicAdd(&hist[bin], 1);
+            }
+        }
+        if (pass == 0 && n_nan) atomicAdd(&sh_nan, n_nan);
+        __syncthreads();
+        if (pass == 0) {
+            const int valid = nc - sh_nan;
+            kk = k < valid ? k : valid;
+            need = kk;
+            if (kk == 0) break;   // (uniform)
+        }
+        // thread t owns RBINS / SEL_T bins from RBINS - 1 - t * (RBINS / SEL_T) downwards: `above` = keys in the bins above its own
+        int own = 0;
+        int cnt[RBINS / SEL_T];
+#pragma unroll
+        for (int j = 0; j < RBINS / SEL_T; j++) { cnt[j] = hist[RBINS - 1 - (tid * (RBINS / SEL_T) + j)]; own += cnt[j]; }
+        int above = block_excl_scan(own, wsum);
+        if (above < need && need <= above + own) {   // exactly one thread: the bins' total is >= need
+#pragma unroll
+            for (int j = 0; j < RBINS / SEL_T; j++) {
+                if (above < need && need <= above + cnt[j]) {
+                    sh_bin = RBINS - 1 - (tid * (RBINS / SEL_T) + j);
+                    sh_above = above;
+                    sh_count = cnt[j];
+                }
+                above += cnt[j];
+            }
+        }
+        __syncthreads();
+        prefix = (prefix << width) | (uint64_t)sh_bin;
+        need -= sh_above;
+        const int in_bin = sh_count;
+        __syncthreads();   // (sh_* and hist are rewritten by the next pass)
+        if (shift > 0 && in_bin == need && prefix != 0) { take_all = true; break; }
+    }
+
+    if (kk > 0) {
+        // keys above T are taken, and of the keys equal to T the `n_eq` of lowest cell index
+        const uint64_t T = take_all ? (prefix << shift) - 1 : prefix;
+        const int n_eq = take_all ? 0 : need;
+        const int n_gt = kk - n_eq;
+        // ---- ascending-index sweep: wave w owns cells [w * seg, (w + 1) * seg), 64 at a time; counts first, then positions ----
+        // (the places come from ballots and running counts in index order, never from the order atomics arrive in)
+        const int seg = ((nc + SEL_W * 64 - 1) / (SEL_W * 64)) * 64;
+        const int c_lo = wave * seg, c_hi = (c_lo + seg) < nc ? (c_lo + seg) : nc;
+        int my_gt = 0, my_eq = 0;
+        for (int c0 = c_lo + lane; c0 < c_hi; c0 += 64 * SEL_U) {
+            double sv[SEL_U];
+#pragma unroll
+            for (int u = 0; u < SEL_U; u++) sv[u] = (c0 + 64 * u) < c_hi ? row[tile_pos(c0 + 64 * u)] : 0.0;
+#pragma unroll
+            for (int u = 0; u < SEL_U; u++) {
+                const uint64_t key = score_key(sv[u]);
+                my_gt += (c0 + 64 * u) < c_hi && key > T;
+                my_eq += (c0 + 64 * u) < c_hi && key == T;
+            }
+        }
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) { my_gt += __shfl_xor(my_gt, o, 64); my_eq += __shfl_xor(my_eq, o, 64); }
+        if (lane == 0) { seg_gt[wave] = my_gt; seg_eq[wave] = my_eq; }
+        __syncthreads();
+        int run_gt = 0, run_eq = 0;   // entries of each kind at lower cell indices than this wave's next 64
+        for (int w = 0; w < wave; w++) { run_gt += seg_gt[w]; run_eq += seg_eq[w]; }
+        const uint64_t below = (1ull << lane) - 1;
+        for (int cu = c_lo; cu < c_hi; cu += 64 * SEL_U) {
+            double sv[SEL_U];
+#pragma unroll
+            for (int u = 0; u < SEL_U; u++) sv[u] = (cu + 64 * u + lane) < c_hi ? row[tile_pos(cu + 64 * u + lane)] : 0.0;
+#pragma unroll
+            for (int u = 0; u < SEL_U; u++) {
+                const int c = cu + 64 * u + lane;
+                const double s = sv[u];
+                const uint64_t key = score_key(s);
+                const bool gt = c < c_hi && key > T, eq = c < c_hi && key == T;
+                const uint64_t m_gt = __ballot(gt), m_eq = __ballot(eq);
+                int slot = -1;
+                if (gt) slot = run_gt + __popcll(m_gt & below);
+                else if (eq) {
+                    const int e = run_eq + __popcll(m_eq & below);
+                    if (e < n_eq) slot = n_gt + e;
+                }
+                if (slot >= 0 && slot < KMAX) { cand_s[slot] = s; cand_i[slot] = c; }
+                run_gt += __popcll(m_gt);
+                run_eq += __popcll(m_eq);
+            }
+        }
+    }
+    // ---- bitonic sort of the candidates on better(), padded to a power of two with entries that sort last ------------------
+    int n2 = 1;
+    while (n2 < kk) n2 <<= 1;
+    for (int j = kk + tid; j < n2; j += SEL_T) { cand_s[j] = -INFINITY; cand_i[j] = 0x7fffffff; }
+    __syncthreads();
+    for (int size = 2; size <= n2; size <<= 1) {
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            for (int p = tid; p < (n2 >> 1); p += SEL_T) {
+                const int i = ((p & ~(stride - 1)) << 1) | (p & (stride - 1));   // lower element of the pair
+                const int j = i | stride;
+                const bool first_wins = (i & size) == 0;   // this run ends up best-first (the last stage: all of them)
+                const double si = cand_s[i], sj = cand_s[j];
+                const int ii = cand_i[i], ij = cand_i[j];
+                if (better(sj, ij, si, ii) == first_wins) {
+                    cand_s[i] = sj; cand_i[i] = ij;
+                    cand_s[j] = si; cand_i[j] = ii;
+                }
+            }
+            __syncthreads();
+        }
+    }
+    for (int j = tid; j < k; j += SEL_T) {
+        const bool ok = j < kk;
+        out_idx[j] = ok ? (int64_t)cand_i[j] + index_offset : -1;
+        out_score[j] = ok ? cand_s[j] : -INFINITY;
+    }
+}
+
 int pick_splits(int64_t nq, int64_t nc) {
-    const int64_t qblocks = (nq + QB - 1) / QB;
+    const int64_t qblocks = nq > 0 ? (nq + QB - 1) / QB : 1;   // (the size query of an empty call)
     int64_t want = (2LL * num_cus() + qblocks - 1) / qblocks;  // ~2 workgroups per CU in flight
     int64_t max_split = (nc + 4 * CB - 1) / (4 * CB);          // keep >= 128 cells per split
     if (want > max_split) want = max_split;
@@ -186,27 +446,71 @@ int pick_splits(int64_t nq, int64_t nc) {
     return (int)want;
 }
 
+// k > KREG: queries per chunk and the row stride of the score tile (include/t2p.h states the formula); chunk 0 = one
+// query's scores alone exceed the tile bound
+constexpr size_t kScoreTileBytes = (size_t)256 << 20;   // the Infinity Cache
+int64_t score_ld(int64_t nc) { return (nc + 15) / 16 * 16; }
+int64_t score_chunk(int64_t nq, int64_t nc) {
+    const size_t row = (size_t)score_ld(nc) * sizeof(double);
+    int64_t cap = row == 0 ? nq : (int64_t)((kScoreTileBytes - 256) / row);
+    if (cap >= QB) cap = cap / QB * QB;   // whole query blocks of the score kernel
+    return nq < cap ? nq : cap;
+}
+
+template <int DIM>
+void launch_scores(dim3 grid, hipStream_t st, const float* Q, const float* Cm, int64_t nq, int64_t nc, int cps, double* S,
+                   int64_t ld_s) {
+    hipLaunchKernelGGL(k_sim_scores<DIM>, grid, dim3(256), 0, st, Q, Cm, nq, nc, cps, S, ld_s);
+}
+
 }  // namespace
 
 size_t sim_topk_workspace_bytes(int64_t nq, int64_t nc, int k) {
-    (void)k;
+    if (k > KREG) return (size_t)score_chunk(nq, nc) * score_ld(nc) * sizeof(double) + 256;
     const int sp = pick_splits(nq, nc);
     return (size_t)nq * sp * 4 * KCAP * (sizeof(double) + sizeof(int)) + 256;
 }
 
 int launch_sim_topk(const float* Q, const float* Cm, int64_t nq, int64_t nc, int dim, int k, int64_t c_index_offset,
                     int64_t* out_idx, double* out_score, void* ws, size_t ws_bytes, hipStream_t st) {
-    T2P_CHECK_ARG(k >= 1 && k <= KCAP, "sim_topk: k=%d outside [1,%d]", k, KCAP);
+    T2P_CHECK_ARG(k >= 1 && k <= KMAX, "sim_topk: k=%d outside [1,%d]", k, KMAX);
     T2P_CHECK_ARG(dim == 256 || dim == 128 || dim == 384, "sim_topk: dim=%d not instantiated (128, 256, 384)", dim);
     T2P_CHECK_ARG(nc < 0x7fffffff, "sim_topk: nc too large");
     T2P_CHECK_ARG((((uintptr_t)Q) & 15) == 0 && (((uintptr_t)Cm) & 15) == 0, "sim_topk: Q and C must be 16-byte aligned");
+    T2P_CHECK_ARG(k <= KREG || score_chunk(1, nc) > 0,
+                  "sim_topk: k=%d > %d keeps one query's float64 scores (8 B x nc=%lld) in a workspace tile of at most %zu B: nc too large",
+                  k, KREG, (long long)nc, kScoreTileBytes);
     if (nq == 0) return 0;
-    const int sp = pick_splits(nq, nc);
     const size_t need = sim_topk_workspace_bytes(nq, nc, k);
     if (ws_bytes < need || ws == nullptr) {
         set_error("sim_topk: workspace %zu B < required %zu B", ws_bytes, need);
         return T2P_E_WORKSPACE;
     }
+    if (k > KREG) {
+        T2P_CHECK_ARG((((uintptr_t)ws) & 15) == 0, "sim_topk: workspace must be 16-byte aligned");
+        const int64_t chunk = score_chunk(nq, nc), ld_s = score_ld(nc);
+        double* S = (double*)ws;
+        for (int64_t qa = 0; qa < nq; qa += chunk) {   // chunks run back to back on `st`: the tile is reused in stream order
+            const int64_t n = (nq - qa) < chunk ? (nq - qa) : chunk;
+            if (nc > 0) {
+                const int sp = pick_splits(n, nc);
+                int cps = (int)((nc + sp - 1) / sp);
+                cps = ((cps + CB - 1) / CB) * CB;
+                const dim3 grid((unsigned)((n + QB - 1) / QB), (unsigned)sp);
+                ProfScope ps_("sim_scores", st);
+                if (dim == 256) launch_scores<256>(grid, st, Q + qa * dim, Cm, n, nc, cps, S, ld_s);
+                else if (dim == 384) launch_scores<384>(grid, st, Q + qa * dim, Cm, n, nc, cps, S, ld_s);
+                else launch_scores<128>(grid, st, Q + qa * dim, Cm, n, nc, cps, S, ld_s);
+            }
+            T2P_CHECK_LAUNCH("sim_scores");
+            ProfScope ps2_("topk_select", st);
+            hipLaunchKernelGGL(k_topk_select, dim3((unsigned)n), dim3(SEL_T), 0, st, (const double*)S, ld_s, (int)nc, k,
+                               c_index_offset, out_idx + qa * k, out_score + qa * k);
+            T2P_CHECK_LAUNCH("topk_select");
+        }
+        return 0;
+    }
+    const int sp = pick_splits(nq, nc);
     const int64_t n_lists = nq * sp * 4 * KCAP;
     double* ps = (double*)ws;
     int* pi = (int*)(ps + n_lists);

@@ -122,8 +122,9 @@ def run_fine(model, poses, cells_dict: Dict[str, object], retrievals: List[Seque
     `model(objects, hints, object_points)` is SuperGlueMatch (or anything returning .matches0 [B, pad] / .offsets
     [B, hints, 2]); unlike the reference, which calls the model once per query (10 samples), `queries_per_call` queries
     share a call - the memory knob of this function: one call packs queries_per_call x max(top_k) x pad_size objects.  None = 64
-    on the host chain, 256 on the on-device path (256 queries x 10 candidates x 16 objects fill the GPU); a given value is honoured
-    on both.  Returns (accuracies_mean, accuracies_offset, accuracies_mean_conf).
+    on the host chain, 256 on the on-device path (256 queries x 10 candidates x 16 objects fill the GPU), and above max(top_k) = 16
+    as many queries as keep a call at the sample count of max(top_k) = 16 (1,024 / 4,096 samples; max(top_k) goes up to 1,024 and
+    a call's memory grows with queries x max(top_k)); a given value is honoured on both.  Returns (accuracies_mean, accuracies_offset, accuracies_mean_conf).
     With an initialised torch.distributed process group the queries are split over the ranks in contiguous blocks
     (samples are independent) and the per-query estimates are all-gathered: every rank returns the same tables.
     scene_dev (scene.DeviceScene holding every cell of `retrievals` and >= pad_size padding objects) + a counter-based
@@ -154,8 +155,8 @@ def run_fine(model, poses, cells_dict: Dict[str, object], retrievals: List[Seque
     # the on-device path needs everything it calls on the model: a model that only has forward_packed takes the host chain
     on_dev = (scene_dev is not None and hasattr(transform, "keys")
               and all(hasattr(model, a) for a in ("forward_packed", "encode_hints", "args", "object_encoder")))
-    if queries_per_call is None:
-        queries_per_call = 256 if on_dev else 64
+    if queries_per_call is None:   # 4,096 / 1,024 samples per call at most: 256 / 64 queries up to max(top_k) = 16, fewer above
+        queries_per_call = min(256, 4096 // kmax) if on_dev else min(64, 1024 // kmax)
     queries_per_call = max(1, int(queries_per_call))
     if on_dev:
         ids_of_cell = scene_dev.padded_object_ids(pad_size)                                  # [n_cells, pad]

@@ -84,6 +84,8 @@ def run_coarse(model, scenes: IO.Scenes, transform, top_k: Sequence[int], thresh
     import time
     import warnings
     from . import distributed as TD
+    from .retrieval import check_top_k
+    kmax = check_top_k(top_k)   # ValueError before anything is encoded or uploaded
     cells, poses = scenes.all_cells, scenes.all_poses
     texts = scenes.texts
     can = (scene_dev is not None or on_device_input(model, transform)) and hasattr(model, "encode_scene_cells")
@@ -125,7 +127,6 @@ def run_coarse(model, scenes: IO.Scenes, transform, top_k: Sequence[int], thresh
         enc = [model.encode_text(texts[a: min(a + texts_per_call, hi)]) for a in range(lo, hi, texts_per_call)]
         return torch.cat(enc) if enc else torch.zeros((0, model.embed_dim), device=model.device)
 
-    kmax = int(max(top_k))
     rank_fn = topk_fn if topk_fn is not None else (lambda q, c, k: retrieve_topk(c, q, k))
     idx, _ = TD.sharded_retrieval(encode_cells, encode_queries, rank_fn, len(cells), len(texts), kmax, group)
     idx = np.asarray(idx.cpu()) if hasattr(idx, "cpu") else np.asarray(idx)
@@ -156,6 +157,8 @@ def evaluate(model_coarse, model_fine, scenes: IO.Scenes, transform, top_k=(1, 5
     timings: optional dict that receives wall times (`scene_s` upload, `coarse_s`, `fine_s`)."""
     import time
     import warnings
+    from .retrieval import check_top_k
+    check_top_k(top_k)   # ValueError before the scene is uploaded
     scene_dev = None
     t0 = time.perf_counter()
     coarse_can = on_device_input(model_coarse, transform) and hasattr(model_coarse, "encode_scene_cells")
@@ -232,6 +235,8 @@ def main(argv: Optional[List[str]] = None):
     ap.add_argument("--use_features", nargs="+", default=["class", "color", "position"])
     ap.add_argument("--seed", type=int, default=0, help="seed of the T.FixedPoints draw")
     a = ap.parse_args(argv)
+    from .retrieval import check_top_k
+    check_top_k(a.top_k)   # ValueError before the dataset and the checkpoints are read
     # one process per GPU under torch.distributed.run (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from its environment)
     import os
     world, rank, local_rank = (int(os.environ.get(k, d)) for k, d in (("WORLD_SIZE", "1"), ("RANK", "0"), ("LOCAL_RANK", "0")))

@@ -2,12 +2,23 @@
 
 `retrieve_topk(cell_encodings, text_encodings, k)` returns what the reference computes per query as
 `np.argsort(-1.0 * (cell_encodings @ text_encodings[q]))[0:k]` -- for all queries at once, ranked in float64 on the
-GPU (csrc/sim_topk.hip), ties resolved to the lower cell index.
+GPU (csrc/sim_topk.hip), ties resolved to the lower cell index.  Any k from 1 to MAX_TOP_K: up to 16 the kernel keeps
+per-lane lists in registers, above it selects exactly from a float64 score tile (same score bits, same order).
 """
 import numpy as np
 import torch
 
 from . import ops
+
+MAX_TOP_K = 1024   # include/t2p.h: the largest k t2p_sim_topk accepts
+
+
+def check_top_k(top_k) -> int:
+    """max(top_k) of an evaluation's --top_k list, or a ValueError naming the limit: callers check BEFORE they encode."""
+    ks = [int(k) for k in np.atleast_1d(np.asarray(top_k)).tolist()]
+    if not ks or min(ks) < 1 or max(ks) > MAX_TOP_K:
+        raise ValueError(f"top_k={list(ks)}: every k must lie in [1, {MAX_TOP_K}] (the retrieval kernel's limit, include/t2p.h)")
+    return max(ks)
 
 
 def _as_device_f32(x, device):

@@ -468,7 +468,10 @@ int t2p_lstm_cell_backward(const float* dh_gemm, const float* dh_carry_in, const
  * and the layer's beta [C], not y: the ReLU mask (y > 0) is recomputed from x exactly as the forward formed y.
  * Segment max (PointConv aggr="max", gnn.global_max_pool, DynamicEdgeConv aggr="max" over rows sorted by destination):
  * out [n_seg][C], arg [n_seg][C] = winning row (first one on ties, -1 and out = 0 for an empty segment); the backward
- * routes dout to the winning rows. */
+ * routes dout to the winning rows.
+ * Non-finite input, forward: both follow torch.  The ReLU keeps NaN (a NaN or inf among a segment's rows makes that segment's
+ * column of y NaN - its statistics are NaN -, not 0); segment max: a NaN wins over every number (arg = the first NaN row), a column
+ * that is all -inf gives -inf with arg = the segment's first row.  The backward passes on non-finite input are unspecified. */
 size_t t2p_bn_train_workspace_bytes(int64_t rows, int32_t n_seg, int32_t channels);
 int t2p_bn_relu_train_forward(const float* x, const int32_t* seg_ptr, int32_t n_seg, int64_t rows, int32_t channels,
                               const float* gamma, const float* beta, float eps, int32_t relu, float* y, float* mean,

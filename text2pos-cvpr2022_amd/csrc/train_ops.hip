@@ -31,6 +31,11 @@ __device__ __forceinline__ float bn_out(float x, float mean, float invstd, float
     return (x - mean) * invstd * gamma + beta;
 }
 
+// ReLU of the forward.  `v <= 0 ? 0 : v`, not fmaxf(v, 0): fmaxf returns its other operand for a NaN, so a column whose statistics
+// are NaN (one NaN or inf among the segment's rows) came out as zeros and training went on silently; torch.relu keeps the NaN.
+// Finite values, -0 included (-> +0), get fmaxf's bits.
+__device__ __forceinline__ float relu_keep_nan(float v) { return v <= 0.f ? 0.f : v; }
+
 // dz = dy where the ReLU let the activation through (or everywhere without a ReLU), else 0 - as a bit mask.  Written as the
 // select `(!relu || bn_out(...) > 0.f) ? dy : 0.f`, hipcc (ROCm 7.2, -O3) compiled k_bn_bwd_apply4 to `v_mov dz, 0` for ALL lanes
 // followed by an EMPTY `s_and_saveexec` region where the move back belonged: dx came out as if no row had passed the ReLU
@@ -110,7 +115,7 @@ __global__ __launch_bounds__(256) void k_bn_apply(const float* __restrict__ x, c
     const float m = mean[(int64_t)s * C + c], is = invstd[(int64_t)s * C + c], g = gamma[c], b = beta[c];
     for (int r = lo + rl; r < hi; r += kRowsPar) {
         const float v = bn_out(x[(int64_t)r * C + c], m, is, g, b);
-        y[(int64_t)r * C + c] = relu ? fmaxf(v, 0.f) : v;
+        y[(int64_t)r * C + c] = relu ? relu_keep_nan(v) : v;
     }
 }
 
@@ -283,7 +288,7 @@ __global__ __launch_bounds__(256) void k_bn_apply4(const float* __restrict__ x, 
 #pragma unroll
         for (int e = 0; e < 4; e++) {
             const float t = bn_out(v[e], m[e], is[e], g[e], b[e]);
-            o[e] = relu ? fmaxf(t, 0.f) : t;
+            o[e] = relu ? relu_keep_nan(t) : t;
         }
         return o;
     };
@@ -390,7 +395,13 @@ __global__ __launch_bounds__(256) void k_bn_bwd_apply4(const float* __restrict__
     }
 }
 
-// out[s][c] = max over the rows of segment s (first row wins ties), arg[s][c] = that row (-1: empty segment, out = 0)
+// out[s][c] = max over the rows of segment s (first row wins ties), arg[s][c] = that row (-1: empty segment, out = 0).  As
+// torch.max / scatter 'amax': a NaN wins over every number (the first NaN row is reported), a column of -inf gives -inf and its
+// first row - so `best` starts from the lane's first row, not from -inf with no row.
+__device__ __forceinline__ bool max_takes(float v, int r, float best, int who) {   // (v, r) replaces (best, who); r != who
+    if (best != best) return v != v && r < who;
+    return v != v || v > best || (v == best && r < who);
+}
 __global__ __launch_bounds__(256) void k_segment_max(const float* __restrict__ x, const int32_t* __restrict__ seg_ptr, int C,
                                                      float* __restrict__ out, int32_t* __restrict__ arg) {
     __shared__ float bv[kRowsPar][kCols];
@@ -398,18 +409,25 @@ __global__ __launch_bounds__(256) void k_segment_max(const float* __restrict__ x
     const int s = blockIdx.x, cl = threadIdx.x % kCols, rl = threadIdx.x / kCols;
     const int c = blockIdx.y * kCols + cl;
     const bool ok = c < C;
-    float best = -INFINITY;
+    const int r1 = seg_ptr[s + 1];
+    float best = 0.f;
     int who = -1;
-    for (int r = seg_ptr[s] + rl; r < seg_ptr[s + 1]; r += kRowsPar) {
+    int r = seg_ptr[s] + rl;
+    if (r < r1) {
+        best = ok ? x[(int64_t)r * C + c] : 0.f;
+        who = r;
+        r += kRowsPar;
+    }
+    for (; r < r1; r += kRowsPar) {
         const float v = ok ? x[(int64_t)r * C + c] : 0.f;
-        if (v > best) { best = v; who = r; }
+        if (v > best || (v != v && best == best)) { best = v; who = r; }   // rows ascend: an equal value or a later NaN stays out
     }
     bv[rl][cl] = best;
     bi[rl][cl] = who;
     __syncthreads();
     if (ok && rl == 0) {
         for (int k = 1; k < kRowsPar; k++)
-            if (bi[k][cl] >= 0 && (who < 0 || bv[k][cl] > best || (bv[k][cl] == best && bi[k][cl] < who))) {
+            if (bi[k][cl] >= 0 && (who < 0 || max_takes(bv[k][cl], bi[k][cl], best, who))) {
                 best = bv[k][cl];
                 who = bi[k][cl];
             }

@@ -36,7 +36,7 @@ extern "C" {
                                            one chunk: ~0.6 MB per object, i.e. ~38 GB at the default chunk for a batch that
                                            fills it (t2p_encode_cells_workspace_bytes gives the exact figure; a second
                                            stream's call needs its own workspace) */
-#define T2P_TUNING_MASK 0x5              /* t2p_cell_config.tuning: the bits that select a built plan */
+#define T2P_TUNING_MASK 0xD              /* t2p_cell_config.tuning: the bits that select a built plan */
 #define T2P_E_ARG (-1)
 #define T2P_E_WORKSPACE (-2)
 #define T2P_E_UNSUPPORTED (-3)
@@ -190,6 +190,9 @@ typedef struct t2p_cell_config {
      *   bit 2: keep the edge rows of repeated centroids in the row list of SA level 2 (default: the centroids FPS
      *          repeats once an object's distinct positions are used up share one copy of their rows, see
      *          t2p_group_rows_shared; every output bit is the same either way)
+     *   bit 3: SA level 1's rows listed by the scan kernel and pruned in place by t2p_dedup_rows, as before (default, at 256
+     *          points per object and with bit 0 clear: the scan publishes each centroid's hit mask and one builder kernel
+     *          writes the pruned list once, see t2p_group_rows_built; the list is the same bit for bit)
      * Bits outside T2P_TUNING_MASK are refused (T2P_E_ARG).  (Rounds 1-3 kept alternative SA kernels behind further bits; the
      * measured record is docs/notebook.md, the code is in the git history.) */
     int32_t tuning;
@@ -556,6 +559,15 @@ int t2p_group_rows(const float* xyz, int64_t n_obj, int32_t n_pts, const float* 
 int t2p_group_rows_shared(const float* xyz, int64_t n_obj, int32_t n_pts, const float* radius_host /*[3]*/, int32_t self_loops,
                           int32_t share_mask, uint8_t* const* fps_idx /*[3]*/, uint16_t* const* rows /*[3]*/,
                           uint16_t* const* n_rows /*[3]*/, t2p_stream_t stream);
+/* t2p_group_rows_shared followed by t2p_dedup_rows on level 1's list, as t2p_encode_cells runs them by default: the same
+ * fps_idx, lists, counts and terminators, bit for bit.  The scan kernel lists levels 2 and 3 as usual; of level 1 it writes only
+ * each centroid's 256-bit hit mask (into rows[0], which is workspace until the call returns its list there) and stops at the
+ * first tail centroid; a builder kernel then applies the 32-neighbour cap in point order, drops the rows of repeated points
+ * (the repeat test of t2p_dedup_rows: rgb is compared too) and writes the list once.  n_pts must be 256; xyz, rgb and rows[0]
+ * 16-byte aligned. */
+int t2p_group_rows_built(const float* xyz, const float* rgb, int64_t n_obj, int32_t n_pts, const float* radius_host /*[3]*/,
+                         int32_t self_loops, int32_t share_mask, uint8_t* const* fps_idx /*[3]*/, uint16_t* const* rows /*[3]*/,
+                         uint16_t* const* n_rows /*[3]*/, t2p_stream_t stream);
 int t2p_edge_counts(const uint16_t* rows, const uint16_t* n_rows, const int32_t* first_obj, int64_t n_obj, int32_t n_dense,
                     int32_t n_cent, int32_t self_loops, int32_t* counts, t2p_stream_t stream);
 int t2p_edge_expand(const uint16_t* rows, const uint16_t* n_rows, const int32_t* first_obj, const int32_t* cent_ptr, int64_t n_obj,

@@ -25,7 +25,9 @@ sys.path.insert(0, ROOT)
 
 KERNELS = [  # (profile scope, kernel, what)
     ("sample_group", "k_sample_group<true>", "FPS + ball query, 3 levels"),
-    ("dedup_rows", "k_dedup_rows", "SA1 repeated-point rows dropped"),
+    ("dedup_rows", "k_dedup_rows", "SA1 repeated-point rows dropped (tuning bit 3)"),
+    # (k_build_rows consumes the masks it overwrites, so the library never repeats it: its window is the plain step's)
+    ("build_rows", "k_build_rows", "SA1 row list from the scan's hit masks (not repeated in place)"),
     ("ws_edge_sa_k32_n64", "k_sa_points<12>", "SA1 both layers + max"),
     ("ws_dense_k80_n128", "k_ws<80,128,...> DENSE_STORE", "SA2 layer-1 point table"),
     ("ws_edge_sa_k128_n128", "k_sa_rows<128,128,64,4>", "SA2 layer 2 + max"),

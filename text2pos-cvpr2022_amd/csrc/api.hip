@@ -328,9 +328,15 @@ int encode_chunk(const float* xyz, const float* rgb, const float* center, const 
         // (GroupTables::share_tail; same bits, -13 % rows on the synthetic cells) where k_sa_rows consumes them
         for (int l = 0; l < 3; l++) gt.share_tail[l] = sa_shares_tail_rows(l, Geo::H[l], Geo::C[l], bp[l], cfg.n_pts, cfg.tuning) ? 1 : 0;
 
+        // level 0: edges of repeated points leave the row list (same max-aggregate, -36 % SA1 rows on the synthetic cells).
+        // Default: the scan publishes level 0's hit masks and k_build_rows writes the pruned list once; tuning bit 3: the scan
+        // lists every hit and k_dedup_rows prunes the list in place, as before (the same list, bit for bit)
+        const bool prune_l0 = !(cfg.tuning & 1) && cfg.n_pts == 256;
+        gt.mask_l0 = prune_l0 && !(cfg.tuning & 8) && !want_nbr && gt.rows[0] && gt.rows[1] && gt.rows[2] ? 1 : 0;
         T2P_TRY(launch_sample_group(xyz, n, cfg.n_pts, cfg.radius, gt, st));
-        // level 0: edges of repeated points leave the row list (same max-aggregate, -36 % SA1 rows on the synthetic cells)
-        if (!(cfg.tuning & 1) && cfg.n_pts == 256)
+        if (gt.mask_l0)
+            T2P_TRY(launch_build_rows(xyz, rgb, gt.fps_idx[0], n, cfg.n_pts, gt.rows[0], gt.n_rows[0], gt.self_loops, st));
+        else if (prune_l0)
             T2P_TRY(launch_dedup_rows(xyz, rgb, n, cfg.n_pts, gt.rows[0], gt.n_rows[0], g.nc[0], st));
         // the per-centroid row counts of all three levels exist now: cut every level's balanced object ranges at once
         T2P_TRY(launch_sa_balance_levels(bp, Geo::H, Geo::C, st));
@@ -1082,6 +1088,31 @@ int t2p_group_rows_shared(const float* xyz, int64_t n_obj, int32_t n_pts, const 
         gt.share_tail[l] = (share_mask >> l) & 1;
     }
     return launch_sample_group(xyz, n_obj, n_pts, radius_host, gt, (hipStream_t)stream);
+}
+
+int t2p_group_rows_built(const float* xyz, const float* rgb, int64_t n_obj, int32_t n_pts, const float* radius_host,
+                         int32_t self_loops, int32_t share_mask, uint8_t* const* fps_idx, uint16_t* const* rows,
+                         uint16_t* const* n_rows, t2p_stream_t stream) {
+    T2P_CHECK_ARG(xyz && rgb && radius_host && fps_idx && rows && n_rows, "group_rows_built: NULL argument");
+    T2P_CHECK_ARG(n_obj >= 0, "group_rows_built: negative size");
+    T2P_CHECK_ARG((share_mask & ~2) == 0, "group_rows_built: share_mask=%#x (bit 1: SA level 2; no other level has a shared form)", share_mask);
+    T2P_CHECK_ARG(n_pts == 256, "group_rows_built: built for 256 points per object (n_pts = %d)", n_pts);
+    Geo g(n_pts);
+    GroupTables gt{};
+    gt.self_loops = self_loops ? 1 : 0;
+    for (int l = 0; l < 3; l++) {
+        T2P_CHECK_ARG(fps_idx[l] && rows[l] && n_rows[l], "group_rows_built: NULL table of level %d", l);
+        gt.fps_idx[l] = fps_idx[l];
+        gt.rows[l] = rows[l];
+        gt.n_rows[l] = n_rows[l];
+        gt.n_dense[l] = g.nd[l];
+        gt.n_cent[l] = g.nc[l];
+        gt.share_tail[l] = (share_mask >> l) & 1;
+    }
+    gt.mask_l0 = 1;
+    T2P_CHECK_ARG((((uintptr_t)xyz | (uintptr_t)rgb | (uintptr_t)rows[0]) & 15) == 0, "group_rows_built: xyz, rgb and rows[0] must be 16-byte aligned");
+    T2P_TRY(launch_sample_group(xyz, n_obj, n_pts, radius_host, gt, (hipStream_t)stream));
+    return launch_build_rows(xyz, rgb, gt.fps_idx[0], n_obj, n_pts, gt.rows[0], gt.n_rows[0], gt.self_loops, (hipStream_t)stream);
 }
 
 int t2p_edge_counts(const uint16_t* rows, const uint16_t* n_rows, const int32_t* first_obj, int64_t n_obj, int32_t n_dense,

@@ -176,27 +176,47 @@ __device__ void level(const float* px, const float* py, const float* pz, int n_d
 // every later centroid is point 0 too.  These TAIL centroids stand at centroid 0's position: same hits, same edge rows.  The
 // first of them lists its hits once under the pseudo-centroid code `tail_code`; each tail centroid adds only its self-loop row,
 // and the later ones skip the distance pass altogether.  fps_idx and the centroid positions come out as without SHARE.
-template <int PPL, bool SHARE = false>
+// MASK (GroupTables::mask_l0, SA level 1): the level publishes WHICH points each centroid hit and leaves the list to k_build_rows.
+// Lane l owns the STRIDED points l, l + 64, ..: the ballot of the range test of register j is then word j of the centroid's
+// point-ordered hit mask, and "ties -> lowest index" is the lowest j whose tie ballot is non-zero, then its lowest bit - all on
+// the scalar unit.  No hit ranks, no row stores: the four ballots go to `rows_out` as [centroid][PPL x u64] (lane 0, two
+// 16-byte stores).  The scan stops at the first tail centroid: the later ones are point 0 (argument above) and k_build_rows
+// gives them centroid 0's mask, so their slots are not written.  Same dist2 bits, same fps_idx, same centroid positions.
+template <int PPL, bool SHARE = false, bool MASK = false>
 __device__ void level_fast(const float* px, const float* py, const float* pz, int n_c, float r2, uint8_t* sel, float* qx,
                            float* qy, float* qz, uint16_t* __restrict__ rows_out, int self_loops, int* n_rows_out,
                            int tail_code = 0) {
+    static_assert(!(MASK && SHARE) && (!MASK || PPL == 4), "mask mode: level 0 of the 256-point path");
     const int lane = threadIdx.x;
-    const int i0 = lane * PPL;
+    const int i0 = MASK ? lane : lane * PPL;
+    constexpr int ST = MASK ? 64 : 1;   // index step between a lane's points
     float x[PPL], y[PPL], z[PPL];
     uint32_t mind[PPL];   // running minimum of the squared distances, as bit patterns (non-negative floats order like integers)
 #pragma unroll
     for (int j = 0; j < PPL; j++) {
-        x[j] = px[i0 + j];
-        y[j] = py[i0 + j];
-        z[j] = pz[i0 + j];
+        x[j] = px[i0 + j * ST];
+        y[j] = py[i0 + j * ST];
+        z[j] = pz[i0 + j * ST];
         mind[j] = 0x7f800000u;   // +inf
     }
     int cur = 0;
     int base = 0;
     [[maybe_unused]] bool tail_open = false;   // SHARE: the tail's hits are in the list
     for (int c = 0; c < n_c; c++) {
+        if constexpr (MASK) {
+            if (c > 0 && cur == 0) {   // (uniform) tail stop: every later centroid is point 0
+                const float x0 = px[0], y0 = py[0], z0 = pz[0];
+                for (int t = c + lane; t < n_c; t += 64) {
+                    sel[t] = 0;
+                    qx[t] = x0;
+                    qy[t] = y0;
+                    qz[t] = z0;
+                }
+                break;
+            }
+        }
         const float cx = px[cur], cy = py[cur], cz = pz[cur];
-        if (lane == 0) {
+        if (!MASK && lane == 0) {
             sel[c] = (uint8_t)cur;
             qx[c] = cx;
             qy[c] = cy;
@@ -243,6 +263,17 @@ __device__ void level_fast(const float* px, const float* py, const float* pz, in
                 m[j] = __ballot(d[j] < r2);
             }
         }
+        if constexpr (MASK) {
+            if (lane == 0) {   // the centroid and its hit mask, in one lane-0 block
+                sel[c] = (uint8_t)cur;
+                qx[c] = cx;
+                qy[c] = cy;
+                qz[c] = cz;
+                uint4* const mp = (uint4*)((char*)rows_out + 32u * (uint32_t)c);
+                mp[0] = uint4{(uint32_t)m[0], (uint32_t)(m[0] >> 32), (uint32_t)m[1], (uint32_t)(m[1] >> 32)};
+                mp[1] = uint4{(uint32_t)m[2], (uint32_t)(m[2] >> 32), (uint32_t)m[3], (uint32_t)(m[3] >> 32)};
+            }
+        } else {
         int lower = 0, count = 0;
 #pragma unroll
         for (int j = 0; j < PPL; j++) {
@@ -273,20 +304,37 @@ __device__ void level_fast(const float* px, const float* py, const float* pz, in
         const int kept = count < kMaxNbr ? count : kMaxNbr;
         if (self_loops && lane == 0) rows_out[(uint32_t)(base + kept)] = (uint16_t)(((c | 0x80) << 8) | c);
         base += kept + (self_loops ? 1 : 0);
+        }
         if (c + 1 < n_c) {  // uniform
             // (squared distances: non-negative, so the arg-max runs on bit patterns - see wave_max_u)
             uint32_t bd = mind[0];
 #pragma unroll
             for (int j = 1; j < PPL; j++) bd = max(bd, mind[j]);
             const uint32_t mx = wave_max_u(bd);
-            const unsigned long long tie = __ballot(bd == mx);
-            int jb = PPL - 1;
+            if constexpr (MASK) {   // index = 64 j + lane: lowest j with a tie, then its lowest lane
+                unsigned long long tie = __ballot(mind[PPL - 1] == mx);
+                int jb = PPL - 1;
 #pragma unroll
-            for (int j = PPL - 2; j >= 0; j--) jb = mind[j] == mx ? j : jb;
-            cur = __builtin_amdgcn_readlane(i0 + jb, (int)__builtin_ctzll(tie));
+                for (int j = PPL - 2; j >= 0; j--) {
+                    const unsigned long long tj = __ballot(mind[j] == mx);
+                    if (tj != 0) {
+                        tie = tj;
+                        jb = j;
+                    }
+                }
+                cur = 64 * jb + (int)__builtin_ctzll(tie);
+            } else {
+                const unsigned long long tie = __ballot(bd == mx);
+                int jb = PPL - 1;
+#pragma unroll
+                for (int j = PPL - 2; j >= 0; j--) jb = mind[j] == mx ? j : jb;
+                cur = __builtin_amdgcn_readlane(i0 + jb, (int)__builtin_ctzll(tie));
+            }
         }
     }
-    if (lane < 4 && base + lane < n_c * (kMaxNbr + 1)) rows_out[base + lane] = 0xFFFF;
+    if constexpr (!MASK) {
+        if (lane < 4 && base + lane < n_c * (kMaxNbr + 1)) rows_out[base + lane] = 0xFFFF;
+    }
     *n_rows_out = base;
     __syncthreads();
 }
@@ -360,7 +408,8 @@ __device__ __attribute__((noinline)) void emit_point_table(const float* px, cons
 #ifndef T2P_SG_WAVES
 #define T2P_SG_WAVES 6
 #endif
-template <bool FAST>
+// MASK: level 0 in mask mode (level_fast; the list is then written by k_build_rows)
+template <bool FAST, bool MASK = false>
 __global__ __launch_bounds__(64, T2P_SG_WAVES) void k_sample_group(const float* __restrict__ xyz, int64_t n_obj, int n_pts,
                                                      float r0, float r1, float r2, GroupTables gt) {
     // dynamic LDS: coordinates of the 4 levels | FPS selection | (only when the neighbour table is wanted: nbr + cnt);
@@ -424,7 +473,10 @@ __global__ __launch_bounds__(64, T2P_SG_WAVES) void k_sample_group(const float* 
             // wave and capped the occupancy at 11 waves per CU, and this kernel is latency-bound (half the waves: +64 % time)
             uint16_t* g_rows16 = gt.rows[l] ? gt.rows[l] + o * (int64_t)(n_c * (kMaxNbr + 1)) : nullptr;
             if constexpr (FAST) {
-                if (l == 0)
+                if (l == 0 && MASK)
+                    level_fast<4, false, MASK>(pin[l][0], pin[l][1], pin[l][2], n_c, rr[l], sel_lds, pin[l + 1][0], pin[l + 1][1],
+                                               pin[l + 1][2], g_rows16, gt.self_loops, &n_rows);
+                else if (l == 0)
                     level_fast<4>(pin[l][0], pin[l][1], pin[l][2], n_c, rr[l], sel_lds, pin[l + 1][0], pin[l + 1][1],
                                   pin[l + 1][2], g_rows16, gt.self_loops, &n_rows);
                 else if (l == 1 && gt.share_tail[1])
@@ -445,7 +497,7 @@ __global__ __launch_bounds__(64, T2P_SG_WAVES) void k_sample_group(const float* 
             else
                 level<1>(pin[l][0], pin[l][1], pin[l][2], n_d, n_c, rr[l], sel_lds, pin[l + 1][0], pin[l + 1][1],
                          pin[l + 1][2], nbr_lds, cnt_lds, g_rows16, gt.self_loops, &n_rows);
-            if (g_rows16 != nullptr && lane == 0) gt.n_rows[l][o] = (uint16_t)n_rows;
+            if (g_rows16 != nullptr && lane == 0 && !(MASK && l == 0)) gt.n_rows[l][o] = (uint16_t)n_rows;
             if (gt.B[l] != nullptr || gt.tail[l] != nullptr) {
                 const float* wpl = gt.wp[l];
                 asm volatile("" : "+s"(wpl));
@@ -479,6 +531,45 @@ __global__ __launch_bounds__(64, T2P_SG_WAVES) void k_sample_group(const float* 
 // slot holds a lower index with identical coordinates and colour is a repeat (a slot taken by a different point of the
 // same hash only leaves a repeat undetected: its rows stay, which is always valid).  The list is compacted in place
 // (writes never pass the read position), re-terminated and its length updated.
+// The repeat flags of one object's points (one wavefront): rep[i] = 1 when point i repeats an earlier point of the same hash slot
+// bit for bit.  slot [1024], pxyz / prgb [256 * 3] and rep [256] are LDS; returns behind a barrier, with rep complete and the
+// other three arrays free for reuse.  k_dedup_rows and k_build_rows share it: both must miss the same repeats.
+__device__ __forceinline__ void repeat_flags(const float* __restrict__ xyz, const float* __restrict__ rgb, int64_t o, uint32_t* slot,
+                                             float* pxyz, float* prgb, uint8_t* rep) {
+    const int lane = threadIdx.x;
+    const f32x4* sx = (const f32x4*)(xyz + o * kMaxPts * 3);
+    const f32x4* sc = (const f32x4*)(rgb + o * kMaxPts * 3);
+    for (int i = lane; i < kMaxPts * 3 / 4; i += 64) {   // straight 16-byte copies: point j at [3 j .. 3 j + 2]
+        ((f32x4*)pxyz)[i] = sx[i];
+        ((f32x4*)prgb)[i] = sc[i];
+    }
+    for (int i = lane; i < 1024; i += 64) slot[i] = 0xFFFFFFFFu;
+    __syncthreads();
+    uint32_t h[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const int i = lane * 4 + j;
+        uint32_t k = __float_as_uint(pxyz[i * 3]) * 0x9E3779B1u;
+        k = (k ^ (k >> 15)) + __float_as_uint(pxyz[i * 3 + 1]) * 0x85EBCA77u;
+        k = (k ^ (k >> 13)) + __float_as_uint(pxyz[i * 3 + 2]) * 0xC2B2AE3Du;
+        h[j] = (k ^ (k >> 16)) & 1023u;
+        atomicMin(&slot[h[j]], (uint32_t)i);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const int i = lane * 4 + j;
+        const int f = (int)slot[h[j]];   // f <= i: the slot keeps the lowest index of its hash
+        bool r = f != i;
+#pragma unroll
+        for (int e = 0; e < 3; e++)
+            r = r && __float_as_uint(pxyz[f * 3 + e]) == __float_as_uint(pxyz[i * 3 + e]) &&
+                __float_as_uint(prgb[f * 3 + e]) == __float_as_uint(prgb[i * 3 + e]);
+        rep[i] = r ? 1 : 0;
+    }
+    __syncthreads();
+}
+
 __global__ __launch_bounds__(64) void k_dedup_rows(const float* __restrict__ xyz, const float* __restrict__ rgb, int64_t n_obj,
                                                    uint16_t* rows, uint16_t* n_rows, int max_rows) {
     __shared__ uint32_t slot[1024];
@@ -487,37 +578,7 @@ __global__ __launch_bounds__(64) void k_dedup_rows(const float* __restrict__ xyz
     __shared__ uint8_t rep[kMaxPts];
     const int lane = threadIdx.x;
     for (int64_t o = blockIdx.x; o < n_obj; o += gridDim.x) {
-        const f32x4* sx = (const f32x4*)(xyz + o * kMaxPts * 3);
-        const f32x4* sc = (const f32x4*)(rgb + o * kMaxPts * 3);
-        for (int i = lane; i < kMaxPts * 3 / 4; i += 64) {   // straight 16-byte copies: point j at [3 j .. 3 j + 2]
-            ((f32x4*)pxyz)[i] = sx[i];
-            ((f32x4*)prgb)[i] = sc[i];
-        }
-        for (int i = lane; i < 1024; i += 64) slot[i] = 0xFFFFFFFFu;
-        __syncthreads();
-        uint32_t h[4];
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const int i = lane * 4 + j;
-            uint32_t k = __float_as_uint(pxyz[i * 3]) * 0x9E3779B1u;
-            k = (k ^ (k >> 15)) + __float_as_uint(pxyz[i * 3 + 1]) * 0x85EBCA77u;
-            k = (k ^ (k >> 13)) + __float_as_uint(pxyz[i * 3 + 2]) * 0xC2B2AE3Du;
-            h[j] = (k ^ (k >> 16)) & 1023u;
-            atomicMin(&slot[h[j]], (uint32_t)i);
-        }
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const int i = lane * 4 + j;
-            const int f = (int)slot[h[j]];   // f <= i: the slot keeps the lowest index of its hash
-            bool r = f != i;
-#pragma unroll
-            for (int e = 0; e < 3; e++)
-                r = r && __float_as_uint(pxyz[f * 3 + e]) == __float_as_uint(pxyz[i * 3 + e]) &&
-                    __float_as_uint(prgb[f * 3 + e]) == __float_as_uint(prgb[i * 3 + e]);
-            rep[i] = r ? 1 : 0;
-        }
-        __syncthreads();
+        repeat_flags(xyz, rgb, o, slot, pxyz, prgb, rep);
         // 512 rows per step: lane l owns the 8 consecutive rows [512 s + 8 l, +8) (one 16-byte load; the lists are 16-byte
         // aligned and 0xFFFF-terminated inside their allocation), the next step's load is in flight while this one is written
         uint16_t* list = rows + o * (int64_t)max_rows;
@@ -559,6 +620,111 @@ __global__ __launch_bounds__(64) void k_dedup_rows(const float* __restrict__ xyz
     }
 }
 
+
+// ---- level-0 row lists built from the scan's hit masks (GroupTables::mask_l0) ------------------------------------------
+// The final SA1 list of k_sample_group + k_dedup_rows, written once.  In: the object's [128][4 x u64] hit masks at the start of
+// its rows slice (level_fast, MASK) and fps_idx of level 0.  One wavefront per object, lane l builds centroids l and l + 64:
+// cap (the first 32 set bits in point order: the reference's neighbourhood), then the repeat bits are cleared (repeat_flags: the
+// flags k_dedup_rows uses), the rest is listed in ascending order with the self-loop row behind it.  Centroids from the first
+// tail centroid t0 on (c > 0, fps_idx[c] == 0) take centroid 0's mask: the scan stopped there and never wrote their slots.
+// The masks are in registers before the first row is stored - the list goes over them - and the list is assembled in LDS (over
+// the hash table and the staged points, dead by then) and leaves in 16-byte stores.  No loop here waits on another wave.
+
+// w with only its k lowest set bits (k < popcount(w))
+__device__ __forceinline__ unsigned long long lowest_set_bits(unsigned long long w, int k) {
+    if (k <= 0) return 0ull;
+    int p = 0;   // the largest p whose low p bits hold fewer than k set bits
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1)
+        if (__popcll(w & ((1ull << (p + s)) - 1ull)) < k) p += s;
+    return w & ((2ull << p) - 1ull);
+}
+__device__ __forceinline__ int wave_inclusive_sum(int v) {
+    const int lane = threadIdx.x;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const int t = __shfl_up(v, d, 64);
+        v += lane >= d ? t : 0;
+    }
+    return v;
+}
+
+__global__ __launch_bounds__(64) void k_build_rows(const float* __restrict__ xyz, const float* __restrict__ rgb,
+                                                   const uint8_t* __restrict__ fps_idx, int64_t n_obj, uint16_t* rows,
+                                                   uint16_t* __restrict__ n_rows, int self_loops) {
+    constexpr int NC = kMaxPts / 2, MAXR = NC * (kMaxNbr + 1);
+    __shared__ __attribute__((aligned(16))) unsigned char smem[1024 * 4 + 2 * kMaxPts * 3 * 4];   // 10 KB >= the 8,448-byte list
+    __shared__ uint8_t rep[kMaxPts];
+    uint32_t* const slot = (uint32_t*)smem;
+    float* const pxyz = (float*)(smem + 1024 * 4);
+    float* const prgb = pxyz + kMaxPts * 3;
+    uint16_t* const img = (uint16_t*)smem;
+    const int lane = threadIdx.x;
+    const int sl = self_loops ? 1 : 0;
+    for (int64_t o = blockIdx.x; o < n_obj; o += gridDim.x) {
+        repeat_flags(xyz, rgb, o, slot, pxyz, prgb, rep);
+        unsigned long long repw[4];
+#pragma unroll
+        for (int j = 0; j < 4; j++) repw[j] = __ballot(rep[64 * j + lane] != 0);
+        uint16_t* const list = rows + o * (int64_t)MAXR;
+        const uint8_t* const fo = fps_idx + o * (int64_t)NC;
+        const unsigned long long ta = __ballot(lane > 0 && fo[lane] == 0), tb = __ballot(fo[lane + 64] == 0);
+        const int t0 = ta != 0 ? (int)__builtin_ctzll(ta) : tb != 0 ? 64 + (int)__builtin_ctzll(tb) : NC;
+        const uint4* const mk = (const uint4*)list;
+        int n[2], off[2];
+        unsigned long long w[2][4];
+#pragma unroll
+        for (int h = 0; h < 2; h++) {
+            const int c = lane + 64 * h;
+            const int cm = c < t0 ? c : 0;
+            const uint4 lo = mk[2 * cm], hi = mk[2 * cm + 1];
+            w[h][0] = (unsigned long long)lo.x | ((unsigned long long)lo.y << 32);
+            w[h][1] = (unsigned long long)lo.z | ((unsigned long long)lo.w << 32);
+            w[h][2] = (unsigned long long)hi.x | ((unsigned long long)hi.y << 32);
+            w[h][3] = (unsigned long long)hi.z | ((unsigned long long)hi.w << 32);
+            int left = kMaxNbr;
+            n[h] = sl;
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                int pc = __popcll(w[h][j]);
+                if (pc > left) {
+                    w[h][j] = lowest_set_bits(w[h][j], left);
+                    pc = left;
+                }
+                left -= pc;
+                w[h][j] &= ~repw[j];
+                n[h] += __popcll(w[h][j]);
+            }
+        }
+        const int sa = wave_inclusive_sum(n[0]), sb = wave_inclusive_sum(n[1]);
+        const int total_a = __builtin_amdgcn_readlane(sa, 63), total = total_a + __builtin_amdgcn_readlane(sb, 63);
+        off[0] = sa - n[0];
+        off[1] = total_a + sb - n[1];
+#pragma unroll
+        for (int h = 0; h < 2; h++) {
+            const int c = lane + 64 * h;
+            int p = off[h];
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                unsigned long long x = w[h][j];
+                while (x != 0) {
+                    img[p++] = (uint16_t)((c << 8) | (64 * j + (int)__builtin_ctzll(x)));
+                    x &= x - 1;
+                }
+            }
+            if (sl) img[p] = (uint16_t)(((c | 0x80) << 8) | c);
+        }
+        // the 4-row terminator consumers rely on, and 0xFFFF up to the end of the last 16-byte piece that is stored
+        if (lane < 12 && total + lane < MAXR) img[total + lane] = 0xFFFF;
+        __syncthreads();
+        int pieces = (total + 4 + 7) / 8;
+        pieces = pieces < MAXR / 8 ? pieces : MAXR / 8;
+        for (int i = lane; i < pieces; i += 64) ((uint4*)list)[i] = ((const uint4*)img)[i];
+        if (lane == 0) n_rows[o] = (uint16_t)total;
+        __syncthreads();
+    }
+}
+
 }  // namespace
 
 int launch_dedup_rows(const float* xyz, const float* rgb, int64_t n_obj, int n_pts, uint16_t* rows, uint16_t* n_rows,
@@ -572,6 +738,19 @@ int launch_dedup_rows(const float* xyz, const float* rgb, int64_t n_obj, int n_p
     T2P_REPEAT(ps_) hipLaunchKernelGGL(k_dedup_rows, dim3((unsigned)grid), dim3(64), 0, st, xyz, rgb, n_obj, rows, n_rows,
                        n_cent * (kMaxNbr + 1));
     T2P_CHECK_LAUNCH("dedup_rows");
+    return 0;
+}
+
+int launch_build_rows(const float* xyz, const float* rgb, const uint8_t* fps_idx, int64_t n_obj, int n_pts, uint16_t* rows,
+                      uint16_t* n_rows, int self_loops, hipStream_t st) {
+    T2P_CHECK_ARG(n_pts == kMaxPts && xyz && rgb && fps_idx && rows && n_rows, "build_rows: built for %d points per object", kMaxPts);
+    T2P_CHECK_ARG((((uintptr_t)xyz | (uintptr_t)rgb | (uintptr_t)rows) & 15) == 0, "build_rows: xyz, rgb and rows must be 16-byte aligned");
+    if (n_obj == 0) return 0;
+    const int64_t grid = n_obj < (int64_t)num_cus() * 64 ? n_obj : (int64_t)num_cus() * 64;
+    // (not repeated under t2p_profile_repeat: the kernel consumes the masks it overwrites)
+    ProfScope ps_("build_rows", st);
+    hipLaunchKernelGGL(k_build_rows, dim3((unsigned)grid), dim3(64), 0, st, xyz, rgb, fps_idx, n_obj, rows, n_rows, self_loops);
+    T2P_CHECK_LAUNCH("build_rows");
     return 0;
 }
 
@@ -598,7 +777,12 @@ int launch_sample_group(const float* xyz, int64_t n_obj, int n_pts, const float 
     if (want_nbr) lds += (kMaxPts / 2) * kMaxNbr + kMaxPts / 2;
     const bool fast = n_pts == kMaxPts && !want_nbr && gt.rows[0] && gt.rows[1] && gt.rows[2] &&
                       gt.n_dense[0] == kMaxPts && gt.n_dense[1] == kMaxPts / 2 && gt.n_dense[2] == kMaxPts / 4;
-    if (fast)
+    T2P_CHECK_ARG(!gt.mask_l0 || (fast && ((uintptr_t)gt.rows[0] & 15) == 0),
+                  "sample_group: hit masks (mask_l0) exist for 256 points per object with all row lists wanted, rows 16-byte aligned");
+    if (fast && gt.mask_l0)
+        T2P_REPEAT(ps_) hipLaunchKernelGGL((k_sample_group<true, true>), dim3((unsigned)grid), dim3(64), lds, st, xyz, n_obj, n_pts,
+                           radius[0], radius[1], radius[2], gt);
+    else if (fast)
         T2P_REPEAT(ps_) hipLaunchKernelGGL(k_sample_group<true>, dim3((unsigned)grid), dim3(64), lds, st, xyz, n_obj, n_pts, radius[0],
                            radius[1], radius[2], gt);
     else

@@ -209,6 +209,10 @@ struct GroupTables {
     // accumulator slot whose B row is centroid 0's), every tail centroid keeps its self-loop row, and the consumer's drain takes
     // max(acc[c], acc[code]) for tail centroids.  The list is then no longer sorted by centroid.
     int share_tail[3];
+    // mask_l0 != 0 (256-point fast path only): level 0 leaves no list.  The kernel writes each centroid's point-ordered 256-bit
+    // hit mask, [centroid][4 x u64], to the start of the object's rows[0] slice (4,096 of its 8,448 bytes) - up to the first
+    // tail centroid, where it stops - and n_rows[0] is not written.  launch_build_rows turns the masks into the final list.
+    int mask_l0;
     int n_dense[3];
     int n_cent[3];
     // Optional layer-1 tables written by the same kernel (it is VALU-bound and leaves the memory pipes idle; as separate
@@ -232,6 +236,10 @@ int launch_sample_group(const float* xyz, int64_t n_obj, int n_pts, const float 
 // (identical message, so the max-aggregate is unchanged); updates n_rows.  rows [n_obj][n_cent * 33], n_pts = 256.
 int launch_dedup_rows(const float* xyz, const float* rgb, int64_t n_obj, int n_pts, uint16_t* rows, uint16_t* n_rows,
                       int n_cent, hipStream_t st);
+// Level 0's final row lists from the hit masks of a launch_sample_group with mask_l0 (same stream, directly behind it): the
+// list launch_sample_group + launch_dedup_rows leave, bit for bit; writes n_rows.  fps_idx: level 0's.  n_pts = 256.
+int launch_build_rows(const float* xyz, const float* rgb, const uint8_t* fps_idx, int64_t n_obj, int n_pts, uint16_t* rows,
+                      uint16_t* n_rows, int self_loops, hipStream_t st);
 
 // ---- tables.hip / small kernels ------------------------------------------------------------------------------
 // gather level-l centroid positions: out[(o*n_cent + c), 0..2]

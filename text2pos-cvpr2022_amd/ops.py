@@ -254,6 +254,30 @@ def group_rows(xyz: torch.Tensor, radius=(0.2, 0.3, 0.4), self_loops: bool = Tru
     return out
 
 
+def group_rows_built(xyz: torch.Tensor, rgb: torch.Tensor, radius=(0.2, 0.3, 0.4), self_loops: bool = True, share_mask: int = 0):
+    """group_rows followed by dedup_rows on level 0, as the encoder runs them by default (t2p_group_rows_built): the scan
+    publishes level 0's hit masks and one builder kernel writes the pruned list.  xyz, rgb [n_obj, 256, 3] fp32.
+    Returns the dict of group_rows, bit for bit what the two calls leave."""
+    _need(xyz, "xyz", torch.float32, 3)
+    _need(rgb, "rgb", torch.float32, 3, xyz.device)
+    dev = xyz.device
+    n_obj, n_pts, three = xyz.shape
+    if three != 3 or tuple(rgb.shape) != tuple(xyz.shape):
+        raise RuntimeError(f"group_rows_built: xyz and rgb must both be [n_obj, n_pts, 3], got {tuple(xyz.shape)} and {tuple(rgb.shape)}")
+    nd, out = n_pts, dict(fps_idx=[], rows=[], n_rows=[])
+    for _ in range(3):
+        nc = (nd + 1) // 2
+        out["fps_idx"].append(torch.empty((n_obj, nc), dtype=torch.uint8, device=dev))
+        out["rows"].append(torch.empty((n_obj, nc * 33), dtype=torch.int16, device=dev))
+        out["n_rows"].append(torch.empty((n_obj,), dtype=torch.int16, device=dev))
+        nd = nc
+    arr = lambda ts: (C.c_void_p * 3)(*[t.data_ptr() for t in ts])
+    r = (C.c_float * 3)(*[float(v) for v in radius])
+    L.check(L.lib().t2p_group_rows_built(_ptr(xyz), _ptr(rgb), n_obj, n_pts, r, int(bool(self_loops)), int(share_mask),
+                                         arr(out["fps_idx"]), arr(out["rows"]), arr(out["n_rows"]), _stream(dev)), "t2p_group_rows_built")
+    return out
+
+
 def dedup_rows(xyz: torch.Tensor, rgb: torch.Tensor, rows: torch.Tensor, n_rows: torch.Tensor):
     """In-place t2p_dedup_rows: rows uint16 [n_obj, (n_pts / 2) * 33] (as int16 storage), n_rows uint16 [n_obj] (int16)."""
     _need(xyz, "xyz", torch.float32, 3)

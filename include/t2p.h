@@ -361,6 +361,34 @@ int t2p_matching_loss(const float* P, int64_t batch, int32_t n_obj, int32_t n_hi
 /* nn.MSELoss() (mean reduction; training/fine.py:36, :57-59) of a, b [n] fp32 -> loss [1]; float64 accumulation in a fixed order. */
 int t2p_mse_loss(const float* a, const float* b, int64_t n, float* loss, t2p_stream_t stream);
 
+/* Backward of the four entry points above, for training the fine stage (training/fine.py:53-70).  Each recomputes what it needs
+ * from its forward's INPUTS, writes every element of its gradient exactly once (no zero fill, no atomics: the same bits from call
+ * to call) and refuses the sizes its forward refuses, with the same codes, before any launch.  An upstream gradient g is a device
+ * pointer to one float: nothing is read back to the host. */
+/* d_msg [B (n_obj + n_hints)][D] -> d_qkv [B (n_obj + n_hints)][3 D].  With S = scale q k^T, P = softmax(S), scale = 1 / sqrt(D / 4):
+ * dV[m] = sum_t P[t, m] dO[t], dP = dO V^T, dS = P o (dP - rowsum(P o dP)), dq[t] = scale sum_m dS[t, m] k[m],
+ * dk[m] = scale sum_t dS[t, m] q[t]; dq to the q columns of the target rows, dk | dv to the k | v columns of the source rows. */
+int t2p_match_attention_backward(const float* qkv, const float* d_msg, int64_t batch, int32_t n_obj, int32_t n_hints, int32_t embed_dim,
+                                 int32_t cross, float* d_qkv, t2p_stream_t stream);
+/* dP [B][n_obj + 1][n_hints + 1] -> d_mdesc [B (n_obj + n_hints)][D] fp32 and d_bin [B] float64, the per-sample gradient of bin_score
+ * (its gradient is their sum).  float64 throughout: the forward's iterations are run again with every iterate u_t, v_t kept in
+ * `workspace` (sinkhorn_iters (n_obj + n_hints + 2) doubles per sample; T2P_E_WORKSPACE when it is too small), G = dP exp(Z) is
+ * formed from the float64 log couplings, and the unrolled iterations are walked backwards.  sinkhorn_iters = 0 is legal. */
+size_t t2p_match_head_backward_workspace_bytes(int64_t batch, int32_t n_obj, int32_t n_hints, int32_t sinkhorn_iters);
+int t2p_match_head_backward(const float* mdesc, const float* dP, int64_t batch, int32_t n_obj, int32_t n_hints, int32_t embed_dim,
+                            float bin_score, int32_t sinkhorn_iters, float* d_mdesc, double* d_bin, void* workspace,
+                            size_t workspace_bytes, t2p_stream_t stream);
+/* The whole dP [B][n_obj + 1][n_hints + 1]: -g / (B M_b P[b, i, j]) per listed entry of sample b (M_b entries; a pair listed twice
+ * counts twice), 0 elsewhere.  A listed coupling that is 0 gives what the formula gives. */
+int t2p_matching_loss_backward(const float* P, int64_t batch, int32_t n_obj, int32_t n_hints, const int32_t* idx,
+                               const int32_t* entry_ptr, int64_t n_entries, const float* g, float* dP, t2p_stream_t stream);
+/* da [n] = 2 g (a - b) / n. */
+int t2p_mse_loss_backward(const float* a, const float* b, int64_t n, const float* g, float* da, t2p_stream_t stream);
+/* out [cols] = column sums of x [rows][cols], accumulated in float64 in a fixed order and rounded once: the bias gradients of the
+ * matcher's Conv1d layers.  Three of its four bias families per layer stand in front of a softmax or a BatchNorm and have a gradient
+ * that is exactly zero: what is left of it is the rounding of the summands, and an fp32 sum would add its own on top. */
+int t2p_colsum(const float* x, int64_t rows, int32_t cols, float* out, t2p_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Text branch: CellRetrievalNetwork.encode_text (models/cell_retrieval.py:69-75) on token ids produced by the
  * host tokeniser of LanguageEncoder.forward (models/modules.py:60-72).

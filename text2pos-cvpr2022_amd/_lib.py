@@ -116,6 +116,14 @@ SYMBOLS = {
                                  c_void, c_void, c_void, c_void]),
     "t2p_matching_loss": (C.c_int, [c_void, C.c_int64, C.c_int32, C.c_int32, c_void, c_void, C.c_int64, c_void, c_void, c_void]),
     "t2p_mse_loss": (C.c_int, [c_void, c_void, C.c_int64, c_void, c_void]),
+    "t2p_match_attention_backward": (C.c_int, [c_void, c_void, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_void, c_void]),
+    "t2p_match_head_backward_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
+    "t2p_match_head_backward": (C.c_int, [c_void, c_void, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, c_void,
+                                          c_void, c_void, C.c_size_t, c_void]),
+    "t2p_matching_loss_backward": (C.c_int, [c_void, C.c_int64, C.c_int32, C.c_int32, c_void, c_void, C.c_int64, c_void, c_void,
+                                             c_void]),
+    "t2p_mse_loss_backward": (C.c_int, [c_void, c_void, C.c_int64, c_void, c_void, c_void]),
+    "t2p_colsum": (C.c_int, [c_void, C.c_int64, C.c_int32, c_void, c_void]),
     "t2p_profile_enable": (None, [C.c_int]),
     "t2p_profile_report": (C.c_int, [C.c_char_p, C.c_size_t]),
     "t2p_profile_repeat": (None, [C.c_char_p, C.c_int32]),

@@ -7,7 +7,8 @@ The hinge terms, their sum and the gradient with respect to the score matrix com
 `CrossEntropyLoss` is the criterion of the PointNet++ pre-training stage (training/pointcloud/pointnet2.py:37, :134:
 `nn.CrossEntropyLoss()(output.class_pred, batch.y)`) on t2p_softmax_xent (csrc/classify.hip).
 The fine stage (training/fine.py:35-36, :56-62): `MatchingLoss` (training/losses.py:13-30) on t2p_matching_loss and `MSELoss`
-(`nn.MSELoss()`) on t2p_mse_loss (csrc/match_train.hip) - loss VALUES for now, their gradients are the follow-up - and the two
+(`nn.MSELoss()`) on t2p_mse_loss (csrc/match_train.hip), differentiable with respect to P / the input inside
+training.fine_backward() (t2p_matching_loss_backward, t2p_mse_loss_backward; opt-in, refused outside it) - and the two
 host-side validation figures `calc_recall_precision` / `calc_pose_error` (training/losses.py:33-62, :81-123) in NumPy."""
 import numpy as np
 import torch
@@ -107,9 +108,52 @@ class CrossEntropyLoss(nn.Module):
         return loss
 
 
+def _wants_grad(*tensors):
+    return torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in tensors)
+
+
 def _no_grad_inputs(what, *tensors):
-    if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in tensors):
+    """Refuses inputs that would record a graph unless training.fine_backward() is on; returns whether a graph is wanted."""
+    if not _wants_grad(*tensors):
+        return False
+    from . import training
+    if not training.fine_backward_enabled():
         raise NotImplementedError(f"{what}: the backward is not built; detach the inputs or call it under torch.no_grad()")
+    return True
+
+
+class _MatchingLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, P, idx, entry_ptr):
+        x = P.detach()
+        if x.dtype != torch.float32:
+            x = x.float()
+        x = x.contiguous()
+        loss, sample = ops.matching_loss(x, idx, entry_ptr)
+        ctx.save_for_backward(x, idx, entry_ptr)
+        ctx.dtype = P.dtype
+        ctx.mark_non_differentiable(sample)
+        return loss[0], sample
+
+    @staticmethod
+    def backward(ctx, g, _g_sample):
+        x, idx, entry_ptr = ctx.saved_tensors
+        d_p = ops.matching_loss_backward(x, idx, entry_ptr, g.detach().float().reshape(1).contiguous())   # g stays on the device
+        return d_p.to(ctx.dtype), None, None
+
+
+class _MseLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, input, target):
+        a, b = input.detach().float().contiguous(), target.detach().float().contiguous()
+        ctx.save_for_backward(a, b)
+        ctx.dtype = input.dtype
+        return ops.mse_loss(a, b)[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        a, b = ctx.saved_tensors
+        return ops.mse_loss_backward(a, b, g.detach().float().reshape(1).contiguous()).to(ctx.dtype), None
 
 
 class MatchingLoss(nn.Module):
@@ -117,7 +161,8 @@ class MatchingLoss(nn.Module):
     all_matches a list of B integer [M_i, 2] tensors / arrays of (object, hint) pairs, dustbin indices n_obj / n_hints included:
     mean over the samples of the mean over a sample's pairs of -log P[b, i, j], in ONE kernel launch (fixed summation order, float64
     accumulation: bit-identical from call to call).  As in the reference, a listed coupling that is 0 in fp32 gives inf.
-    `last_sample_losses` [B] holds the per-sample means of the latest call.  Forward only.
+    `last_sample_losses` [B] holds the per-sample means of the latest call.  Differentiable with respect to P inside
+    training.fine_backward(): dP = -g / (B M_b P) per listed entry (a pair listed twice counts twice), 0 elsewhere.
     A pair outside [0, n_obj] x [0, n_hints] raises IndexError (the kernel marks the sample with NaN instead of reading through it;
     reading the loss back here costs the host synchronisation the loop's `loss.item()` pays anyway)."""
 
@@ -131,7 +176,7 @@ class MatchingLoss(nn.Module):
             raise RuntimeError("MatchingLoss: P must be a [B, n_obj + 1, n_hints + 1] tensor")
         if not P.is_cuda:
             raise RuntimeError(f"MatchingLoss: P must live on the GPU (got device {P.device}); there is no CPU path")
-        _no_grad_inputs("MatchingLoss", P)
+        grad = _no_grad_inputs("MatchingLoss", P)
         if len(all_matches) != P.shape[0]:
             raise RuntimeError(f"MatchingLoss: {P.shape[0]} samples in P but {len(all_matches)} match lists")
         lists = []
@@ -151,13 +196,16 @@ class MatchingLoss(nn.Module):
         both = np.concatenate([np.clip(flat, -1, np.iinfo(np.int32).max).reshape(-1), ptr]).astype(np.int32)
         dev_both = torch.from_numpy(both).to(P.device)       # one upload
         idx, entry_ptr = dev_both[: 2 * flat.shape[0]].view(-1, 2), dev_both[2 * flat.shape[0]:]
-        x = P.detach()
-        if x.dtype != torch.float32:
-            x = x.float()
-        loss, sample = ops.matching_loss(x.contiguous(), idx, entry_ptr)
+        if grad:
+            loss, sample = _MatchingLossFn.apply(P, idx.contiguous(), entry_ptr.contiguous())
+        else:
+            x = P.detach()
+            if x.dtype != torch.float32:
+                x = x.float()
+            loss, sample = ops.matching_loss(x.contiguous(), idx, entry_ptr)
+            loss = loss[0]
         self.last_sample_losses = sample
-        loss = loss[0]
-        if bool(torch.isnan(loss)):
+        if bool(torch.isnan(loss.detach())):
             m1, n1 = P.shape[1], P.shape[2]
             for b, a in enumerate(lists):
                 bad = np.nonzero((a[:, 0] < 0) | (a[:, 0] >= m1) | (a[:, 1] < 0) | (a[:, 1] >= n1))[0]
@@ -171,7 +219,8 @@ class MatchingLoss(nn.Module):
 
 class MSELoss(nn.Module):
     """`nn.MSELoss()` as training/fine.py:36, :57-59 uses it: criterion(output.offsets, target offsets), mean reduction, one kernel
-    launch with a fixed summation order.  Forward only."""
+    launch with a fixed summation order.  Differentiable with respect to the input inside training.fine_backward()
+    (2 g (input - target) / n); a target that requires grad is refused."""
 
     def forward(self, input, target):
         if not isinstance(input, torch.Tensor) or not isinstance(target, torch.Tensor):
@@ -183,7 +232,12 @@ class MSELoss(nn.Module):
                                "there is no CPU path")
         if input.numel() == 0:
             raise RuntimeError("MSELoss: empty input")
-        _no_grad_inputs("MSELoss", input, target)
+        if _wants_grad(target):
+            from . import training
+            if training.fine_backward_enabled():
+                raise NotImplementedError("MSELoss: the backward with respect to the target is not built; detach the target")
+        if _no_grad_inputs("MSELoss", input, target):
+            return _MseLossFn.apply(input, target)
         return ops.mse_loss(input.detach().float().contiguous(), target.detach().float().contiguous())[0]
 
 

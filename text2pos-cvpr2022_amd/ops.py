@@ -949,6 +949,83 @@ def mse_loss(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     return loss
 
 
+def match_attention_backward(qkv: torch.Tensor, d_msg: torch.Tensor, batch: int, n_obj: int, n_hints: int, cross: bool) -> torch.Tensor:
+    """Gradient of match_attention: qkv [B (n_obj + n_hints), 3 D] as the forward read it, d_msg [B (n_obj + n_hints), D] ->
+    d_qkv [B (n_obj + n_hints), 3 D] (t2p_match_attention_backward; every element written once, no atomics)."""
+    _need(qkv, "qkv", torch.float32, 2)
+    _need(d_msg, "d_msg", torch.float32, 2, qkv.device)
+    rows = int(batch) * (int(n_obj) + int(n_hints))
+    if qkv.shape[0] != rows or qkv.shape[1] % 3 or tuple(d_msg.shape) != (rows, qkv.shape[1] // 3):
+        raise RuntimeError(f"match_attention_backward: qkv is {tuple(qkv.shape)} and d_msg {tuple(d_msg.shape)}, expected "
+                           f"[{rows}, 3 D] and [{rows}, D]")
+    d_qkv = torch.empty_like(qkv)
+    L.check(L.lib().t2p_match_attention_backward(_ptr(qkv), _ptr(d_msg), int(batch), int(n_obj), int(n_hints), d_msg.shape[1],
+                                                 int(bool(cross)), _ptr(d_qkv), _stream(qkv.device)), "t2p_match_attention_backward")
+    return d_qkv
+
+
+def match_head_backward(mdesc: torch.Tensor, d_p: torch.Tensor, batch: int, n_obj: int, n_hints: int, bin_score: float,
+                        sinkhorn_iters: int):
+    """Gradient of match_head's couplings: mdesc [B (n_obj + n_hints), D] as the forward read it, d_p [B, n_obj + 1, n_hints + 1] ->
+    (d_mdesc like mdesc, d_bin [B] float64: the per-sample gradient of bin_score) of t2p_match_head_backward."""
+    _need(mdesc, "mdesc", torch.float32, 2)
+    dev = mdesc.device
+    b, m, n = int(batch), int(n_obj), int(n_hints)
+    _need(d_p, "d_p", torch.float32, 3, dev)
+    if mdesc.shape[0] != b * (m + n) or tuple(d_p.shape) != (b, m + 1, n + 1):
+        raise RuntimeError(f"match_head_backward: mdesc is {tuple(mdesc.shape)} and d_p {tuple(d_p.shape)}, expected "
+                           f"[{b * (m + n)}, D] and [{b}, {m + 1}, {n + 1}]")
+    d_mdesc = torch.empty_like(mdesc)
+    d_bin = torch.empty((b,), dtype=torch.float64, device=dev)
+    ws = torch.empty((max(1, L.lib().t2p_match_head_backward_workspace_bytes(b, m, n, int(sinkhorn_iters))),), dtype=torch.uint8,
+                     device=dev)
+    L.check(L.lib().t2p_match_head_backward(_ptr(mdesc), _ptr(d_p), b, m, n, mdesc.shape[1], float(bin_score), int(sinkhorn_iters),
+                                            _ptr(d_mdesc), _ptr(d_bin), _ptr(ws), ws.numel(), _stream(dev)),
+            "t2p_match_head_backward")
+    return d_mdesc, d_bin
+
+
+def matching_loss_backward(P: torch.Tensor, idx: torch.Tensor, entry_ptr: torch.Tensor, g: torch.Tensor) -> torch.Tensor:
+    """Gradient of matching_loss with respect to P; g: the upstream gradient, one fp32 value ON THE DEVICE (nothing is read back).
+    Returns the whole dP [B, n_obj + 1, n_hints + 1] (t2p_matching_loss_backward)."""
+    _need(P, "P", torch.float32, 3)
+    dev = P.device
+    _need(idx, "idx", torch.int32, 2, dev)
+    _need(entry_ptr, "entry_ptr", torch.int32, 1, dev)
+    _need(g, "g", torch.float32, 1, dev)
+    b = P.shape[0]
+    if idx.shape[1] != 2 or entry_ptr.numel() != b + 1 or g.numel() != 1:
+        raise RuntimeError(f"matching_loss_backward: idx {tuple(idx.shape)} must be [n_entries, 2], entry_ptr [{b + 1}] and g [1]")
+    if b < 1 or P.shape[1] < 2 or P.shape[2] < 2:
+        raise RuntimeError(f"matching_loss_backward: P {tuple(P.shape)} must be [B >= 1, n_obj + 1, n_hints + 1]")
+    d_p = torch.empty_like(P)
+    L.check(L.lib().t2p_matching_loss_backward(_ptr(P), b, P.shape[1] - 1, P.shape[2] - 1, _ptr(idx), _ptr(entry_ptr), idx.shape[0],
+                                               _ptr(g), _ptr(d_p), _stream(dev)), "t2p_matching_loss_backward")
+    return d_p
+
+
+def mse_loss_backward(a: torch.Tensor, b: torch.Tensor, g: torch.Tensor) -> torch.Tensor:
+    """Gradient of mse_loss with respect to a: 2 g (a - b) / n; g: one fp32 value on the device (t2p_mse_loss_backward)."""
+    _need(a, "input", torch.float32)
+    _need(b, "target", torch.float32, None, a.device)
+    _need(g, "g", torch.float32, 1, a.device)
+    if a.shape != b.shape or g.numel() != 1:
+        raise RuntimeError(f"mse_loss_backward: shapes {tuple(a.shape)} and {tuple(b.shape)} differ, or g is not [1]")
+    da = torch.empty_like(a)
+    L.check(L.lib().t2p_mse_loss_backward(_ptr(a), _ptr(b), a.numel(), _ptr(g), _ptr(da), _stream(a.device)), "t2p_mse_loss_backward")
+    return da
+
+
+def colsum(x: torch.Tensor) -> torch.Tensor:
+    """Column sums of x [rows, cols] fp32 -> [cols], accumulated in float64 in a fixed order, rounded once (t2p_colsum)."""
+    _need(x, "x", torch.float32, 2)
+    if x.shape[0] < 1 or x.shape[1] < 1:
+        raise RuntimeError(f"colsum: x {tuple(x.shape)} must have rows and columns")
+    out = torch.empty((x.shape[1],), dtype=torch.float32, device=x.device)
+    L.check(L.lib().t2p_colsum(_ptr(x), x.shape[0], x.shape[1], _ptr(out), _stream(x.device)), "t2p_colsum")
+    return out
+
+
 # ---------------------------------------------------------------------------------------------------------------
 def profile_enable(on: bool):
     """Bracket every kernel launch with hipEvents on its launch stream (bench.py's live per-kernel timing)."""

@@ -8,7 +8,8 @@ checkpoints load with strict=True), with the arithmetic executed by libt2p_hip.s
 
 Callers that drop in unchanged: evaluation/pipeline.py:189-191 (run_fine) and training/fine.py's eval loop.
 In train() mode (under no_grad: training/fine.py validates without calling eval()) the same outputs come from the unfolded,
-batch-statistics path of train_cell.py / train_match.py.  Forward-only: the backward of the matcher is not built.
+batch-statistics path of train_cell.py / train_match.py; with autograd on, that path is differentiable inside
+training.fine_backward() (opt-in, default off: outside it a call that would record a graph is refused, as in eval() mode).
 """
 from copy import deepcopy
 from typing import List
@@ -141,6 +142,9 @@ class SuperGlueMatch(PicklableModule):
     def _check_forward_only(self):
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
             if self.training:
+                from . import training
+                if training.fine_backward_enabled():
+                    return
                 raise NotImplementedError("the backward of the matcher is not built (multi-head attention, the optimal-"
                                           "transport head and the two fine losses are forward-only): run the training-mode "
                                           "forward under torch.no_grad()")

@@ -227,7 +227,10 @@ class _LinearFn(torch.autograd.Function):
     every row of dY and X read once per row range, fixed-order reduction of the partial blocks: deterministic)."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias):
+    def forward(ctx, x, weight, bias, bias_f64=False):
+        """bias_f64: db from ops.colsum (float64 accumulation, one rounding) instead of the fp32 column sums that ride along in
+        the weight-gradient kernel - for layers whose bias gradient is exactly zero (train_match.py)."""
+        ctx.bias_f64 = bool(bias_f64)
         k, n = x.shape[1], weight.shape[0]
         kw = weight.shape[1]                               # k > kw: x arrives with zero columns behind its kw inputs (edge_features)
         pad = (-k) % 8                                     # the GEMM wants K % 4 == 0 and N % 8 == 0: zero columns
@@ -250,17 +253,21 @@ class _LinearFn(torch.autograd.Function):
     def backward(ctx, dy):
         xp, wp = ctx.saved_tensors
         dy = dy.contiguous()
-        need_x, need_w, need_b = ctx.needs_input_grad
+        need_x, need_w, need_b = ctx.needs_input_grad[:3]
+        extra = (None,) * (len(ctx.needs_input_grad) - 3)
         # [M, N] x [N, K]: the weight is its own k-major operand
-        dx = ops.gemm(dy, wp)[:, : ctx.k] if need_x else None
+        # (an output width that is no multiple of 4, mlp_offsets' 2 columns: ops.matmul zero-pads the product's inner dimension)
+        dx = (ops.gemm(dy, wp) if dy.shape[1] % 4 == 0 else ops.matmul(dy, wp))[:, : ctx.k] if need_x else None
         dw = db = None
         want_b = bool(need_b and ctx.has_bias)
         if need_w:                                         # frozen layers (--pointnet_freeze) skip it
-            dw, db = ops.linear_wgrad(dy, xp, want_colsum=want_b)
+            dw, db = ops.linear_wgrad(dy, xp, want_colsum=want_b and not ctx.bias_f64)
             dw = dw[:, : ctx.kw]
-        elif want_b:
+        elif want_b and not ctx.bias_f64:
             db = dy.sum(0)
-        return dx, dw, db
+        if want_b and ctx.bias_f64:
+            db = ops.colsum(dy)
+        return (dx, dw, db) + extra
 
 
 def linear(x, lin: torch.nn.Linear):

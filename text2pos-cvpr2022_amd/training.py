@@ -2,14 +2,16 @@
 train_pointnet_epoch, val_pointnet_epoch below) and of the reference's coarse training (training/coarse.py:31-62, `train_epoch`) on the HIP path: same batch
 dictionary (`texts`, `objects`, `object_points` as the reference's Kitti360CoarseDataset.collate_fn yields them), same
 order of calls; the arithmetic is docs/notebook.md 4.8.  val_fine_epoch is the validation pass of the fine stage
-(training/fine.py:119-170, `eval_epoch`), which the reference runs in train() mode.  The data side (datasets, augmentation, plotting) stays with the caller."""
+(training/fine.py:119-170, `eval_epoch`), which the reference runs in train() mode; train_fine_epoch is its training pass
+(training/fine.py:36-116, `train_epoch`), inside the opt-in fine_backward().  The data side (datasets, augmentation, plotting) stays with the caller."""
+import contextlib
 from typing import Iterable, Optional
 
 import numpy as np
 import torch
 
 from . import ops
-from .losses import HardestRankingLoss, PairwiseRankingLoss, calc_pose_error, calc_recall_precision
+from .losses import HardestRankingLoss, MatchingLoss, MSELoss, PairwiseRankingLoss, calc_pose_error, calc_recall_precision
 
 
 def make_criterion(args) -> torch.nn.Module:
@@ -140,3 +142,72 @@ def val_fine_epoch(model, dataloader: Iterable[dict]) -> dict:
         for k, v in fine_batch_stats(batch, output).items():
             stats[k].append(v)
     return {k: float(np.mean(v)) if v else float("nan") for k, v in stats.items()}
+
+
+# ---- the fine stage's backward: opt-in ------------------------------------------------------------------------------------------------
+_FINE_BACKWARD = False    # consulted by SuperGlueMatch._check_forward_only (train() branch) and losses._no_grad_inputs
+
+
+def fine_backward_enabled() -> bool:
+    return _FINE_BACKWARD
+
+
+def enable_fine_backward(on: bool = True) -> bool:
+    """Sets the switch; returns what it was.  Off (the default): SuperGlueMatch in train() mode, MatchingLoss and MSELoss refuse
+    inputs that would record a graph.  On: they are differentiable (csrc/match_train.hip's backward kernels).  eval() mode with
+    autograd stays refused either way."""
+    global _FINE_BACKWARD
+    was, _FINE_BACKWARD = _FINE_BACKWARD, bool(on)
+    return was
+
+
+@contextlib.contextmanager
+def fine_backward(on: bool = True):
+    """`with training.fine_backward(): ...` - the switch of enable_fine_backward for the body, restored afterwards (also when the
+    body raises)."""
+    was = enable_fine_backward(on)
+    try:
+        yield
+    finally:
+        enable_fine_backward(was)
+
+
+FINE_TRAIN_KEYS = ("loss", "loss_offsets") + FINE_VAL_KEYS
+
+
+def train_fine_epoch(model, dataloader: Iterable[dict], optimizer, max_batches: Optional[int] = None) -> dict:
+    """training/fine.py:36-116 (`train_epoch`): one pass over `dataloader` (batches as Kitti360FineDataset.collate_fn builds them:
+    objects, hint_descriptions, object_points, matches, all_matches, offsets, poses) in train() mode, loss = MatchingLoss(P,
+    all_matches) + 5 MSELoss(offsets, target offsets), and the reference's seven statistics as means over the batches: loss,
+    loss_offsets, recall, precision, pose_mid, pose_mean, pose_offsets (fine_batch_stats).  Enters fine_backward() itself.
+    A step whose loss is not finite (an untrained matcher's listed couplings can lie below fp32's range: -log 0) is skipped - no
+    backward, no optimizer.step() - and counted in stats["skipped_steps"]; the reference gets there through detect_anomaly and its
+    try / except around loss.backward().  Its loss still enters the mean, as in the reference."""
+    model.train()
+    criterion_matching, criterion_offsets = MatchingLoss(), MSELoss()
+    stats = {k: [] for k in FINE_TRAIN_KEYS}
+    skipped = 0
+    dev = model.device
+    with fine_backward():
+        for i_batch, batch in enumerate(dataloader):
+            if max_batches is not None and i_batch >= max_batches:
+                break
+            optimizer.zero_grad()
+            output = model(batch["objects"], batch["hint_descriptions"], batch["object_points"])
+            loss_matching = criterion_matching(output.P, batch["all_matches"])
+            target = torch.from_numpy(np.ascontiguousarray(np.asarray(batch["offsets"], dtype=np.float32))).to(dev)
+            loss_offsets = criterion_offsets(output.offsets, target)
+            loss = loss_matching + 5 * loss_offsets
+            value = loss.item()
+            if np.isfinite(value):
+                loss.backward()
+                optimizer.step()
+            else:
+                skipped += 1
+            stats["loss"].append(value)
+            stats["loss_offsets"].append(loss_offsets.item())
+            for k, v in fine_batch_stats(batch, output).items():
+                stats[k].append(v)
+    out = {k: float(np.mean(v)) if v else float("nan") for k, v in stats.items()}
+    out["skipped_steps"] = skipped
+    return out

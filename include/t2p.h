@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define T2P_ABI_VERSION 31
+#define T2P_ABI_VERSION 32
 #define T2P_DEFAULT_CHUNK_OBJECTS 65000 /* t2p_cell_config.chunk_objects == 0 */
 #define T2P_MAX_CHUNK_OBJECTS 65535     /* 32-bit table offsets / 16-bit local indices: chunk_objects and the largest single
                                            cell may not exceed it (T2P_E_ARG otherwise).  The caller-provided workspace holds
@@ -611,9 +611,32 @@ int t2p_dedup_rows(const float* xyz, const float* rgb, int64_t n_obj, int32_t n_
 /* knn of DynamicEdgeConv (cell_retrieval.py:46-48): x [n][dim], seg_ptr [n_seg+1] int32, out [n][k] int32 */
 int t2p_knn(const float* x, int32_t dim, const int32_t* seg_ptr, int32_t n_seg, int32_t max_seg_rows, int32_t k,
             int32_t* out_idx, t2p_stream_t stream);
-/* C[M][ldc] (+c0) = act(A[M][lda] W[K][N] + bias[N]);  K % 4 == 0, N % 8 == 0, lda % 4 == 0 */
+/* C[M][ldc] (+c0) = act(A[M][lda] W[K][N] + bias[N]);  K % 4 == 0, N % 8 == 0, lda % 4 == 0; A and W 16-byte aligned.
+ * Only columns [c0, c0 + N) of rows [0, M) of C are written.  bias may be NULL.  act is the identity (relu = 0) or ReLU as
+ * torch.relu states it: v <= 0 ? 0 : v, so a NaN stays a NaN (a non-finite element of A reaches exactly its own row of C). */
 int t2p_gemm(const float* a, int32_t lda, const float* w, const float* bias, float* c, int32_t ldc, int32_t c0,
              int64_t m, int32_t k, int32_t n, int32_t relu, t2p_stream_t stream);
+/* t2p_gemm with a residual added behind the activation: C = act(A W + bias) + resid[M][ldr] (resid NULL: t2p_gemm).  resid may
+ * alias C (ldr = ldc, resid = c + c0: each element is read and written by one thread).  -1 on NULL operands or pitches below
+ * the widths (lda < k, ldc < c0 + n, ldr < n). */
+int t2p_gemm_residual(const float* a, int32_t lda, const float* w, const float* bias, float* c, int32_t ldc, int32_t c0,
+                      int64_t m, int32_t k, int32_t n, int32_t relu, const float* resid, int32_t ldr, t2p_stream_t stream);
+/* The same contract on the f16x3 matrix path (csrc/tg_gemm_x3.hip), the default-precision GEMM of the heads and the matcher:
+ * wx is the image of packing.py::pack_gemm_x3 for `scale` (a power of two), 16-byte aligned.  A is split into fp16 hi + lo on
+ * the fly; hi.hi + hi.lo + lo.hi share one fp32 accumulator, the epilogue divides by scale.  amax_in (may be NULL) is the
+ * fp16-range guard word of A: the kernel raises it (atomic max on the bit pattern) to max |A[m][k]| over [M][K] exactly.
+ * A NaN in A reaches its own row of C and nothing else (an infinity is past the guard: its row becomes NaN).
+ * -1 on NULL operands (a, wx, c with m > 0), sizes below 1, pitches below the widths (lda < k, ldc < c0 + n, ldr < n), and a
+ * scale that is not a positive power of two. */
+int t2p_gemm_x3(const float* a, int32_t lda, const void* wx, float scale, const float* bias, float* c, int32_t ldc, int32_t c0,
+                int64_t m, int32_t k, int32_t n, int32_t relu, const float* resid, int32_t ldr, uint32_t* amax_in,
+                t2p_stream_t stream);
+/* C[M][ldc] = A[M][lda] W[K][N] for few rows and a long K (csrc/tg_gemm.hip::k_gemm_skinny, the per-step products of the
+ * training-mode LSTM): no bias, no activation; K % 4 == 0 (K >= 4), lda % 4 == 0, A 16-byte aligned, any N.  fp32 MFMA, sums
+ * in another order than t2p_gemm's (deterministic).  -1 on NULL operands (with m > 0), sizes below 1, lda < k or ldc < n, and a K or
+ * lda that is no multiple of 4. */
+int t2p_gemm_skinny(const float* a, int32_t lda, const float* w, float* c, int32_t ldc, int64_t m, int32_t k, int32_t n,
+                    t2p_stream_t stream);
 /* C[k1][n] (ldc) = A[m][k1]^T B[m][n]: a product whose reduction runs over the ROWS - the weight gradient dW = dY^T X of
  * every nn.Linear, the recurrent / input weight gradients of the LSTM and its gate-table gradient in the training-mode path
  * (training/coarse.py:31-62 through autograd).  The rows are split over the grid and the partial products added in a fixed

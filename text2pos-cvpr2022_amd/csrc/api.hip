@@ -1,6 +1,7 @@
 // extern "C" entry points of libt2p_hip.so (see include/t2p.h) and the launch orchestration of the cell branch.
 #include <stdarg.h>
 #include <stdlib.h>
+#include <math.h>
 #include <string.h>
 
 #include <mutex>
@@ -1163,6 +1164,37 @@ int t2p_knn(const float* x, int32_t dim, const int32_t* seg_ptr, int32_t n_seg, 
 int t2p_gemm(const float* a, int32_t lda, const float* w, const float* bias, float* c, int32_t ldc, int32_t c0,
              int64_t m, int32_t k, int32_t n, int32_t relu, t2p_stream_t stream) {
     return launch_gemm(a, lda, w, bias, c, ldc, c0, m, k, n, relu, (hipStream_t)stream);
+}
+
+// sizes, operands and pitches of the stage-level GEMM exports (a NULL operand is allowed only for an empty product)
+static int check_gemm_args(const char* what, const void* a, int lda, const void* w, const void* c, int ldc, int c0, int64_t m, int k, int n) {
+    T2P_CHECK_ARG(m >= 0 && k >= 1 && n >= 1, "%s: bad sizes m=%lld k=%d n=%d", what, (long long)m, k, n);
+    T2P_CHECK_ARG(m == 0 || (a && w && c), "%s: NULL argument", what);
+    T2P_CHECK_ARG(lda >= k && c0 >= 0 && ldc >= c0 + n, "%s: lda=%d < k=%d or ldc=%d < c0 + n = %d", what, lda, k, ldc, c0 + n);
+    return 0;
+}
+
+int t2p_gemm_residual(const float* a, int32_t lda, const float* w, const float* bias, float* c, int32_t ldc, int32_t c0,
+                      int64_t m, int32_t k, int32_t n, int32_t relu, const float* resid, int32_t ldr, t2p_stream_t stream) {
+    T2P_TRY(check_gemm_args("gemm_residual", a, lda, w, c, ldc, c0, m, k, n));
+    T2P_CHECK_ARG(resid == nullptr || ldr >= n, "gemm_residual: ldr=%d < n=%d", ldr, n);
+    return launch_gemm(a, lda, w, bias, c, ldc, c0, m, k, n, relu, (hipStream_t)stream, resid, ldr);
+}
+
+int t2p_gemm_x3(const float* a, int32_t lda, const void* wx, float scale, const float* bias, float* c, int32_t ldc, int32_t c0,
+                int64_t m, int32_t k, int32_t n, int32_t relu, const float* resid, int32_t ldr, uint32_t* amax_in,
+                t2p_stream_t stream) {
+    T2P_TRY(check_gemm_args("gemm_x3", a, lda, wx, c, ldc, c0, m, k, n));
+    T2P_CHECK_ARG(resid == nullptr || ldr >= n, "gemm_x3: ldr=%d < n=%d", ldr, n);
+    int exp2_ = 0;
+    T2P_CHECK_ARG(scale > 0.f && frexpf(scale, &exp2_) == 0.5f, "gemm_x3: scale=%g must be a power of two", (double)scale);
+    return launch_gemm_x3(a, lda, wx, scale, bias, c, ldc, c0, m, k, n, relu, (hipStream_t)stream, resid, ldr, amax_in);
+}
+
+int t2p_gemm_skinny(const float* a, int32_t lda, const float* w, float* c, int32_t ldc, int64_t m, int32_t k, int32_t n,
+                    t2p_stream_t stream) {
+    T2P_TRY(check_gemm_args("gemm_skinny", a, lda, w, c, ldc, 0, m, k, n));
+    return launch_gemm_skinny(a, lda, w, c, ldc, m, k, n, (hipStream_t)stream);
 }
 
 size_t t2p_gemm_tn_workspace_bytes(int64_t m, int32_t k1, int32_t n) { return gemm_tn_workspace_bytes(m, k1, n); }

@@ -99,7 +99,7 @@ __global__ __launch_bounds__(256) void k_gemm(const float* __restrict__ A, int l
                 const int64_t row = m0 + wr * (TS / 2) + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
                 if (row < M) {
                     float v = acc[i][j][e] + bv;
-                    if (relu) v = fmaxf(v, 0.f);
+                    if (relu) v = v <= 0.f ? 0.f : v;   // keeps NaN, as torch.relu (fmaxf would return 0)
                     if (R) v += R[row * (int64_t)ldr + col];  // residual (may alias C: same element, same thread)
                     C[row * (int64_t)ldc + c0 + col] = v;
                 }
@@ -138,7 +138,9 @@ __global__ __launch_bounds__(1024) void k_gemm_skinny(const float* __restrict__ 
 #pragma unroll 4
         for (int k = k_begin; k < k_end; k += 8) {
             const bool k_ok = k + 4 * h < K;          // (K = 8 i + 4: the upper half of the last group is past the end)
-            const int ks_ = k_ok ? k : 0;
+            // a masked half re-reads columns 0..3 of its row of A and rows 0..3 of W (ap and wp carry + 4 h: taken back here),
+            // which exist for every K >= 4; with ap + 0 it read columns 4..7 - past both operands at K == 4
+            const int ks_ = k_ok ? k : -4 * h;
             f32x4 a = *(const f32x4*)(ap + ks_);
             float b[4];
 #pragma unroll

@@ -146,7 +146,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm_x3(const float* __restrict__ A,
                 const int64_t row = m0 + wr * (TS / 2) + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
                 if (row < M) {
                     float v = fmaf(acc[i][j][e], inv_scale, bv);
-                    if (relu) v = fmaxf(v, 0.f);
+                    if (relu) v = v <= 0.f ? 0.f : v;   // keeps NaN, as torch.relu (fmaxf would return 0)
                     if (R) v += R[row * (int64_t)ldr + col];
                     C[row * (int64_t)ldc + c0 + col] = v;
                 }

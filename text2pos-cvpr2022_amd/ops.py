@@ -341,42 +341,131 @@ def matmul(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     return out if np_ == n else out[:, :n].contiguous()
 
 
-def gemm_tn(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
-    """a[M, K1]^T @ b[M, N] -> [K1, N] (t2p_gemm_tn): rows split over the grid, partials added in a fixed order.  The
-    weight-gradient products of the training-mode path (dW = dY^T X, ...): no transposed copy, no library GEMM."""
-    _need(a, "a", torch.float32, 2)
-    _need(b, "b", torch.float32, 2, a.device)
-    m, k1 = a.shape
-    if b.shape[0] != m:
-        raise RuntimeError(f"gemm_tn: a is [{m},{k1}] but b is {tuple(b.shape)}")
-    n = b.shape[1]
-    out = torch.empty((k1, n), dtype=torch.float32, device=a.device)
-    if m == 0:
-        return out.zero_()
-    ws = torch.empty((L.lib().t2p_gemm_tn_workspace_bytes(m, k1, n),), dtype=torch.uint8, device=a.device)
-    L.check(L.lib().t2p_gemm_tn(_ptr(a), k1, _ptr(b), n, _ptr(out), n, m, k1, n, _ptr(ws), ws.numel(), _stream(a.device)),
-            "t2p_gemm_tn")
+def _need_span(t: torch.Tensor, name: str, rows: int, pitch: int, width: int, dtype=torch.float32, device=None, first: int = 0):
+    """t is a contiguous buffer that holds `rows` rows of `width` elements at a pitch of `pitch`, the first at element `first`."""
+    _need(t, name, dtype, None, device)
+    if rows < 0 or width < 0 or first < 0 or pitch < first + width:
+        raise RuntimeError(f"{name}: rows={rows}, width={width} at column {first} do not fit a pitch of {pitch}")
+    need = 0 if rows == 0 else (rows - 1) * pitch + first + width
+    if t.numel() < need:
+        raise RuntimeError(f"{name}: {t.numel()} elements, but {rows} rows of {width} at pitch {pitch} (+{first}) need {need}")
+    return t
+
+
+def _resid_ptr(resid: Optional[torch.Tensor], ldr: int, first: int, m: int, n: int, device):
+    """Address of element `first` of the residual buffer (None: no residual) after checking that m rows of n at pitch ldr fit."""
+    if resid is None:
+        return None
+    _need(resid, "resid", torch.float32, None, device)
+    if ldr < n or first < 0 or resid.numel() < (0 if m == 0 else (m - 1) * ldr + first + n):
+        raise RuntimeError(f"resid: {resid.numel()} elements do not hold {m} rows of {n} at pitch {ldr} (+{first})")
+    return C.c_void_p(resid.data_ptr() + 4 * first)
+
+
+def gemm_residual(a: torch.Tensor, lda: int, w_kmajor: torch.Tensor, bias: Optional[torch.Tensor], out: torch.Tensor, ldc: int,
+                  c0: int, m: int, relu: bool = False, resid: Optional[torch.Tensor] = None, ldr: int = 0, resid_first: int = 0):
+    """out[:m, c0 : c0 + N] (pitch ldc) = act(a[:m, :K] (pitch lda) @ w_kmajor[K, N] + bias) + resid[:m, :N] (pitch ldr, from element
+    resid_first of its buffer) on t2p_gemm_residual.  a, out and resid are contiguous buffers of any shape, addressed through the
+    pitches; everything of `out` outside the window stays as it is.  resid may be `out` itself (resid_first = c0, ldr = ldc)."""
+    _need(w_kmajor, "w", torch.float32, 2, a.device)
+    k, n = w_kmajor.shape
+    _need_span(a, "a", m, lda, k)
+    _need_span(out, "out", m, ldc, n, device=a.device, first=c0)
+    if bias is not None and _need(bias, "bias", torch.float32, 1, a.device).numel() != n:
+        raise RuntimeError(f"gemm_residual: bias has {bias.numel()} elements, n = {n}")
+    r_ptr = _resid_ptr(resid, ldr, resid_first, m, n, a.device)
+    L.check(L.lib().t2p_gemm_residual(_ptr(a), lda, _ptr(w_kmajor), _ptr(bias), _ptr(out), ldc, c0, m, k, n, int(relu), r_ptr, ldr,
+                                      _stream(a.device)), "t2p_gemm_residual")
     return out
 
 
-def linear_wgrad(dy: torch.Tensor, x: torch.Tensor, want_colsum: bool = True):
+def gemm_x3(a: torch.Tensor, lda: int, wx: torch.Tensor, scale: float, bias: Optional[torch.Tensor], out: torch.Tensor, ldc: int,
+            c0: int, m: int, k: int, n: int, relu: bool = False, resid: Optional[torch.Tensor] = None, ldr: int = 0,
+            resid_first: int = 0, amax_in: Optional[torch.Tensor] = None):
+    """gemm_residual on the f16x3 matrix path (t2p_gemm_x3): wx is packing.pack_gemm_x3(w_kmajor[k, n], scale) on the device,
+    amax_in an optional int32 [1] guard word that the kernel raises to the bit pattern of max |a[:m, :k]|."""
+    _need(wx, "wx", torch.int16, 3, a.device)
+    if tuple(wx.shape) != (2, n, (k + 31) // 32 * 32):
+        raise RuntimeError(f"gemm_x3: wx is {tuple(wx.shape)}, the image of a [{k}, {n}] weight is {(2, n, (k + 31) // 32 * 32)}")
+    _need_span(a, "a", m, lda, k)
+    _need_span(out, "out", m, ldc, n, device=a.device, first=c0)
+    if bias is not None and _need(bias, "bias", torch.float32, 1, a.device).numel() != n:
+        raise RuntimeError(f"gemm_x3: bias has {bias.numel()} elements, n = {n}")
+    r_ptr = _resid_ptr(resid, ldr, resid_first, m, n, a.device)
+    if amax_in is not None and _need(amax_in, "amax_in", torch.int32, 1, a.device).numel() != 1:
+        raise RuntimeError("gemm_x3: amax_in is one int32 word")
+    L.check(L.lib().t2p_gemm_x3(_ptr(a), lda, _ptr(wx), float(scale), _ptr(bias), _ptr(out), ldc, c0, m, k, n, int(relu), r_ptr, ldr,
+                                _ptr(amax_in), _stream(a.device)), "t2p_gemm_x3")
+    return out
+
+
+def gemm_skinny(a: torch.Tensor, lda: int, w_kmajor: torch.Tensor, out: torch.Tensor, ldc: int, m: int):
+    """out[:m, :N] (pitch ldc) = a[:m, :K] (pitch lda) @ w_kmajor[K, N] on the few-rows kernel of the training-mode LSTM
+    (t2p_gemm_skinny)."""
+    _need(w_kmajor, "w", torch.float32, 2, a.device)
+    k, n = w_kmajor.shape
+    _need_span(a, "a", m, lda, k)
+    _need_span(out, "out", m, ldc, n, device=a.device)
+    L.check(L.lib().t2p_gemm_skinny(_ptr(a), lda, _ptr(w_kmajor), _ptr(out), ldc, m, k, n, _stream(a.device)), "t2p_gemm_skinny")
+    return out
+
+
+def gemm_tn(a: torch.Tensor, b: torch.Tensor, k1: Optional[int] = None, n: Optional[int] = None, out: Optional[torch.Tensor] = None):
+    """a[M, K1]^T @ b[M, N] -> [K1, N] (t2p_gemm_tn): rows split over the grid, partials added in a fixed order.  The
+    weight-gradient products of the training-mode path (dW = dY^T X, ...): no transposed copy, no library GEMM.
+    Pitches: with k1 / n the operands are the first k1 / n columns of a / b, whose row lengths are the pitches lda / ldb; with
+    `out` ([K1, ldc] float32) the product goes into its first n columns and the others stay as they are."""
+    _need(a, "a", torch.float32, 2)
+    _need(b, "b", torch.float32, 2, a.device)
+    m, lda = a.shape
+    if b.shape[0] != m:
+        raise RuntimeError(f"gemm_tn: a is [{m},{lda}] but b is {tuple(b.shape)}")
+    ldb = b.shape[1]
+    k1, n = lda if k1 is None else int(k1), ldb if n is None else int(n)
+    if not (1 <= k1 <= lda and 1 <= n <= ldb):
+        raise RuntimeError(f"gemm_tn: k1={k1}, n={n} do not fit the operands' rows of {lda} and {ldb}")
+    if out is None:
+        out = torch.empty((k1, n), dtype=torch.float32, device=a.device)
+    elif _need(out, "out", torch.float32, 2, a.device).shape[0] != k1 or out.shape[1] < n:
+        raise RuntimeError(f"gemm_tn: out is {tuple(out.shape)}, the product is [{k1},{n}]")
+    if m == 0:
+        out[:, :n] = 0
+        return out
+    ws = torch.empty((L.lib().t2p_gemm_tn_workspace_bytes(m, k1, n),), dtype=torch.uint8, device=a.device)
+    L.check(L.lib().t2p_gemm_tn(_ptr(a), lda, _ptr(b), ldb, _ptr(out), out.shape[1], m, k1, n, _ptr(ws), ws.numel(),
+                                _stream(a.device)), "t2p_gemm_tn")
+    return out
+
+
+def linear_wgrad(dy: torch.Tensor, x: torch.Tensor, want_colsum: bool = True, k1: Optional[int] = None, n: Optional[int] = None,
+                 out: Optional[torch.Tensor] = None):
     """(dy[M, K1]^T @ x[M, N] -> [K1, N], column sums of dy [K1] or None) in one pass over the rows (t2p_linear_wgrad_f32): the
-    weight and bias gradients of a Linear.  Row pitches must be multiples of 4 floats (the layers of the path are)."""
+    weight and bias gradients of a Linear.  Row pitches must be multiples of 4 floats (the layers of the path are; a whole
+    operand of another width is zero-padded here).  Pitches as in gemm_tn: k1 / n select the first columns of dy / x, whose row
+    lengths are lda / ldb (multiples of 4 then); `out` [K1, ldc] takes the product in its first n columns."""
     _need(dy, "dy", torch.float32, 2)
     _need(x, "x", torch.float32, 2, dy.device)
-    m, k1 = dy.shape
+    m = dy.shape[0]
     if x.shape[0] != m:
-        raise RuntimeError(f"linear_wgrad: dy is [{m},{k1}] but x is {tuple(x.shape)}")
-    n = x.shape[1]
-    if k1 % 4:
+        raise RuntimeError(f"linear_wgrad: dy is [{m},{dy.shape[1]}] but x is {tuple(x.shape)}")
+    pitched = k1 is not None or n is not None
+    k1, n = dy.shape[1] if k1 is None else int(k1), x.shape[1] if n is None else int(n)
+    if not (1 <= k1 <= dy.shape[1] and 1 <= n <= x.shape[1]):
+        raise RuntimeError(f"linear_wgrad: k1={k1}, n={n} do not fit the operands' rows of {dy.shape[1]} and {x.shape[1]}")
+    if pitched and (dy.shape[1] % 4 or x.shape[1] % 4):
+        raise RuntimeError(f"linear_wgrad: pitches {dy.shape[1]} and {x.shape[1]} must be multiples of 4")
+    if dy.shape[1] % 4:
         dy = torch.nn.functional.pad(dy, (0, (-k1) % 4)).contiguous()
-    if n % 4:
+    if x.shape[1] % 4:
         x = torch.nn.functional.pad(x, (0, (-n) % 4)).contiguous()
-    out = torch.empty((k1, n), dtype=torch.float32, device=dy.device)
+    if out is None:
+        out = torch.empty((k1, n), dtype=torch.float32, device=dy.device)
+    elif _need(out, "out", torch.float32, 2, dy.device).shape[0] != k1 or out.shape[1] < n:
+        raise RuntimeError(f"linear_wgrad: out is {tuple(out.shape)}, the product is [{k1},{n}]")
     colsum = torch.empty((k1,), dtype=torch.float32, device=dy.device) if want_colsum else None
     ws = torch.empty((L.lib().t2p_linear_wgrad_workspace_bytes(m, k1, n),), dtype=torch.uint8, device=dy.device)
-    L.check(L.lib().t2p_linear_wgrad_f32(_ptr(dy), dy.shape[1], _ptr(x), x.shape[1], _ptr(out), n, _ptr(colsum), m, k1, n, _ptr(ws),
-                                         ws.numel(), _stream(dy.device)), "t2p_linear_wgrad_f32")
+    L.check(L.lib().t2p_linear_wgrad_f32(_ptr(dy), dy.shape[1], _ptr(x), x.shape[1], _ptr(out), out.shape[1], _ptr(colsum), m, k1, n,
+                                         _ptr(ws), ws.numel(), _stream(dy.device)), "t2p_linear_wgrad_f32")
     return out, colsum
 
 

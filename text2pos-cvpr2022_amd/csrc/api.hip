@@ -1,4 +1,5 @@
-// extern "C" entry points of libt2p_hip.so (see include/t2p.h) and the launch orchestration of the cell branch.
+// Library infrastructure (error text, device caches, opt-in kernel timing) and the extern "C" entry points of libt2p_hip.so
+// (include/t2p.h) other than the cell encoder's (cell_encoder.hip): the text encoder, the LSTM training loops, thin exports.
 #include <stdarg.h>
 #include <stdlib.h>
 #include <math.h>
@@ -107,481 +108,6 @@ ProfScope::~ProfScope() {
     if (slot >= 0) (void)hipEventRecord((hipEvent_t)ev_end, st);
 }
 
-namespace {
-
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
-struct Bump {
-    char* base;
-    size_t off, cap;
-    template <typename T>
-    T* take(size_t n) {
-        off = align_up(off, 256);
-        T* p = (T*)(base ? base + off : nullptr);
-        off += n * sizeof(T);
-        return p;
-    }
-};
-
-// Level geometry for n_pts points: dense/centroid counts, feature widths, hidden widths.
-struct Geo {
-    int nd[3], nc[3];
-    int gp;   // GA max group: SA level 3 writes gp rows per object (the next power of two >= nc[2]; rows past nc[2] repeat the last)
-    static constexpr int H[3] = {32, 128, 256};
-    static constexpr int C[3] = {64, 128, 256};
-    static constexpr int LD[3] = {96, 160, 288};  // SA output row = [C | xyz 0 | 28 pad columns: zero at level 3, never written at levels 1-2 (their readers mask them: k_live)]: K % 32 == 0 for the next GEMM
-    explicit Geo(int n_pts) {
-        nd[0] = n_pts;
-        for (int l = 0; l < 3; l++) {
-            nc[l] = (nd[l] + 1) / 2;
-            if (l < 2) nd[l + 1] = nc[l];
-        }
-        gp = 1;
-        while (gp < nc[2]) gp *= 2;
-    }
-    // f16x3: the specialised SA kernels (LDS centroid table) are built for the level shapes of 256 points per object
-    bool specialised(int l) const {
-        static constexpr int ND[3] = {256, 128, 64}, NC[3] = {128, 64, 32};
-        return nd[l] == ND[l] && nc[l] == NC[l];
-    }
-};
-constexpr int Geo::H[3];
-constexpr int Geo::C[3];
-constexpr int Geo::LD[3];
-
-struct CellWs {
-    GroupTables gt;
-    float *A[3], *B[3], *F[3];
-    float *gh, *f0, *f1, *f2, *cat, *emb, *embn, *P, *Q, *x1, *pool, *l1, *l2;
-    int32_t *knn, *seg_ptr, *first, *prefix[3], *bounds[3];
-    uint32_t* guard;  // [G_SLOTS] fp16-range guard words of the chunk (t2p_common.h)
-};
-
-// rows of GA layer 1's output: n objects x gp rows, rounded up to the 32-row tiles GA layer 2 reads
-int64_t gh_rows(int64_t n, const Geo& g) { return (n * g.gp + 31) / 32 * 32; }
-
-// Carve the per-chunk workspace (n objects, nb cells).  With base == nullptr this only measures.
-size_t carve(Bump& b, int64_t n, int64_t nb, const t2p_cell_config& cfg, CellWs* ws) {
-    Geo g(cfg.n_pts);
-    const int D = cfg.embed_dim;
-    const int nfeat = (cfg.use_class ? 1 : 0) + (cfg.use_color ? 1 : 0) + (cfg.use_position ? 1 : 0);
-    CellWs w{};
-    for (int l = 0; l < 3; l++) {
-        w.gt.n_dense[l] = g.nd[l];
-        w.gt.n_cent[l] = g.nc[l];
-        w.gt.fps_idx[l] = b.take<uint8_t>(n * g.nc[l]);
-        w.gt.nbr[l] = b.take<uint8_t>(n * g.nc[l] * 32);   // only filled when a trace asks for it
-        w.gt.cnt[l] = b.take<uint8_t>(n * g.nc[l]);
-        w.gt.rows[l] = b.take<uint16_t>(n * g.nc[l] * 33);
-        w.gt.n_rows[l] = b.take<uint16_t>(n);
-        w.A[l] = b.take<float>(n * g.nd[l] * Geo::H[l]);
-        w.B[l] = b.take<float>(n * g.nc[l] * Geo::H[l]);
-        w.F[l] = b.take<float>(n * (l == 2 ? g.gp : g.nc[l]) * Geo::LD[l]);
-    }
-    w.gh = b.take<float>(gh_rows(n, g) * 512);
-    w.f0 = b.take<float>(n * 1024);
-    w.f1 = b.take<float>(n * 512);
-    w.f2 = b.take<float>(n * 256);
-    w.cat = b.take<float>(n * (size_t)(nfeat > 0 ? nfeat : 1) * D);
-    w.emb = b.take<float>(n * D);
-    w.embn = b.take<float>(n * D);
-    w.P = b.take<float>(n * D);
-    w.Q = b.take<float>(n * D);
-    w.x1 = b.take<float>(n * D);
-    w.knn = b.take<int32_t>(n * (size_t)cfg.knn_k);
-    w.first = b.take<int32_t>(n);
-    for (int l = 0; l < 3; l++) {
-        w.prefix[l] = b.take<int32_t>(n + 1);
-        w.bounds[l] = b.take<int32_t>(1024 + 1);
-    }
-    w.seg_ptr = b.take<int32_t>(nb + 1);
-    w.guard = b.take<uint32_t>(G_SLOTS);
-    w.pool = b.take<float>(nb * D);
-    w.l1 = b.take<float>(nb * D);
-    w.l2 = b.take<float>(nb * D);
-    if (ws) *ws = w;
-    return align_up(b.off, 256);
-}
-
-// Default chunk: as many objects as the 32-bit table offsets of the SA kernels allow (< 65,536); measured 32,768 / 49,152 /
-// 65,000 objects per chunk: 105.1 / 104.4 / 104.1 ms per 12k-cell step (fewer launches, fewer kernel tails), ~0.6 MB each
-int default_chunk(const t2p_cell_config& cfg) { return cfg.chunk_objects > 0 ? cfg.chunk_objects : T2P_DEFAULT_CHUNK_OBJECTS; }
-
-int check_cfg(const t2p_cell_config* cfg) {
-    T2P_CHECK_ARG(cfg != nullptr, "encode_cells: cfg is NULL");
-    if (cfg->n_pts < 8 || cfg->n_pts > 256) {
-        set_error("encode_cells: n_pts=%d not built (8 <= n_pts <= 256 points per object)", cfg->n_pts);
-        return T2P_E_UNSUPPORTED;
-    }
-    if (cfg->objects_only) {
-        if (cfg->embed_dim < 64 || cfg->embed_dim > 512 || cfg->embed_dim % 64 != 0) {
-            set_error("encode_cells: objects_only supports embed_dim in {64, 128, ..., 512}, got %d", cfg->embed_dim);
-            return T2P_E_UNSUPPORTED;
-        }
-    } else if (cfg->embed_dim != 256 && cfg->embed_dim != 128 && cfg->embed_dim != 384) {
-        set_error("encode_cells: embed_dim=%d not built for the cell head (128, 256, 384; the host pads e.g. 300 to 384)", cfg->embed_dim);
-        return T2P_E_UNSUPPORTED;
-    }
-    T2P_CHECK_ARG(cfg->variation == 0 || cfg->variation == 1, "encode_cells: variation=%d (0 = max, 1 = mean)",
-                  cfg->variation);
-    if (cfg->variation == 1 && cfg->knn_k != 8) {
-        set_error("encode_cells: variation=1 (mean aggregation) is built for knn_k = 8 only, got %d", cfg->knn_k);
-        return T2P_E_UNSUPPORTED;
-    }
-    T2P_CHECK_ARG(cfg->pointnet_features >= 0 && cfg->pointnet_features <= 2, "encode_cells: pointnet_features=%d",
-                  cfg->pointnet_features);
-    T2P_CHECK_ARG(cfg->use_class || cfg->use_color || cfg->use_position, "encode_cells: use_features is empty");
-    T2P_CHECK_ARG(cfg->knn_k >= 1 && cfg->knn_k <= 32, "encode_cells: knn_k=%d outside [1,32]", cfg->knn_k);
-    T2P_CHECK_ARG(cfg->precision == 0 || cfg->precision == 1, "encode_cells: precision=%d (0 = fp32, 1 = f16x3)",
-                  cfg->precision);
-    T2P_CHECK_ARG((cfg->tuning & ~T2P_TUNING_MASK) == 0, "encode_cells: tuning=%#x has bits outside %#x", cfg->tuning, T2P_TUNING_MASK);
-    // 32-bit byte offsets into the per-chunk tables (n_obj * 128 points * 128 floats * 4 B < 2^32) and 16-bit object-local
-    // indices cap a chunk at 65,535 objects; checked here, not deep inside a kernel launcher
-    T2P_CHECK_ARG(cfg->chunk_objects >= 0 && cfg->chunk_objects <= T2P_MAX_CHUNK_OBJECTS,
-                  "encode_cells: chunk_objects=%d outside [0, %d] (0 = default %d); the workspace takes ~0.6 MB per object of a chunk",
-                  cfg->chunk_objects, T2P_MAX_CHUNK_OBJECTS, T2P_DEFAULT_CHUNK_OBJECTS);
-    T2P_CHECK_ARG(!cfg->class_embed || cfg->class_idx != nullptr, "encode_cells: class_embed needs class_idx");
-    T2P_CHECK_ARG(!cfg->color_embed || cfg->color_idx != nullptr, "encode_cells: color_embed needs color_idx");
-    return 0;
-}
-
-template <typename T>
-int copy_trace(T* dst, const T* src, size_t n, hipStream_t st) {
-    if (dst == nullptr || n == 0) return 0;
-    hipError_t e = hipMemcpyAsync(dst, src, n * sizeof(T), hipMemcpyDeviceToDevice, st);
-    if (e != hipSuccess) {
-        set_error("encode_cells: trace copy failed: %s", hipGetErrorString(e));
-        return (int)e;
-    }
-    return 0;
-}
-
-int encode_chunk(const float* xyz, const float* rgb, const float* center, const float* mean_rgb,
-                 const int32_t* cell_ptr_dev /* at first cell of chunk */, int32_t o_lo, int64_t n, int64_t nb,
-                 int max_cell, const t2p_cell_weights& W, const t2p_cell_config& cfg, float* out,
-                 const t2p_cell_trace* tr, int64_t trace_obj0, CellWs& ws, hipStream_t st, bool trunk_only = false) {
-    // trunk_only (t2p_pointnet2_forward): the chunk is ONE cell of n objects (cell_ptr_dev is not read), the run stops behind
-    // lin2 and hands features0 / 1 / 2 back through tr
-    Geo g(cfg.n_pts);
-    const int D = cfg.embed_dim;
-    // fp16-range guard (f16x3 only): the chunk's words are cleared by the first kernel and judged by the last
-    uint32_t* guard = (cfg.precision == 1 && cfg.overflow_flag != nullptr) ? ws.guard : nullptr;
-    auto gslot = [&](int i) -> uint32_t* { return guard ? guard + i : nullptr; };
-    GuardBounds gbounds{};
-    for (int l = 0; l < 3; l++) gbounds.wp_l1[l] = W.sa_wp_l1[l];
-    gbounds.a1_l1 = W.sa_a1_l1;
-    gbounds.a1_bmax = W.sa_b1_absmax;
-    gbounds.ga1_l1 = W.ga_w1_l1;
-    gbounds.ga1_bmax = W.ga_b1_absmax;
-    // f16x3: the SA kernels of the level shapes of 256 points build their centroid tables B_i = W1p pos_i in LDS (sa_points.hip,
-    // sa_rows.hip, sa3.hip); the HBM tables B_l are then neither written nor read.  The stream kernel (ws_sa.hip: fp32, and f16x3 at
-    // the other shapes) gathers its table from HBM.
-    bool lds_btab[3];
-    for (int l = 0; l < 3; l++) lds_btab[l] = cfg.precision == 1 && g.specialised(l);
-    // level 0 runs on sa_points.hip, which computes layer 1 per edge from the points themselves: no point table A_1 either
-    const bool sa1_points = lds_btab[0];
-    if (trunk_only)
-        T2P_TRY(launch_one_cell_index(n, ws.seg_ptr, ws.first, st, guard));
-    else
-        T2P_TRY(launch_cell_index(cell_ptr_dev, (int)nb, o_lo, ws.seg_ptr, ws.first, st, guard));
-    // models/object_encoder.py:86: the PointNet++ only runs when the "class" feature does not come from class_embedding
-    const bool run_pointnet = cfg.use_class && !cfg.class_embed;
-    if (run_pointnet) {
-    ws.gt.self_loops = cfg.self_loops;
-    {
-        GroupTables gt = ws.gt;
-        const bool want_nbr = tr != nullptr && (tr->nbr[0] || tr->nbr[1] || tr->nbr[2] || tr->cnt[0] || tr->cnt[1] || tr->cnt[2]);
-        if (!want_nbr)
-            for (int l = 0; l < 3; l++) gt.nbr[l] = gt.cnt[l] = nullptr;
-        // the layer-1 tables that depend on geometry only are written by the same kernel: B_l = W1p_l pos_i (+ the
-        // [xyz | 0] tail of the F_l rows) for every level, and the K = 6 point table A_1 of level 0
-        for (int l = 0; l < 3; l++) {
-            const int cf = l == 0 ? 3 : Geo::C[l - 1];
-            gt.B[l] = lds_btab[l] ? nullptr : ws.B[l];
-            gt.wp[l] = W.sa_w1[l] + (size_t)cf * Geo::H[l];
-            gt.H[l] = Geo::H[l];
-            gt.tail[l] = ws.F[l];
-            gt.ld_tail[l] = Geo::LD[l];
-            gt.tail_col0[l] = Geo::C[l];
-        }
-        gt.tail_rows[2] = g.gp;
-        gt.A1 = sa1_points ? nullptr : ws.A[0];
-        gt.w1 = W.sa_w1[0];
-        gt.b1 = W.sa_b1[0];
-        gt.rgb = rgb;
-        gt.H1 = Geo::H[0];
-        gt.guard = guard;
-
-        // the launch shapes of the three SA levels (which kernel runs a level decides its row-list form and its balancing)
-        SaParams bp[3] = {};
-        for (int l = 0; l < 3; l++) {
-            bp[l].n_rows = gt.n_rows[l];
-            bp[l].n_obj = n;
-            bp[l].prefix_ws = ws.prefix[l];
-            bp[l].bounds_ws = ws.bounds[l];
-            bp[l].W_x3 = cfg.precision == 1 ? W.sa_w2_x3[l] : nullptr;
-            bp[l].wp = lds_btab[l] ? W.sa_w1[l] : nullptr;   // (non-null = LDS centroid table: selects the launch shape)
-            bp[l].n_dense = g.nd[l];
-            bp[l].n_cent = g.nc[l];
-        }
-        bp[0].w1 = sa1_points ? W.sa_w1[0] : nullptr;
-        // level 2: the centroids FPS repeats once an object's distinct positions are used up share one copy of their edge rows
-        // (GroupTables::share_tail; same bits, -13 % rows on the synthetic cells) where k_sa_rows consumes them
-        for (int l = 0; l < 3; l++) gt.share_tail[l] = sa_shares_tail_rows(l, Geo::H[l], Geo::C[l], bp[l], cfg.n_pts, cfg.tuning) ? 1 : 0;
-
-        // level 0: edges of repeated points leave the row list (same max-aggregate, -36 % SA1 rows on the synthetic cells).
-        // Default: the scan publishes level 0's hit masks and k_build_rows writes the pruned list once; tuning bit 3: the scan
-        // lists every hit and k_dedup_rows prunes the list in place, as before (the same list, bit for bit)
-        const bool prune_l0 = !(cfg.tuning & 1) && cfg.n_pts == 256;
-        gt.mask_l0 = prune_l0 && !(cfg.tuning & 8) && !want_nbr && gt.rows[0] && gt.rows[1] && gt.rows[2] ? 1 : 0;
-        T2P_TRY(launch_sample_group(xyz, n, cfg.n_pts, cfg.radius, gt, st));
-        if (gt.mask_l0)
-            T2P_TRY(launch_build_rows(xyz, rgb, gt.fps_idx[0], n, cfg.n_pts, gt.rows[0], gt.n_rows[0], gt.self_loops, st));
-        else if (prune_l0)
-            T2P_TRY(launch_dedup_rows(xyz, rgb, n, cfg.n_pts, gt.rows[0], gt.n_rows[0], g.nc[0], st));
-        // the per-centroid row counts of all three levels exist now: cut every level's balanced object ranges at once
-        T2P_TRY(launch_sa_balance_levels(bp, Geo::H, Geo::C, st));
-    }
-
-    // ---- three set-abstraction levels -----------------------------------------------------------------------
-    for (int l = 0; l < 3; l++) {
-        const int H = Geo::H[l], C = Geo::C[l];
-        const int cf = l == 0 ? 3 : Geo::C[l - 1];  // feature columns in front of the xyz columns
-        const float* pos_src = l == 0 ? xyz : ws.F[l - 1];
-        const int ld_pos = l == 0 ? 3 : Geo::LD[l - 1];
-        const int pos_col0 = l == 0 ? 0 : Geo::C[l - 1];
-        // layer-1 point table A_j = W1 [x_j | pos_j] + b1
-        if (l != 0) {  // (level 0: written by k_sample_group)
-            WsParams p{};
-            p.A = ws.F[l - 1];
-            p.lda = Geo::LD[l - 1];
-            p.k_live = Geo::C[l - 1] + 4;   // [features | xyz 0]; the pad columns behind are never written
-            p.W = W.sa_w1[l];
-            p.W_x3 = cfg.precision == 1 ? W.sa_w1_x3[l] : nullptr;
-            p.ldw = H;
-            p.bias = W.sa_b1[l];
-            p.out = ws.A[l];
-            p.ldo = H;
-            p.relu = 0;
-            p.M = n * g.nd[l];
-            p.amax_out = gslot(l == 1 ? G_A2 : G_A3);
-            T2P_TRY(launch_ws(WS_DENSE_STORE, Geo::LD[l - 1] - (cfg.precision == 1 ? 16 : 0), H, p, st));  // (f16x3: K stops at C + 16)
-        }
-        // per-edge ReLU(A_j - B_i) -> layer 2 -> max per centroid
-        SaParams p{};
-        p.A = ws.A[l];
-        p.Bc = ws.B[l];
-        p.wp = lds_btab[l] ? W.sa_w1[l] + (size_t)cf * Geo::H[l] : nullptr;
-        p.W = W.sa_w2[l];
-        p.W_x3 = cfg.precision == 1 ? W.sa_w2_x3[l] : nullptr;
-        p.bias = cfg.precision == 1 ? W.sa_b2_x3[l] : W.sa_b2[l];
-        p.out_scale = cfg.precision == 1 ? 1.0f / W.sa_w2_scale[l] : 1.0f;
-        p.out = ws.F[l];
-        p.ldo = Geo::LD[l];
-        p.rows = ws.gt.rows[l];
-        p.n_rows = ws.gt.n_rows[l];
-        p.first = ws.first;
-        p.fps_idx = ws.gt.fps_idx[l];
-        p.pos_src = pos_src;
-        p.ld_pos = ld_pos;
-        p.pos_col0 = pos_col0;
-        if (l == 0 && sa1_points) {
-            p.feat_src = rgb;
-            p.w1 = W.sa_w1[0];
-            p.b1 = W.sa_b1[0];
-        }
-        p.n_dense = g.nd[l];
-        p.n_cent = g.nc[l];
-        p.n_obj = n;
-        p.prefix_ws = ws.prefix[l];
-        p.bounds_ws = ws.bounds[l];
-        p.balanced = 1;
-        p.amax_out = gslot(G_F1 + l);
-        if (l == 2) p.out_rows = g.gp;
-        T2P_TRY(launch_ws_sa(H, C, p, st));
-    }
-    // ---- global abstraction: [x | pos] -> 512 -> 1024, max over the object's nc[2] points (gp rows, the padding repeats one) ---
-    {
-        WsParams p{};
-        p.A = ws.F[2];
-        p.lda = Geo::LD[2];
-        p.W = W.ga_w1;
-        p.W_x3 = cfg.precision == 1 ? W.ga_w1_x3 : nullptr;
-        p.ldw = 512;
-        p.bias = W.ga_b1;
-        p.out = ws.gh;
-        // f16x3: GA1 hands its ReLU output to GA2 already split into fp16 hi / lo planes (same bytes as fp32), so the
-        // eight column-slice workgroups of GA2 stage it with plain 16-byte copies instead of re-splitting it 8 times
-        _Float16* gh_hi = (_Float16*)ws.gh;
-        _Float16* gh_lo = gh_hi + (size_t)gh_rows(n, g) * 512;
-        if (cfg.precision == 1) {
-            p.out_hi = gh_hi;
-            p.out_lo = gh_lo;
-            p.amax_out = gslot(G_GA_H);
-        }
-        p.ldo = 512;
-        p.relu = 1;
-        p.M = n * g.gp;
-        T2P_TRY(launch_ws(WS_DENSE_STORE, Geo::LD[2] - (cfg.precision == 1 ? 16 : 0), 512, p, st));
-        WsParams q{};
-        q.A = ws.gh;
-        if (cfg.precision == 1) {
-            q.A_hi = gh_hi;
-            q.A_lo = gh_lo;
-        }
-        q.lda = 512;
-        q.W = W.ga_w2;
-        q.W_x3 = cfg.precision == 1 ? W.ga_w2_x3 : nullptr;
-        q.ldw = 1024;
-        q.bias = W.ga_b2;
-        q.out = ws.f0;
-        q.ldo = 1024;
-        q.relu = 1;
-        q.M = n * g.gp;
-        q.group_rows = g.gp;
-        T2P_TRY(launch_ws(WS_DENSE_GROUPMAX, 512, 1024, q, st));
-    }
-    // ---- PointNet2 heads + ObjectEncoder ------------------------------------------------------------------------
-    if (cfg.precision == 1 && W.lin1_x3 && W.lin2_x3) {
-        T2P_TRY(launch_gemm_x3(ws.f0, 1024, W.lin1_x3, W.lin1_scale, W.lin1_b, ws.f1, 512, 0, n, 1024, 512, 1, st, nullptr, 0, gslot(G_PN_F0)));
-        T2P_TRY(launch_gemm_x3(ws.f1, 512, W.lin2_x3, W.lin2_scale, W.lin2_b, ws.f2, 256, 0, n, 512, 256, 1, st, nullptr, 0, gslot(G_PN_F1)));
-    } else {
-        T2P_TRY(launch_gemm(ws.f0, 1024, W.lin1_w, W.lin1_b, ws.f1, 512, 0, n, 1024, 512, 1, st));
-        T2P_TRY(launch_gemm(ws.f1, 512, W.lin2_w, W.lin2_b, ws.f2, 256, 0, n, 512, 256, 1, st));
-    }
-    }  // run_pointnet
-    if (trunk_only) {
-        T2P_TRY(copy_trace(tr->features0, ws.f0, (size_t)n * 1024, st));
-        T2P_TRY(copy_trace(tr->features1, ws.f1, (size_t)n * 512, st));
-        T2P_TRY(copy_trace(tr->features2, ws.f2, (size_t)n * 256, st));
-        T2P_TRY(launch_guard_check(guard, cfg.overflow_flag, gbounds, st));
-        return 0;
-    }
-    const int nfeat = (cfg.use_class ? 1 : 0) + (cfg.use_color ? 1 : 0) + (cfg.use_position ? 1 : 0);
-    const int ldcat = nfeat * D;
-    int slot = 0;
-    if (cfg.use_class && cfg.class_embed) {
-        T2P_TRY(launch_gather_rownorm(W.class_embedding, cfg.class_idx + o_lo, n, D, ws.cat, ldcat, slot * D, st));
-        slot++;
-    } else if (cfg.use_class) {
-        const float* fin = cfg.pointnet_features == 0 ? ws.f0 : (cfg.pointnet_features == 1 ? ws.f1 : ws.f2);
-        const int kin = cfg.pointnet_features == 0 ? 1024 : (cfg.pointnet_features == 1 ? 512 : 256);
-        // mlp_pointnet into P (scratch), then F.normalize into the concat slot
-        if (cfg.precision == 1 && W.pn_x3)
-            T2P_TRY(launch_gemm_x3(fin, kin, W.pn_x3, W.pn_scale, W.pn_b, ws.P, D, 0, n, kin, D, 1, st, nullptr, 0,
-                                          gslot(G_PN_F0 + cfg.pointnet_features)));
-        else
-            T2P_TRY(launch_gemm(fin, kin, W.pn_w, W.pn_b, ws.P, D, 0, n, kin, D, 1, st));
-        T2P_TRY(launch_rownorm(ws.P, D, n, D, ws.cat, ldcat, slot * D, st));
-        slot++;
-    }
-    if (cfg.use_color && cfg.color_embed) {
-        T2P_TRY(launch_gather_rownorm(W.color_embedding, cfg.color_idx + o_lo, n, D, ws.cat, ldcat, slot * D, st));
-        slot++;
-    } else if (cfg.use_color) {
-        T2P_TRY(launch_mlp3_norm(mean_rgb, n, W.col_w1, W.col_b1, W.col_w2, W.col_b2, D, ws.cat, ldcat, slot * D, st));
-        slot++;
-    }
-    if (cfg.use_position) {
-        T2P_TRY(launch_mlp3_norm(center, n, W.pos_w1, W.pos_b1, W.pos_w2, W.pos_b2, D, ws.cat, ldcat, slot * D, st));
-        slot++;
-    }
-    const float* emb = ws.cat;  // single feature: embeddings[0] is returned un-merged (object_encoder.py:137-140)
-    if (nfeat > 1) {
-        if (cfg.precision == 1 && W.merge_x3)
-            T2P_TRY(launch_gemm_x3(ws.cat, ldcat, W.merge_x3, W.merge_scale, W.merge_b, ws.emb, D, 0, n, ldcat, D, 1, st, nullptr, 0, gslot(G_GEMM_IN)));
-        else
-            T2P_TRY(launch_gemm(ws.cat, ldcat, W.merge_w, W.merge_b, ws.emb, D, 0, n, ldcat, D, 1, st));
-        emb = ws.emb;
-    }
-    if (cfg.objects_only) {  // the fine stage consumes ObjectEncoder.forward's output as is
-        T2P_TRY(copy_trace(tr->obj_emb + trace_obj0 * D, emb, (size_t)n * D, st));
-        T2P_TRY(launch_guard_check(guard, cfg.overflow_flag, gbounds, st));
-        return 0;
-    }
-    // ---- cell head: normalize, DynamicEdgeConv(k, max), global max pool, lin, normalize -------------------------
-    T2P_TRY(launch_rownorm(emb, D, n, D, ws.embn, D, 0, st));
-    if (cfg.precision == 1 && W.g_wp_x3 && W.g_wq_x3) {
-        T2P_TRY(launch_gemm_x3(ws.embn, D, W.g_wp_x3, W.g_wp_scale, W.g_bp, ws.P, D, 0, n, D, D, 0, st, nullptr, 0, gslot(G_GEMM_IN)));
-        T2P_TRY(launch_gemm_x3(ws.embn, D, W.g_wq_x3, W.g_wq_scale, nullptr, ws.Q, D, 0, n, D, D, 0, st, nullptr, 0, gslot(G_GEMM_IN)));
-    } else {
-        T2P_TRY(launch_gemm(ws.embn, D, W.g_wp, W.g_bp, ws.P, D, 0, n, D, D, 0, st));
-        T2P_TRY(launch_gemm(ws.embn, D, W.g_wq, nullptr, ws.Q, D, 0, n, D, D, 0, st));
-    }
-    T2P_TRY(launch_knn(ws.embn, D, ws.seg_ptr, (int)nb, max_cell, cfg.knn_k, ws.knn, st));
-    {
-        WsParams p{};
-        p.A = ws.Q;
-        p.lda = D;
-        p.Bc = ws.P;
-        p.W = W.g_w2;
-        p.W_x3 = cfg.precision == 1 ? W.g_w2_x3 : nullptr;   // f16x3 image of layer 2 (absent: fp32 MFMA)
-        p.amax_out = gslot(G_EDGE);                                         // (here: the rows this kernel splits itself)
-        p.ldw = D;
-        p.bias = W.g_b2;
-        p.out = ws.x1;
-        p.ldo = D;
-        p.relu = 1;
-        // small calls (the reference's 64-cell batches: ~1,000 objects = 31 groups of 32 on 256 CUs): groups of 8 destinations
-        p.knn_group = (n + 31) / 32 < num_cus() ? 8 : 32;
-        p.n_groups = (n + p.knn_group - 1) / p.knn_group;
-        p.knn_idx = ws.knn;
-        p.knn_k = cfg.knn_k;
-        p.n_dst = n;
-        p.mean = cfg.variation == 1;  // cell_retrieval.py:50-54: DynamicEdgeConv(aggr="mean") + global_mean_pool
-        T2P_TRY(launch_ws(WS_EDGE_KNN, D, D, p, st));
-    }
-    T2P_TRY(launch_segmax(ws.x1, D, ws.seg_ptr, (int)nb, ws.pool, cfg.variation == 1, st));
-    T2P_TRY(launch_gemm(ws.pool, D, W.lin_w1, W.lin_b1, ws.l1, D, 0, nb, D, D, 1, st));
-    T2P_TRY(launch_gemm(ws.l1, D, W.lin_w2, W.lin_b2, ws.l2, D, 0, nb, D, D, 1, st));
-    T2P_TRY(launch_rownorm(ws.l2, D, nb, D, out, D, 0, st));
-    T2P_TRY(launch_guard_check(guard, cfg.overflow_flag, gbounds, st));
-
-    if (tr && run_pointnet) {
-        for (int l = 0; l < 3; l++) {
-            T2P_TRY(copy_trace(tr->fps_idx[l] ? tr->fps_idx[l] + trace_obj0 * g.nc[l] : nullptr, ws.gt.fps_idx[l],
-                               (size_t)n * g.nc[l], st));
-            T2P_TRY(copy_trace(tr->nbr[l] ? tr->nbr[l] + trace_obj0 * g.nc[l] * 32 : nullptr, ws.gt.nbr[l],
-                               (size_t)n * g.nc[l] * 32, st));
-            T2P_TRY(copy_trace(tr->cnt[l] ? tr->cnt[l] + trace_obj0 * g.nc[l] : nullptr, ws.gt.cnt[l],
-                               (size_t)n * g.nc[l], st));
-            if (tr->sa_out[l] && n > 0) {   // [features | xyz 0] of every row; the pad columns behind are left as the caller set them
-                const int rows = l == 2 ? g.gp : g.nc[l];   // (level 3: the gp - nc[2] padding rows of an object stay behind)
-                const size_t ld = Geo::LD[l] * sizeof(float);
-                hipError_t e = hipSuccess;
-                if (rows == g.nc[l])
-                    e = hipMemcpy2DAsync(tr->sa_out[l] + trace_obj0 * g.nc[l] * Geo::LD[l], ld, ws.F[l], ld, (Geo::C[l] + 4) * sizeof(float),
-                                         (size_t)n * g.nc[l], hipMemcpyDeviceToDevice, st);
-                for (int c = 0; rows != g.nc[l] && c < g.nc[l] && e == hipSuccess; c++)   // centroid c of every object
-                    e = hipMemcpy2DAsync(tr->sa_out[l] + (trace_obj0 * g.nc[l] + c) * Geo::LD[l], g.nc[l] * ld, ws.F[l] + (size_t)c * Geo::LD[l],
-                                         rows * ld, (Geo::C[l] + 4) * sizeof(float), (size_t)n, hipMemcpyDeviceToDevice, st);
-                if (e != hipSuccess) {
-                    set_error("encode_cells: trace copy failed: %s", hipGetErrorString(e));
-                    return (int)e;
-                }
-            }
-        }
-        T2P_TRY(copy_trace(tr->features0 ? tr->features0 + trace_obj0 * 1024 : nullptr, ws.f0, (size_t)n * 1024, st));
-        T2P_TRY(copy_trace(tr->features1 ? tr->features1 + trace_obj0 * 512 : nullptr, ws.f1, (size_t)n * 512, st));
-        T2P_TRY(copy_trace(tr->features2 ? tr->features2 + trace_obj0 * 256 : nullptr, ws.f2, (size_t)n * 256, st));
-    }
-    if (tr) {
-        T2P_TRY(copy_trace(tr->obj_emb ? tr->obj_emb + trace_obj0 * D : nullptr, emb, (size_t)n * D, st));
-        // knn indices are chunk-local object rows; tests use a single chunk or add the chunk offset themselves
-        T2P_TRY(copy_trace(tr->knn_idx ? tr->knn_idx + trace_obj0 * cfg.knn_k : nullptr, ws.knn,
-                           (size_t)n * cfg.knn_k, st));
-    }
-    return 0;
-}
-
-// Whole cells per chunk, at most `chunk` objects (a single larger cell still forms its own chunk).
-int64_t next_chunk_end(const int32_t* cp, int64_t c0, int64_t n_cells, int chunk) {
-    int64_t c1 = c0 + 1;
-    while (c1 < n_cells && (cp[c1 + 1] - cp[c0]) <= chunk) c1++;
-    return c1;
-}
-
-}  // namespace
 }  // namespace t2p
 
 using namespace t2p;
@@ -635,105 +161,6 @@ int t2p_profile_report(char* buf, size_t n) {
 }
 const char* t2p_last_error(void) { return g_err; }
 
-size_t t2p_encode_cells_workspace_bytes(int64_t n_obj, int64_t n_cells, const t2p_cell_config* cfg) {
-    if (cfg == nullptr || n_obj <= 0) return 256;
-    // a chunk holds at most max(chunk_objects, largest cell) objects; the caller may not know the largest cell here,
-    // so size for min(n_obj, chunk) and let t2p_encode_cells re-check against the actual partition.
-    int64_t n = default_chunk(*cfg);
-    if (n > n_obj) n = n_obj;
-    int64_t nb = n_cells < n ? n_cells : n;
-    Bump b{nullptr, 0, 0};
-    return carve(b, n, nb > 0 ? nb : 1, *cfg, nullptr) + 256;
-}
-
-int t2p_encode_cells(const float* xyz, const float* rgb, const float* center, const float* mean_rgb,
-                     const int32_t* cell_ptr_host, const int32_t* cell_ptr, int64_t n_obj, int64_t n_cells,
-                     const t2p_cell_weights* w, const t2p_cell_config* cfg, float* out, const t2p_cell_trace* trace,
-                     void* workspace, size_t workspace_bytes, t2p_stream_t stream) {
-    hipStream_t st = (hipStream_t)stream;
-    T2P_TRY(check_cfg(cfg));
-    T2P_CHECK_ARG(w != nullptr && cell_ptr_host != nullptr && cell_ptr != nullptr, "encode_cells: NULL argument");
-    T2P_CHECK_ARG(n_cells >= 0 && n_obj >= 0, "encode_cells: negative size");
-    if (n_cells == 0) return 0;  // an empty batch has no output rows (and its buffers may be NULL)
-    if (cfg->objects_only)
-        T2P_CHECK_ARG(trace != nullptr && trace->obj_emb != nullptr, "encode_cells: objects_only needs trace->obj_emb");
-    else
-        T2P_CHECK_ARG(out != nullptr, "encode_cells: out is NULL");
-    T2P_CHECK_ARG(!cfg->class_embed || w->class_embedding != nullptr, "encode_cells: class_embedding weights missing");
-    T2P_CHECK_ARG(!cfg->color_embed || w->color_embedding != nullptr, "encode_cells: color_embedding weights missing");
-    if (cfg->precision == 1)
-        T2P_CHECK_ARG(w->sa_w2_x3[0] && w->sa_w2_x3[1] && w->sa_w2_x3[2] && w->sa_b2_x3[0] && w->sa_b2_x3[1] &&
-                          w->sa_b2_x3[2] && w->sa_w2_scale[0] > 0.f && w->sa_w2_scale[1] > 0.f && w->sa_w2_scale[2] > 0.f &&
-                          w->sa_w1_x3[1] && w->sa_w1_x3[2] &&
-                          w->ga_w1_x3 && w->ga_w2_x3,
-                      "encode_cells: precision = f16x3 needs the packed *_x3 weight images");
-    if (cfg->precision == 1 && cfg->overflow_flag != nullptr)
-        T2P_CHECK_ARG(w->ga_w1_l1 > 0.f && w->ga_b1_absmax >= 0.f && w->sa_a1_l1 > 0.f && w->sa_wp_l1[0] >= 0.f,
-                      "encode_cells: the fp16-range guard needs the weight norms of t2p_cell_weights (packing.py)");
-    T2P_CHECK_ARG(cell_ptr_host[0] == 0 && cell_ptr_host[n_cells] == n_obj,
-                  "encode_cells: cell_ptr must start at 0 and end at n_obj=%lld (got %d..%d)", (long long)n_obj,
-                  cell_ptr_host[0], cell_ptr_host[n_cells]);
-    for (int64_t c = 0; c < n_cells; c++)
-        T2P_CHECK_ARG(cell_ptr_host[c + 1] > cell_ptr_host[c],
-                      "encode_cells: cell %lld is empty (the reference asserts >= 1 object per cell, "
-                      "dataloading/kitti360pose/utils.py:108)", (long long)c);
-    T2P_CHECK_ARG((((uintptr_t)xyz | (uintptr_t)rgb | (uintptr_t)workspace) & 15) == 0,
-                  "encode_cells: xyz, rgb and workspace must be 16-byte aligned");
-    const int chunk = default_chunk(*cfg);
-    for (int64_t c0 = 0; c0 < n_cells;) {
-        const int64_t c1 = next_chunk_end(cell_ptr_host, c0, n_cells, chunk);
-        const int32_t o_lo = cell_ptr_host[c0], o_hi = cell_ptr_host[c1];
-        const int64_t n = o_hi - o_lo, nb = c1 - c0;
-        int max_cell = 0;
-        for (int64_t c = c0; c < c1; c++) {
-            const int m = cell_ptr_host[c + 1] - cell_ptr_host[c];
-            max_cell = m > max_cell ? m : max_cell;
-        }
-        T2P_CHECK_ARG(n <= T2P_MAX_CHUNK_OBJECTS,
-                      "encode_cells: cell %lld alone holds %lld objects; a chunk (whole cells) is limited to %d objects",
-                      (long long)c0, (long long)n, T2P_MAX_CHUNK_OBJECTS);
-        Bump b{(char*)workspace, 0, workspace_bytes};
-        CellWs ws;
-        const size_t need = carve(b, n, nb, *cfg, &ws);
-        if (need > workspace_bytes) {
-            set_error("encode_cells: workspace %zu B < %zu B needed for a chunk of %lld objects / %lld cells",
-                      workspace_bytes, need, (long long)n, (long long)nb);
-            return T2P_E_WORKSPACE;
-        }
-        const int64_t P3 = (int64_t)cfg->n_pts * 3;
-        T2P_TRY(encode_chunk(xyz + o_lo * P3, rgb + o_lo * P3, center + (int64_t)o_lo * 3, mean_rgb + (int64_t)o_lo * 3,
-                             cell_ptr + c0, o_lo, n, nb, max_cell, *w, *cfg, out ? out + c0 * cfg->embed_dim : nullptr, trace, o_lo, ws,
-                             st));
-        c0 = c1;
-    }
-    return 0;
-}
-
-// ---- PointNet++ as a classifier of its own (models/pointcloud/pointnet2.py:80-100) ------------------------------------------
-// The trunk-only configuration the chunk runner is driven with: the caller's geometry / precision / guard / tuning, everything
-// behind lin2 at the values that make carve() and check_cfg() happy (those stages do not run).
-static t2p_cell_config trunk_cfg(const t2p_cell_config& in) {
-    t2p_cell_config c{};
-    c.n_pts = in.n_pts;
-    c.embed_dim = 256;
-    c.pointnet_features = 2;
-    c.use_class = 1;
-    c.self_loops = in.self_loops;
-    c.knn_k = 8;
-    for (int l = 0; l < 3; l++) c.radius[l] = in.radius[l];
-    c.precision = in.precision;
-    c.overflow_flag = in.overflow_flag;
-    c.tuning = in.tuning;
-    return c;
-}
-
-size_t t2p_pointnet2_workspace_bytes(int64_t n_obj, const t2p_cell_config* cfg) {
-    if (cfg == nullptr || n_obj <= 0) return 256;
-    const t2p_cell_config c = trunk_cfg(*cfg);
-    Bump b{nullptr, 0, 0};
-    return carve(b, n_obj, 1, c, nullptr) + 256;
-}
-
 int t2p_classifier_heads(const float* features2, const float* head_w, const float* head_b, int64_t n, int32_t n_classes,
                          int32_t n_colors, float* class_pred, float* color_pred, t2p_stream_t stream) {
     T2P_CHECK_ARG(features2 && head_w && head_b && class_pred && color_pred, "classifier_heads: NULL argument");
@@ -752,56 +179,6 @@ int t2p_softmax_xent(const float* logits, int32_t ld_logits, const int32_t* labe
     T2P_CHECK_ARG(n >= 0 && n_classes >= 1, "softmax_xent: n=%lld, n_classes=%d", (long long)n, n_classes);
     T2P_CHECK_ARG(ld_logits >= n_classes && ld_d >= n_classes, "softmax_xent: row pitch below n_classes=%d", n_classes);
     return launch_softmax_xent(logits, ld_logits, labels, n, n_classes, row_loss, d_logits, ld_d, correct, (hipStream_t)stream);
-}
-
-int t2p_pointnet2_forward(const float* xyz, const float* rgb, int64_t n_obj, const t2p_cell_weights* w, const t2p_cell_config* cfg,
-                          const float* head_w, const float* head_b, int32_t n_classes, int32_t n_colors, float* features0,
-                          float* features1, float* features2, float* class_pred, float* color_pred, void* workspace,
-                          size_t workspace_bytes, t2p_stream_t stream) {
-    hipStream_t st = (hipStream_t)stream;
-    T2P_CHECK_ARG(cfg != nullptr && w != nullptr, "pointnet2_forward: NULL argument");
-    const t2p_cell_config c = trunk_cfg(*cfg);
-    T2P_TRY(check_cfg(&c));
-    T2P_CHECK_ARG(n_obj >= 0, "pointnet2_forward: negative size");
-    T2P_CHECK_ARG(n_obj <= T2P_MAX_CHUNK_OBJECTS,
-                  "pointnet2_forward: %lld objects in one batch; the batch is one cell, limited to %d objects", (long long)n_obj,
-                  T2P_MAX_CHUNK_OBJECTS);
-    const bool heads = head_w != nullptr;
-    if (heads) {
-        T2P_CHECK_ARG(head_b != nullptr && class_pred != nullptr && color_pred != nullptr,
-                      "pointnet2_forward: the heads need head_b, class_pred and color_pred");
-        if (n_classes < 1 || n_classes > 64 || n_colors < 1 || n_colors > 64) {
-            set_error("pointnet2_forward: n_classes=%d / n_colors=%d outside [1, 64]", n_classes, n_colors);
-            return T2P_E_UNSUPPORTED;
-        }
-    }
-    if (n_obj == 0) return 0;
-    T2P_CHECK_ARG(xyz != nullptr && rgb != nullptr && workspace != nullptr, "pointnet2_forward: NULL argument");
-    if (c.precision == 1)
-        T2P_CHECK_ARG(w->sa_w2_x3[0] && w->sa_w2_x3[1] && w->sa_w2_x3[2] && w->sa_b2_x3[0] && w->sa_b2_x3[1] && w->sa_b2_x3[2] &&
-                          w->sa_w2_scale[0] > 0.f && w->sa_w2_scale[1] > 0.f && w->sa_w2_scale[2] > 0.f && w->sa_w1_x3[1] &&
-                          w->sa_w1_x3[2] && w->ga_w1_x3 && w->ga_w2_x3,
-                      "pointnet2_forward: precision = f16x3 needs the packed *_x3 weight images");
-    if (c.precision == 1 && c.overflow_flag != nullptr)
-        T2P_CHECK_ARG(w->ga_w1_l1 > 0.f && w->ga_b1_absmax >= 0.f && w->sa_a1_l1 > 0.f && w->sa_wp_l1[0] >= 0.f,
-                      "pointnet2_forward: the fp16-range guard needs the weight norms of t2p_cell_weights (packing.py)");
-    T2P_CHECK_ARG((((uintptr_t)xyz | (uintptr_t)rgb | (uintptr_t)workspace) & 15) == 0,
-                  "pointnet2_forward: xyz, rgb and workspace must be 16-byte aligned");
-    Bump b{(char*)workspace, 0, workspace_bytes};
-    CellWs ws;
-    const size_t need = carve(b, n_obj, 1, c, &ws);
-    if (need > workspace_bytes) {
-        set_error("pointnet2_forward: workspace %zu B < %zu B needed for %lld objects", workspace_bytes, need, (long long)n_obj);
-        return T2P_E_WORKSPACE;
-    }
-    t2p_cell_trace tr{};
-    tr.features0 = features0;
-    tr.features1 = features1;
-    tr.features2 = features2;
-    T2P_TRY(encode_chunk(xyz, rgb, nullptr, nullptr, nullptr, 0, n_obj, 1, (int)n_obj, *w, c, nullptr, &tr, 0, ws, st, true));
-    if (heads)   // (on the workspace's copy of features2: the caller need not ask for it)
-        T2P_TRY(launch_classifier_heads(ws.f2, head_w, head_b, n_obj, n_classes, n_colors, class_pred, color_pred, st));
-    return 0;
 }
 
 size_t t2p_encode_text_workspace_bytes(int64_t batch, int32_t vocab, int32_t embed_dim) {
@@ -1033,87 +410,6 @@ int t2p_sim_topk(const float* queries, const float* cells, int64_t nq, int64_t n
                   "sim_topk: NULL argument");
     return launch_sim_topk(queries, cells, nq, nc, dim, k, index_offset, out_idx, out_score, workspace, workspace_bytes,
                            (hipStream_t)stream);
-}
-
-int t2p_sample_group(const float* xyz, int64_t n_obj, int32_t n_pts, const float* radius_host,
-                     uint8_t* const* fps_idx, uint8_t* const* nbr, uint8_t* const* cnt, t2p_stream_t stream) {
-    T2P_CHECK_ARG(xyz && radius_host && fps_idx && nbr && cnt, "sample_group: NULL argument");
-    Geo g(n_pts);
-    GroupTables gt{};
-    gt.self_loops = 0;
-    for (int l = 0; l < 3; l++) {
-        gt.fps_idx[l] = fps_idx[l];
-        gt.nbr[l] = nbr[l];
-        gt.cnt[l] = cnt[l];
-        gt.rows[l] = nullptr;
-        gt.n_rows[l] = nullptr;
-        gt.n_dense[l] = g.nd[l];
-        gt.n_cent[l] = g.nc[l];
-    }
-    return launch_sample_group(xyz, n_obj, n_pts, radius_host, gt, (hipStream_t)stream);
-}
-
-int t2p_group_rows(const float* xyz, int64_t n_obj, int32_t n_pts, const float* radius_host, int32_t self_loops,
-                   uint8_t* const* fps_idx, uint16_t* const* rows, uint16_t* const* n_rows, t2p_stream_t stream) {
-    T2P_CHECK_ARG(xyz && radius_host && fps_idx && rows && n_rows, "group_rows: NULL argument");
-    Geo g(n_pts);
-    GroupTables gt{};
-    gt.self_loops = self_loops ? 1 : 0;
-    for (int l = 0; l < 3; l++) {
-        T2P_CHECK_ARG(fps_idx[l] && rows[l] && n_rows[l], "group_rows: NULL table of level %d", l);
-        gt.fps_idx[l] = fps_idx[l];
-        gt.rows[l] = rows[l];
-        gt.n_rows[l] = n_rows[l];
-        gt.n_dense[l] = g.nd[l];
-        gt.n_cent[l] = g.nc[l];
-    }
-    return launch_sample_group(xyz, n_obj, n_pts, radius_host, gt, (hipStream_t)stream);
-}
-
-int t2p_group_rows_shared(const float* xyz, int64_t n_obj, int32_t n_pts, const float* radius_host, int32_t self_loops,
-                          int32_t share_mask, uint8_t* const* fps_idx, uint16_t* const* rows, uint16_t* const* n_rows,
-                          t2p_stream_t stream) {
-    T2P_CHECK_ARG(xyz && radius_host && fps_idx && rows && n_rows, "group_rows_shared: NULL argument");
-    T2P_CHECK_ARG((share_mask & ~2) == 0, "group_rows_shared: share_mask=%#x (bit 1: SA level 2; no other level has a shared form)", share_mask);
-    T2P_CHECK_ARG(share_mask == 0 || n_pts == 256, "group_rows_shared: shared lists exist for 256 points per object (n_pts = %d)", n_pts);
-    Geo g(n_pts);
-    GroupTables gt{};
-    gt.self_loops = self_loops ? 1 : 0;
-    for (int l = 0; l < 3; l++) {
-        T2P_CHECK_ARG(fps_idx[l] && rows[l] && n_rows[l], "group_rows_shared: NULL table of level %d", l);
-        gt.fps_idx[l] = fps_idx[l];
-        gt.rows[l] = rows[l];
-        gt.n_rows[l] = n_rows[l];
-        gt.n_dense[l] = g.nd[l];
-        gt.n_cent[l] = g.nc[l];
-        gt.share_tail[l] = (share_mask >> l) & 1;
-    }
-    return launch_sample_group(xyz, n_obj, n_pts, radius_host, gt, (hipStream_t)stream);
-}
-
-int t2p_group_rows_built(const float* xyz, const float* rgb, int64_t n_obj, int32_t n_pts, const float* radius_host,
-                         int32_t self_loops, int32_t share_mask, uint8_t* const* fps_idx, uint16_t* const* rows,
-                         uint16_t* const* n_rows, t2p_stream_t stream) {
-    T2P_CHECK_ARG(xyz && rgb && radius_host && fps_idx && rows && n_rows, "group_rows_built: NULL argument");
-    T2P_CHECK_ARG(n_obj >= 0, "group_rows_built: negative size");
-    T2P_CHECK_ARG((share_mask & ~2) == 0, "group_rows_built: share_mask=%#x (bit 1: SA level 2; no other level has a shared form)", share_mask);
-    T2P_CHECK_ARG(n_pts == 256, "group_rows_built: built for 256 points per object (n_pts = %d)", n_pts);
-    Geo g(n_pts);
-    GroupTables gt{};
-    gt.self_loops = self_loops ? 1 : 0;
-    for (int l = 0; l < 3; l++) {
-        T2P_CHECK_ARG(fps_idx[l] && rows[l] && n_rows[l], "group_rows_built: NULL table of level %d", l);
-        gt.fps_idx[l] = fps_idx[l];
-        gt.rows[l] = rows[l];
-        gt.n_rows[l] = n_rows[l];
-        gt.n_dense[l] = g.nd[l];
-        gt.n_cent[l] = g.nc[l];
-        gt.share_tail[l] = (share_mask >> l) & 1;
-    }
-    gt.mask_l0 = 1;
-    T2P_CHECK_ARG((((uintptr_t)xyz | (uintptr_t)rgb | (uintptr_t)rows[0]) & 15) == 0, "group_rows_built: xyz, rgb and rows[0] must be 16-byte aligned");
-    T2P_TRY(launch_sample_group(xyz, n_obj, n_pts, radius_host, gt, (hipStream_t)stream));
-    return launch_build_rows(xyz, rgb, gt.fps_idx[0], n_obj, n_pts, gt.rows[0], gt.n_rows[0], gt.self_loops, (hipStream_t)stream);
 }
 
 int t2p_edge_counts(const uint16_t* rows, const uint16_t* n_rows, const int32_t* first_obj, int64_t n_obj, int32_t n_dense,

@@ -92,6 +92,20 @@ int matrix_wgs(); // workgroups of the persistent matrix kernels (= num_cus() un
 // lock; returns 0 or the hipError_t (message kept for t2p_last_error)
 int reserve_lds(const void* kernel, size_t bytes, const char* what);
 
+// Caller-provided workspaces are carved by bumping a 256-byte-aligned offset; base == nullptr only measures
+inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+struct Bump {
+    char* base;
+    size_t off, cap;
+    template <typename T>
+    T* take(size_t n) {
+        off = align_up(off, 256);
+        T* p = (T*)(base ? base + off : nullptr);
+        off += n * sizeof(T);
+        return p;
+    }
+};
+
 // ---- fp16-range guard of the f16x3 path -------------------------------------------------------------------------
 // The split-precision path converts fp32 activations to fp16 (hi = fp16(v) to nearest: a value past 65504 would
 // become inf).  Every kernel that performs such a conversion reports the largest magnitude it converted into one
@@ -278,6 +292,14 @@ int launch_gemm_skinny(const float* A, int lda, const float* W, float* C, int ld
 int launch_gemm_x3(const float* A, int lda, const void* Wx, float scale, const float* bias, float* C, int ldc, int c0,
                    int64_t M, int K, int N, int relu, hipStream_t st, const float* resid = nullptr, int ldr = 0,
                    uint32_t* amax_in = nullptr /* f16x3 guard word for the rows of A */);
+// One dense layer's weights: the k-major fp32 matrix w, or (x3 != nullptr) its pack_gemm_x3 image and the image's scale.  The
+// path is chosen where the descriptor is built; every call site is one launch_dense (amax_in goes to the f16x3 kernel only).
+struct DenseW { const float* w; const void* x3; float scale; };   // x3 == nullptr: fp32-MFMA path
+inline int launch_dense(const float* A, int lda, const DenseW& W, const float* bias, float* C, int ldc, int c0, int64_t M, int K, int N,
+                        int relu, hipStream_t st, const float* resid = nullptr, int ldr = 0, uint32_t* amax_in = nullptr) {
+    if (W.x3 != nullptr) return launch_gemm_x3(A, lda, W.x3, W.scale, bias, C, ldc, c0, M, K, N, relu, st, resid, ldr, amax_in);
+    return launch_gemm(A, lda, W.w, bias, C, ldc, c0, M, K, N, relu, st, resid, ldr);
+}
 
 // tg_gemm_tn.hip: C[K1, N] = A[M, K1]^T B[M, N], rows split over the grid + fixed-order reduction (training-mode gradients)
 size_t gemm_tn_workspace_bytes(int64_t M, int K1, int N);

@@ -161,6 +161,37 @@ _overlap_memo, _stream_sets, _handed_out, _spin_memo = {}, {}, {}, {}
 
 
 # ---------------------------------------------------------------------------------------------------------------
+def _level_geometry(n_pts: int):
+    """[(n_dense, n_cent)] of the three SA levels: every level keeps ceil(n_dense / 2) centroids, the next level's points."""
+    levels, nd = [], n_pts
+    for _ in range(3):
+        levels.append((nd, (nd + 1) // 2))
+        nd = levels[-1][1]
+    return levels
+
+
+# per-level tables of k_sample_group and of the encoder's trace: shape from (n_obj, n_cent, level), dtype
+_LEVEL_TABLES = {
+    "fps_idx": (lambda n, nc, l: (n, nc), torch.uint8),
+    "nbr": (lambda n, nc, l: (n, nc, 32), torch.uint8),
+    "cnt": (lambda n, nc, l: (n, nc), torch.uint8),
+    "rows": (lambda n, nc, l: (n, nc * 33), torch.int16),      # uint16 bits
+    "n_rows": (lambda n, nc, l: (n,), torch.int16),
+    "sa_out": (lambda n, nc, l: (n * nc, (64, 128, 256)[l] + 32), torch.float32),
+}
+
+
+def _level_tables(n_obj: int, n_pts: int, device, names, alloc=torch.empty):
+    """One tensor per level for each name of _LEVEL_TABLES, and their addresses as the void*[3] arrays of the C ABI."""
+    tables = {name: [alloc(_LEVEL_TABLES[name][0](n_obj, nc, l), dtype=_LEVEL_TABLES[name][1], device=device)
+                     for l, (_, nc) in enumerate(_level_geometry(n_pts))] for name in names}
+    return tables, {name: (C.c_void_p * 3)(*[t.data_ptr() for t in ts]) for name, ts in tables.items()}
+
+
+def _radius(radius):
+    return (C.c_float * 3)(*[float(v) for v in radius])
+
+
 def sample_group(xyz: torch.Tensor, radius=(0.2, 0.3, 0.4)):
     """Fused FPS + ball query of the three SA levels.  xyz [n_obj, n_pts, 3] fp32.
     Returns dict(fps_idx=[3 x uint8 [n_obj, n_c]], nbr=[3 x uint8 [n_obj, n_c, 32]], cnt=[3 x uint8 [n_obj, n_c]])."""
@@ -168,16 +199,8 @@ def sample_group(xyz: torch.Tensor, radius=(0.2, 0.3, 0.4)):
     n_obj, n_pts, three = xyz.shape
     if three != 3:
         raise RuntimeError(f"xyz: last dimension must be 3, got {three}")
-    nd, out = n_pts, dict(fps_idx=[], nbr=[], cnt=[])
-    for _ in range(3):
-        nc = (nd + 1) // 2
-        out["fps_idx"].append(torch.empty((n_obj, nc), dtype=torch.uint8, device=xyz.device))
-        out["nbr"].append(torch.empty((n_obj, nc, 32), dtype=torch.uint8, device=xyz.device))
-        out["cnt"].append(torch.empty((n_obj, nc), dtype=torch.uint8, device=xyz.device))
-        nd = nc
-    arr = lambda ts: (C.c_void_p * 3)(*[t.data_ptr() for t in ts])
-    r = (C.c_float * 3)(*[float(v) for v in radius])
-    L.check(L.lib().t2p_sample_group(_ptr(xyz), n_obj, n_pts, r, arr(out["fps_idx"]), arr(out["nbr"]), arr(out["cnt"]),
+    out, arr = _level_tables(n_obj, n_pts, xyz.device, ("fps_idx", "nbr", "cnt"))
+    L.check(L.lib().t2p_sample_group(_ptr(xyz), n_obj, n_pts, _radius(radius), arr["fps_idx"], arr["nbr"], arr["cnt"],
                                      _stream(xyz.device)), "t2p_sample_group")
     return out
 
@@ -195,38 +218,29 @@ def group_edges(xyz: torch.Tensor, first_obj: torch.Tensor, radius=(0.2, 0.3, 0.
     n_obj, n_pts, three = xyz.shape
     if three != 3 or first_obj.numel() != n_obj:
         raise RuntimeError("group_edges: xyz must be [n_obj, n_pts, 3] and first_obj [n_obj]")
-    nds, ncs, fps, rows, n_rows = [], [], [], [], []
-    nd = n_pts
-    for _ in range(3):
-        nc = (nd + 1) // 2
-        nds.append(nd)
-        ncs.append(nc)
-        fps.append(torch.empty((n_obj, nc), dtype=torch.uint8, device=dev))
-        rows.append(torch.empty((n_obj, nc * 33), dtype=torch.int16, device=dev))
-        n_rows.append(torch.empty((n_obj,), dtype=torch.int16, device=dev))
-        nd = nc
-    arr = lambda ts: (C.c_void_p * 3)(*[t.data_ptr() for t in ts])
-    r = (C.c_float * 3)(*[float(v) for v in radius])
+    levels = _level_geometry(n_pts)
+    t, arr = _level_tables(n_obj, n_pts, dev, ("fps_idx", "rows", "n_rows"))
+    rows, n_rows = t["rows"], t["n_rows"]
     st = _stream(dev)
-    L.check(L.lib().t2p_group_rows(_ptr(xyz), n_obj, n_pts, r, int(bool(self_loops)), arr(fps), arr(rows), arr(n_rows), st),
-            "t2p_group_rows")
+    L.check(L.lib().t2p_group_rows(_ptr(xyz), n_obj, n_pts, _radius(radius), int(bool(self_loops)), arr["fps_idx"], arr["rows"],
+                                   arr["n_rows"], st), "t2p_group_rows")
     cent_ptrs = []
-    for l in range(3):
-        counts = torch.empty((n_obj * ncs[l],), dtype=torch.int32, device=dev)
-        L.check(L.lib().t2p_edge_counts(_ptr(rows[l]), _ptr(n_rows[l]), _ptr(first_obj), n_obj, nds[l], ncs[l],
+    for l, (nd, nc) in enumerate(levels):
+        counts = torch.empty((n_obj * nc,), dtype=torch.int32, device=dev)
+        L.check(L.lib().t2p_edge_counts(_ptr(rows[l]), _ptr(n_rows[l]), _ptr(first_obj), n_obj, nd, nc,
                                         int(bool(self_loops)), _ptr(counts), st), "t2p_edge_counts")
-        cp = torch.zeros((n_obj * ncs[l] + 1,), dtype=torch.int32, device=dev)
+        cp = torch.zeros((n_obj * nc + 1,), dtype=torch.int32, device=dev)
         torch.cumsum(counts, 0, dtype=torch.int32, out=cp[1:])
         cent_ptrs.append(cp)
     totals = torch.stack([cp[-1] for cp in cent_ptrs]).cpu().tolist()      # the one read-back
     out = []
-    for l in range(3):
+    for l, (nd, nc) in enumerate(levels):
         e = int(totals[l])
         src = torch.empty((e,), dtype=torch.int32, device=dev)
         dst = torch.empty((e,), dtype=torch.int32, device=dev)
-        L.check(L.lib().t2p_edge_expand(_ptr(rows[l]), _ptr(n_rows[l]), _ptr(first_obj), _ptr(cent_ptrs[l]), n_obj, nds[l], ncs[l],
+        L.check(L.lib().t2p_edge_expand(_ptr(rows[l]), _ptr(n_rows[l]), _ptr(first_obj), _ptr(cent_ptrs[l]), n_obj, nd, nc,
                                         int(bool(self_loops)), _ptr(src), _ptr(dst), st), "t2p_edge_expand")
-        out.append(dict(fps_idx=fps[l], src=src, dst=dst, cent_ptr=cent_ptrs[l], n_dense=nds[l], n_cent=ncs[l]))
+        out.append(dict(fps_idx=t["fps_idx"][l], src=src, dst=dst, cent_ptr=cent_ptrs[l], n_dense=nd, n_cent=nc))
     return out
 
 
@@ -240,17 +254,9 @@ def group_rows(xyz: torch.Tensor, radius=(0.2, 0.3, 0.4), self_loops: bool = Tru
     n_obj, n_pts, three = xyz.shape
     if three != 3:
         raise RuntimeError(f"xyz: last dimension must be 3, got {three}")
-    nd, out = n_pts, dict(fps_idx=[], rows=[], n_rows=[])
-    for _ in range(3):
-        nc = (nd + 1) // 2
-        out["fps_idx"].append(torch.empty((n_obj, nc), dtype=torch.uint8, device=dev))
-        out["rows"].append(torch.empty((n_obj, nc * 33), dtype=torch.int16, device=dev))
-        out["n_rows"].append(torch.empty((n_obj,), dtype=torch.int16, device=dev))
-        nd = nc
-    arr = lambda ts: (C.c_void_p * 3)(*[t.data_ptr() for t in ts])
-    r = (C.c_float * 3)(*[float(v) for v in radius])
-    L.check(L.lib().t2p_group_rows_shared(_ptr(xyz), n_obj, n_pts, r, int(bool(self_loops)), int(share_mask), arr(out["fps_idx"]),
-                                          arr(out["rows"]), arr(out["n_rows"]), _stream(dev)), "t2p_group_rows_shared")
+    out, arr = _level_tables(n_obj, n_pts, dev, ("fps_idx", "rows", "n_rows"))
+    L.check(L.lib().t2p_group_rows_shared(_ptr(xyz), n_obj, n_pts, _radius(radius), int(bool(self_loops)), int(share_mask),
+                                          arr["fps_idx"], arr["rows"], arr["n_rows"], _stream(dev)), "t2p_group_rows_shared")
     return out
 
 
@@ -264,17 +270,9 @@ def group_rows_built(xyz: torch.Tensor, rgb: torch.Tensor, radius=(0.2, 0.3, 0.4
     n_obj, n_pts, three = xyz.shape
     if three != 3 or tuple(rgb.shape) != tuple(xyz.shape):
         raise RuntimeError(f"group_rows_built: xyz and rgb must both be [n_obj, n_pts, 3], got {tuple(xyz.shape)} and {tuple(rgb.shape)}")
-    nd, out = n_pts, dict(fps_idx=[], rows=[], n_rows=[])
-    for _ in range(3):
-        nc = (nd + 1) // 2
-        out["fps_idx"].append(torch.empty((n_obj, nc), dtype=torch.uint8, device=dev))
-        out["rows"].append(torch.empty((n_obj, nc * 33), dtype=torch.int16, device=dev))
-        out["n_rows"].append(torch.empty((n_obj,), dtype=torch.int16, device=dev))
-        nd = nc
-    arr = lambda ts: (C.c_void_p * 3)(*[t.data_ptr() for t in ts])
-    r = (C.c_float * 3)(*[float(v) for v in radius])
-    L.check(L.lib().t2p_group_rows_built(_ptr(xyz), _ptr(rgb), n_obj, n_pts, r, int(bool(self_loops)), int(share_mask),
-                                         arr(out["fps_idx"]), arr(out["rows"]), arr(out["n_rows"]), _stream(dev)), "t2p_group_rows_built")
+    out, arr = _level_tables(n_obj, n_pts, dev, ("fps_idx", "rows", "n_rows"))
+    L.check(L.lib().t2p_group_rows_built(_ptr(xyz), _ptr(rgb), n_obj, n_pts, _radius(radius), int(bool(self_loops)), int(share_mask),
+                                         arr["fps_idx"], arr["rows"], arr["n_rows"], _stream(dev)), "t2p_group_rows_built")
     return out
 
 
@@ -616,18 +614,10 @@ def encode_cells(xyz, rgb, center, mean_rgb, cell_ptr_host: np.ndarray, cell_ptr
             raise RuntimeError(f"encode_cells: unknown trace outputs {sorted(unknown)}")
         tr = L.CellTrace()
         trace = {}
-        shapes, nd = [], n_pts
-        for c in (64, 128, 256):
-            nc = (nd + 1) // 2
-            shapes.append((nc, c))
-            nd = nc
-        per_level = {"fps_idx": lambda nc, c: ((n_obj, nc), torch.uint8), "nbr": lambda nc, c: ((n_obj, nc, 32), torch.uint8),
-                     "cnt": lambda nc, c: ((n_obj, nc), torch.uint8),
-                     "sa_out": lambda nc, c: ((n_obj * nc, c + 32), torch.float32)}
-        for name, fn in per_level.items():
-            if name in names:
-                trace[name] = [torch.zeros(fn(nc, c)[0], dtype=fn(nc, c)[1], device=dev) for nc, c in shapes]
-                setattr(tr, name, (C.c_void_p * 3)(*[t.data_ptr() for t in trace[name]]))
+        per_level, arr = _level_tables(n_obj, n_pts, dev, [k for k in ("fps_idx", "nbr", "cnt", "sa_out") if k in names], torch.zeros)
+        trace.update(per_level)
+        for name in per_level:
+            setattr(tr, name, arr[name])
         flat = {"features0": ((n_obj, 1024), torch.float32), "features1": ((n_obj, 512), torch.float32),
                 "features2": ((n_obj, 256), torch.float32), "obj_emb": ((n_obj, D), torch.float32),
                 "knn_idx": ((n_obj, cfg.knn_k), torch.int32)}

@@ -2,7 +2,7 @@
 layout as models/superglue_matcher.py::SuperGlueMatch (incl. the un-used `superglue.kenc.*` parameters, so that whole
 checkpoints load with strict=True), with the arithmetic executed by libt2p_hip.so on an MI355X:
 
-  ObjectEncoder.forward (models/object_encoder.py:61-142)   -> t2p_encode_cells(objects_only)   (csrc/api.hip)
+  ObjectEncoder.forward (models/object_encoder.py:61-142)   -> t2p_encode_cells(objects_only)   (csrc/cell_encoder.hip)
   LanguageEncoder per hint sentence (models/modules.py:59-92) -> t2p_encode_text                (csrc/lstm.hip)
   SuperGlue.forward + mlp_offsets (models/superglue.py:239-330, models/superglue_matcher.py:116) -> t2p_match (csrc/match.hip)
 

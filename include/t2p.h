@@ -445,6 +445,21 @@ size_t t2p_sim_topk_workspace_bytes(int64_t nq, int64_t nc, int32_t k);
 int t2p_sim_topk(const float* queries, const float* cells, int64_t nq, int64_t nc, int32_t dim, int32_t k,
                  int64_t index_offset, int64_t* out_idx, double* out_score, void* workspace, size_t workspace_bytes,
                  t2p_stream_t stream);
+/* Group-restricted retrieval: the street oracle of the reference's evaluation (evaluation/pipeline.py:93-108: float64
+ * scores of a query against the whole database, `scores[cell_street_indices != pose_street_idx] = -np.inf`, then
+ * `argsort(-scores)[:k]`).  The arguments of t2p_sim_topk plus query_group [nq] and cell_group [nc] (int32, any values:
+ * only equality matters; cell_group is indexed like `cells`, index_offset shifts only the indices written out; nothing is
+ * read past cell_group[nc - 1]).  Workspace: t2p_sim_topk_workspace_bytes(nq, nc, k), the same as the unrestricted call.
+ *   effective score  s'(q, c) = cell_group[c] == query_group[q] ? s(q, c) : -inf, s = t2p_sim_topk's score bit for bit.
+ *   The mask is a select, not arithmetic: a masked pair is -inf whatever its product was, NaN included.
+ *   The result is the first k entries of the same order on s' (score descending, ties to the lower cell index): a query
+ *   whose group holds fewer than k cells gets its group's cells first, then masked cells with score -inf in ascending
+ *   index - what argsort on the masked array gives under the pinned tie rule.  An allowed cell whose score is NaN is never
+ *   retrieved; nc < k fills the tail with -1 / -inf.  Same k range, widths, alignment rules and two selection paths as
+ *   t2p_sim_topk; a NULL group pointer (with nq > 0 / nc > 0) is T2P_E_ARG, nothing launched. */
+int t2p_sim_topk_grouped(const float* queries, const float* cells, const int32_t* query_group, const int32_t* cell_group,
+                         int64_t nq, int64_t nc, int32_t dim, int32_t k, int64_t index_offset, int64_t* out_idx,
+                         double* out_score, void* workspace, size_t workspace_bytes, t2p_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Opt-in kernel timing for bench.py: when enabled, every kernel launch of the calls above is bracketed by hipEvents

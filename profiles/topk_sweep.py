@@ -2,6 +2,9 @@
 # tensors: one JSON line per (shape, k).  Device events around `--calls` back-to-back calls, median over `--steps` such windows
 # after `--warmup` of them; the per-kernel split comes from a separate profiled call (ops.profile_report), outside the timed windows.
 #   python profiles/topk_sweep.py [--shapes 1000x12000,1250x100000] [--ks 10,16,17,32,100,256,1024] [--steps 9] [--warmup 3]
+# --groups G adds the group-restricted call (t2p_sim_topk_grouped; cells and queries uniform over G ids) timed in windows that
+# alternate with windows of the unrestricted call: `grouped_ms` and the per-pair ratios grouped / unrestricted.
+# --skip-torch leaves the float64 GEMM + topk yardstick out (A/B runs of two builds of the library: T2P_LIB).
 import argparse
 import json
 import os
@@ -31,6 +34,25 @@ def timed(fn, steps, warmup, calls):
     return float(np.median(ms)), min(ms), max(ms)
 
 
+def timed_pairs(fn_a, fn_b, steps, warmup, calls):
+    """Windows of fn_a and fn_b in alternation: (median ms of a, median ms of b, per-pair ratios b / a)."""
+    def window(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(calls):
+            fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1) / calls
+    a_ms, b_ms = [], []
+    for i in range(warmup + steps):
+        ta, tb = window(fn_a), window(fn_b)
+        if i >= warmup:
+            a_ms.append(ta)
+            b_ms.append(tb)
+    return float(np.median(a_ms)), float(np.median(b_ms)), [b / a for a, b in zip(a_ms, b_ms)]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", default="1000x12000,1250x100000")
@@ -39,6 +61,8 @@ def main():
     ap.add_argument("--steps", type=int, default=9)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--calls", type=int, default=0, help="calls per timed window (0: 20 for the small shape, 3 above 10^8 scores)")
+    ap.add_argument("--groups", type=int, default=0, help="also time the group-restricted call with this many group ids")
+    ap.add_argument("--skip-torch", action="store_true", help="do not time torch's float64 GEMM + topk")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "topk_sweep needs cuda:0: there is no CPU path to time"
     dev = torch.device("cuda:0")
@@ -49,9 +73,27 @@ def main():
         q = torch.nn.functional.normalize(torch.randn(nq, a.dim, generator=g), dim=-1).to(dev)
         calls = a.calls or (20 if nq * nc <= 10 ** 8 else 3)
         cd, qd = c.double(), q.double()      # (the yardstick's conversion is not in its time)
+        if a.groups:
+            cg = torch.randint(0, a.groups, (nc,), generator=g).to(torch.int32).to(dev)
+            qg = torch.randint(0, a.groups, (nq,), generator=g).to(torch.int32).to(dev)
         for k in (int(x) for x in a.ks.split(",")):
             med, lo, hi = timed(lambda: t2p.retrieve_topk(c, q, k), a.steps, a.warmup, calls)
-            t_med, t_lo, t_hi = timed(lambda: (qd @ cd.T).topk(k), a.steps, a.warmup, calls)
+            t_med, t_lo, t_hi = (0.0, 0.0, 0.0) if a.skip_torch else timed(lambda: (qd @ cd.T).topk(k), a.steps, a.warmup, calls)
+            grouped = {}
+            if a.groups:
+                u_ms, g_ms, ratios = timed_pairs(lambda: t2p.retrieve_topk(c, q, k),
+                                                 lambda: t2p.retrieve_topk(c, q, k, cell_groups=cg, query_groups=qg),
+                                                 a.steps, a.warmup, calls)
+                ops.profile_report()
+                ops.profile_enable(True)
+                try:
+                    t2p.retrieve_topk(c, q, k, cell_groups=cg, query_groups=qg)
+                finally:
+                    ops.profile_enable(False)
+                grouped = dict(groups=a.groups, paired_ungrouped_ms=round(u_ms, 4), grouped_ms=round(g_ms, 4),
+                               ratio_median=round(float(np.median(ratios)), 4), ratio_min=round(min(ratios), 4),
+                               ratio_max=round(max(ratios), 4),
+                               grouped_kernels={n: dict(launches=cnt, ms=round(ms, 4)) for n, (cnt, ms) in ops.profile_report().items()})
             idx, score = t2p.retrieve_topk(c, q, k)
             want = (qd @ cd.T).topk(k)
             torch.cuda.synchronize()
@@ -66,7 +108,7 @@ def main():
                                   ms=round(med, 4), ms_min=round(lo, 4), ms_max=round(hi, 4),
                                   torch_f64_gemm_topk_ms=round(t_med, 4), torch_min=round(t_lo, 4), torch_max=round(t_hi, 4),
                                   kernels=kernels, workspace_bytes=int(ops.L.lib().t2p_sim_topk_workspace_bytes(nq, nc, k)),
-                                  max_score_diff_vs_torch=float((score - want.values).abs().max()))), flush=True)
+                                  max_score_diff_vs_torch=float((score - want.values).abs().max()), **grouped)), flush=True)
         del c, q, cd, qd
 
 

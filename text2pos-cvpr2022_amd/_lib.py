@@ -79,6 +79,8 @@ SYMBOLS = {
     "t2p_sim_topk_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int32]),
     "t2p_sim_topk": (C.c_int, [c_void, c_void, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int64, c_void, c_void,
                                c_void, C.c_size_t, c_void]),
+    "t2p_sim_topk_grouped": (C.c_int, [c_void, c_void, c_void, c_void, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int64,
+                                       c_void, c_void, c_void, C.c_size_t, c_void]),
     "t2p_lstm_cell_forward": (C.c_int, [c_void, c_void, c_void, c_void, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                         c_void, c_void, c_void, c_void, c_void, c_void]),
     "t2p_lstm_train_forward": (C.c_int, [c_void, c_void, c_void, c_void, C.c_int64, C.c_int32, C.c_int32, C.c_int32, c_void, c_void,

@@ -412,6 +412,17 @@ int t2p_sim_topk(const float* queries, const float* cells, int64_t nq, int64_t n
                            (hipStream_t)stream);
 }
 
+int t2p_sim_topk_grouped(const float* queries, const float* cells, const int32_t* query_group, const int32_t* cell_group,
+                         int64_t nq, int64_t nc, int32_t dim, int32_t k, int64_t index_offset, int64_t* out_idx,
+                         double* out_score, void* workspace, size_t workspace_bytes, t2p_stream_t stream) {
+    T2P_CHECK_ARG(nq >= 0 && nc >= 0, "sim_topk_grouped: negative size");
+    T2P_CHECK_ARG((queries != nullptr || nq == 0) && (cells != nullptr || nc == 0) &&
+                      ((out_idx != nullptr && out_score != nullptr) || nq == 0 || k < 1),
+                  "sim_topk_grouped: NULL argument");
+    return launch_sim_topk_grouped(queries, cells, query_group, cell_group, nq, nc, dim, k, index_offset, out_idx, out_score,
+                                   workspace, workspace_bytes, (hipStream_t)stream);
+}
+
 int t2p_edge_counts(const uint16_t* rows, const uint16_t* n_rows, const int32_t* first_obj, int64_t n_obj, int32_t n_dense,
                     int32_t n_cent, int32_t self_loops, int32_t* counts, t2p_stream_t stream) {
     T2P_CHECK_ARG(n_obj >= 0 && (n_obj == 0 || (rows && n_rows && first_obj && counts)), "edge_counts: NULL argument");

@@ -18,6 +18,10 @@
 // the number of keys above it, an ascending-index sweep with a scan collects everything above and the lowest-index ties,
 // and a bitonic sort in LDS puts the k candidates into better() order.  Queries go through in chunks whose score tile
 // stays within 256 MiB (the Infinity Cache: the select passes re-read what the score kernel just wrote).
+//
+// t2p_sim_topk_grouped (the street oracle, evaluation/pipeline.py:93-108: `scores[cell_street != pose_street] = -inf` before the
+// argsort) is the same two paths with GROUPED product kernels: the epilogue selects -inf for a pair whose group ids differ.  Merge and
+// select already order -inf entries (after every finite score, lowest cell index first), so they are shared as they are.
 #include "t2p_common.h"
 
 namespace t2p {
@@ -29,6 +33,7 @@ constexpr int KMAX = 1024;   // largest supported k (the select kernel's LDS can
 constexpr int QB = 128;      // queries per workgroup (4 waves x 2 tiles x 16)
 constexpr int CB = 32;       // cells staged per iteration
 typedef double f64x2 __attribute__((ext_vector_type(2)));
+typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 struct Cand {
     double s;
@@ -39,14 +44,23 @@ __device__ __forceinline__ bool better(double s, int i, double s2, int i2) { ret
 // D layout of v_mfma_f64_16x16x4_f64: column (query) = lane & 15, row (cell) = (lane >> 4) + 4 * reg
 __device__ __forceinline__ int d_row(int lane, int reg) { return (lane >> 4) + 4 * reg; }
 
+// A lane of the product loop owns cells cell0 + (lane >> 4) + 4 r of a 16-cell tile; where its four values are kept side by
+// side, cell c sits at tile_pos(c) = (c & ~15) | (c & 3) << 2 | (c >> 2) & 3 (the two 2-bit fields swapped; its own inverse).
+__device__ __forceinline__ int tile_pos(int c) { return (c & ~15) | ((c & 3) << 2) | ((c >> 2) & 3); }
+
 // The product loop of both paths: a workgroup of 4 waves keeps queries [q0_wg, q0_wg + QB) as MFMA B operands in registers
 // (wave w: two 16-query tiles from q0_wg + 32 w), streams cells [c_begin, c_end) through c_lds in CB-row blocks
 // (register-prefetched) and hands every finished 16 x 16 tile to epi(t, cell0, acc): lane `lane` holds, for query
 // q0_wg + 32 w + 16 t + (lane & 15), the scores of cells cell0 + d_row(lane, r) in acc[r], r = 0..3 (cells >= c_end are
 // products with zero rows; the epilogue drops them).  One fp64 fma chain over dim per pair, the same whatever the epilogue.
-template <int DIM, class Epi>
+// GROUPED (t2p_sim_topk_grouped): the block's CB group ids travel with its rows - one register of the first CB threads,
+// prefetched under the same cell < c_end guard (nothing is read past cell_group[c_end - 1]), stored to g_lds at tile_pos so
+// that a lane's four cells sit side by side - and epi receives them as cg[r] (ids of cells >= c_end are 0 and unused).
+// Without GROUPED cell_group / g_lds are not touched and cg is a constant the epilogues ignore.
+template <int DIM, bool GROUPED, class Epi>
 __device__ __forceinline__ void sim_product_loop(const float* __restrict__ Q, const float* __restrict__ Cm, int64_t nq,
-                                                 int64_t q0_wg, int64_t c_begin, int64_t c_end, float* c_lds, Epi&& epi) {
+                                                 int64_t q0_wg, int64_t c_begin, int64_t c_end, float* c_lds,
+                                                 const int32_t* __restrict__ cell_group, int* g_lds, Epi&& epi) {
     constexpr int LDC = DIM + 4;
     constexpr int KQ = DIM / 4;   // k per lane group (lane>>4 owns k in [g*KQ, (g+1)*KQ))
     constexpr int F4 = CB * DIM / 4 / 256;
@@ -68,7 +82,11 @@ __device__ __forceinline__ void sim_product_loop(const float* __restrict__ Q, co
     }
 
     f32x4 stage[F4];
+    int gstage = 0;
     auto load_block = [&](int64_t cb) {
+        if constexpr (GROUPED) {
+            if (tid < CB) gstage = (cb + tid) < c_end ? cell_group[cb + tid] : 0;
+        }
 #pragma unroll
         for (int it = 0; it < F4; it++) {
             const int qd = it * 256 + tid;
@@ -78,6 +96,9 @@ __device__ __forceinline__ void sim_product_loop(const float* __restrict__ Q, co
         }
     };
     auto store_block = [&]() {
+        if constexpr (GROUPED) {
+            if (tid < CB) g_lds[tile_pos(tid)] = gstage;
+        }
 #pragma unroll
         for (int it = 0; it < F4; it++) {
             const int qd = it * 256 + tid;
@@ -108,18 +129,29 @@ __device__ __forceinline__ void sim_product_loop(const float* __restrict__ Q, co
                         acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(ad, (double)qreg[t][s4 * 4 + e], acc[t], 0, 0, 0);
                 }
             }
+            i32x4 cg = {0, 0, 0, 0};
+            if constexpr (GROUPED) cg = *(const i32x4*)(g_lds + ct * 16 + g4 * 4);   // == tile_pos(ct * 16 + d_row(lane, r)), r = 0..3
 #pragma unroll
-            for (int t = 0; t < 2; t++) epi(t, cb + ct * 16, acc[t]);
+            for (int t = 0; t < 2; t++) epi(t, cb + ct * 16, acc[t], cg);
         }
         __syncthreads();
     }
 }
 
-template <int DIM>
+// GROUPED: a pair whose groups differ enters the lists as (-inf, cell) - a select on the finished score, so the allowed pairs'
+// bits are those of the ungrouped kernel; the lists start at (-inf, 0x7fffffff), so masked cells fill what the group leaves.
+template <int DIM, bool GROUPED>
 __global__ __launch_bounds__(256, 1) void k_sim_partial(const float* __restrict__ Q, const float* __restrict__ Cm,
+                                                         const int32_t* __restrict__ query_group,
+                                                         const int32_t* __restrict__ cell_group,
                                                          int64_t nq, int64_t nc, int cells_per_split,
                                                          double* __restrict__ ps, int* __restrict__ pi, int n_split) {
     __shared__ __attribute__((aligned(16))) float c_lds[CB * (DIM + 4)];
+    int* g_lds = nullptr;
+    if constexpr (GROUPED) {
+        __shared__ __attribute__((aligned(16))) int g_buf[CB];
+        g_lds = g_buf;
+    }
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g4 = lane >> 4, l15 = lane & 15;
     const int64_t q0 = (int64_t)blockIdx.x * QB + wave * 32;
     const int split = blockIdx.y;
@@ -132,12 +164,21 @@ __global__ __launch_bounds__(256, 1) void k_sim_partial(const float* __restrict_
     for (int t = 0; t < 2; t++)
 #pragma unroll
         for (int j = 0; j < KCAP; j++) { ls[t][j] = -INFINITY; li[t][j] = 0x7fffffff; }
+    int qgrp[2] = {0, 0};
+    if constexpr (GROUPED) {
+#pragma unroll
+        for (int t = 0; t < 2; t++) {
+            const int64_t q = q0 + t * 16 + l15;
+            if (q < nq) qgrp[t] = query_group[q];
+        }
+    }
 
-    sim_product_loop<DIM>(Q, Cm, nq, (int64_t)blockIdx.x * QB, c_begin, c_end, c_lds, [&](int t, int64_t cell0, const f64x4& acc) {
+    sim_product_loop<DIM, GROUPED>(Q, Cm, nq, (int64_t)blockIdx.x * QB, c_begin, c_end, c_lds, cell_group, g_lds,
+                                   [&](int t, int64_t cell0, const f64x4& acc, const i32x4& cg) {
 #pragma unroll
         for (int r = 0; r < 4; r++) {
             const int64_t cell = cell0 + d_row(lane, r);
-            const double s = acc[r];
+            const double s = (!GROUPED || cg[r] == qgrp[t]) ? acc[r] : -INFINITY;
             const int ci = (int)cell;
             if (cell < c_end && better(s, ci, ls[t][KCAP - 1], li[t][KCAP - 1])) {
                 ls[t][KCAP - 1] = s;
@@ -205,28 +246,46 @@ __global__ __launch_bounds__(256) void k_topk_merge(const double* __restrict__ p
 }
 
 // ---- k in (KREG, KMAX]: score tile + exact selection ---------------------------------------------------------------------
-// Score tile of a query chunk: row q holds ld_s (a multiple of 16) doubles.  A lane of the product loop owns cells
-// cell0 + (lane >> 4) + 4 r of a 16-cell tile; it stores its four scores side by side, so cell c of a row sits at
-// tile_pos(c) = (c & ~15) | (c & 3) << 2 | (c >> 2) & 3 (the two 2-bit fields swapped; its own inverse) and the four lane
-// groups of a query fill one 128-byte line.
-__device__ __forceinline__ int tile_pos(int c) { return (c & ~15) | ((c & 3) << 2) | ((c >> 2) & 3); }
+// Score tile of a query chunk: row q holds ld_s (a multiple of 16) doubles.  A lane stores its four scores side by side, so
+// cell c of a row sits at tile_pos(c) and the four lane groups of a query fill one 128-byte line.
 
-template <int DIM>
+// GROUPED: a pair whose groups differ is written as -inf (score_key(-inf) > 0: k_topk_select retrieves it after every
+// finite score, lowest index first).
+template <int DIM, bool GROUPED>
 __global__ __launch_bounds__(256, 1) void k_sim_scores(const float* __restrict__ Q, const float* __restrict__ Cm,
+                                                        const int32_t* __restrict__ query_group,
+                                                        const int32_t* __restrict__ cell_group,
                                                         int64_t nq, int64_t nc, int cells_per_split,
                                                         double* __restrict__ S, int64_t ld_s) {
     __shared__ __attribute__((aligned(16))) float c_lds[CB * (DIM + 4)];
+    int* g_lds = nullptr;
+    if constexpr (GROUPED) {
+        __shared__ __attribute__((aligned(16))) int g_buf[CB];
+        g_lds = g_buf;
+    }
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g4 = lane >> 4, l15 = lane & 15;
     const int64_t q0 = (int64_t)blockIdx.x * QB + wave * 32;
     const int64_t c_begin = (int64_t)blockIdx.y * cells_per_split;
     const int64_t c_end = (c_begin + cells_per_split) < nc ? (c_begin + cells_per_split) : nc;
-    sim_product_loop<DIM>(Q, Cm, nq, (int64_t)blockIdx.x * QB, c_begin, c_end, c_lds, [&](int t, int64_t cell0, const f64x4& acc) {
+    int qgrp[2] = {0, 0};
+    if constexpr (GROUPED) {
+#pragma unroll
+        for (int t = 0; t < 2; t++) {
+            const int64_t q = q0 + t * 16 + l15;
+            if (q < nq) qgrp[t] = query_group[q];
+        }
+    }
+    sim_product_loop<DIM, GROUPED>(Q, Cm, nq, (int64_t)blockIdx.x * QB, c_begin, c_end, c_lds, cell_group, g_lds,
+                                   [&](int t, int64_t cell0, const f64x4& acc, const i32x4& cg) {
         const int64_t q = q0 + t * 16 + l15;
         // whole 16-cell tiles: cell0 < c_end <= nc keeps cell0 + 15 < ld_s; the cells past nc in the last one are never read
         if (q < nq && cell0 < c_end) {
+            double s[4];
+#pragma unroll
+            for (int r = 0; r < 4; r++) s[r] = (!GROUPED || cg[r] == qgrp[t]) ? acc[r] : -INFINITY;
             double* dst = S + q * ld_s + cell0 + g4 * 4;   // == tile_pos(cell0 + d_row(lane, r)) for r = 0..3
-            *(f64x2*)dst = f64x2{acc[0], acc[1]};
-            *(f64x2*)(dst + 2) = f64x2{acc[2], acc[3]};
+            *(f64x2*)dst = f64x2{s[0], s[1]};
+            *(f64x2*)(dst + 2) = f64x2{s[2], s[3]};
         }
     });
 }
@@ -457,11 +516,23 @@ int64_t score_chunk(int64_t nq, int64_t nc) {
     return nq < cap ? nq : cap;
 }
 
+// qg == nullptr: the ungrouped kernels (the instantiations t2p_sim_topk has always run)
 template <int DIM>
-void launch_scores(dim3 grid, hipStream_t st, const float* Q, const float* Cm, int64_t nq, int64_t nc, int cps, double* S,
-                   int64_t ld_s) {
-    hipLaunchKernelGGL(k_sim_scores<DIM>, grid, dim3(256), 0, st, Q, Cm, nq, nc, cps, S, ld_s);
+void launch_scores(dim3 grid, hipStream_t st, const float* Q, const float* Cm, const int32_t* qg, const int32_t* cg, int64_t nq,
+                   int64_t nc, int cps, double* S, int64_t ld_s) {
+    if (qg) hipLaunchKernelGGL((k_sim_scores<DIM, true>), grid, dim3(256), 0, st, Q, Cm, qg, cg, nq, nc, cps, S, ld_s);
+    else hipLaunchKernelGGL((k_sim_scores<DIM, false>), grid, dim3(256), 0, st, Q, Cm, qg, cg, nq, nc, cps, S, ld_s);
 }
+template <int DIM>
+void launch_partial(dim3 grid, hipStream_t st, const float* Q, const float* Cm, const int32_t* qg, const int32_t* cg, int64_t nq,
+                    int64_t nc, int cps, double* ps, int* pi, int sp) {
+    if (qg) hipLaunchKernelGGL((k_sim_partial<DIM, true>), grid, dim3(256), 0, st, Q, Cm, qg, cg, nq, nc, cps, ps, pi, sp);
+    else hipLaunchKernelGGL((k_sim_partial<DIM, false>), grid, dim3(256), 0, st, Q, Cm, qg, cg, nq, nc, cps, ps, pi, sp);
+}
+
+// both entry points: qg / cg are nullptr for the unrestricted call
+int sim_topk_impl(const float* Q, const float* Cm, const int32_t* qg, const int32_t* cg, int64_t nq, int64_t nc, int dim, int k,
+                  int64_t c_index_offset, int64_t* out_idx, double* out_score, void* ws, size_t ws_bytes, hipStream_t st);
 
 }  // namespace
 
@@ -473,6 +544,20 @@ size_t sim_topk_workspace_bytes(int64_t nq, int64_t nc, int k) {
 
 int launch_sim_topk(const float* Q, const float* Cm, int64_t nq, int64_t nc, int dim, int k, int64_t c_index_offset,
                     int64_t* out_idx, double* out_score, void* ws, size_t ws_bytes, hipStream_t st) {
+    return sim_topk_impl(Q, Cm, nullptr, nullptr, nq, nc, dim, k, c_index_offset, out_idx, out_score, ws, ws_bytes, st);
+}
+
+int launch_sim_topk_grouped(const float* Q, const float* Cm, const int32_t* query_group, const int32_t* cell_group, int64_t nq,
+                            int64_t nc, int dim, int k, int64_t c_index_offset, int64_t* out_idx, double* out_score, void* ws,
+                            size_t ws_bytes, hipStream_t st) {
+    T2P_CHECK_ARG((query_group != nullptr || nq == 0) && (cell_group != nullptr || nc == 0), "sim_topk_grouped: NULL group array");
+    // (query_group is NULL only with nq == 0, which launches nothing; with nc == 0 no kernel reads cell_group)
+    return sim_topk_impl(Q, Cm, query_group, cell_group, nq, nc, dim, k, c_index_offset, out_idx, out_score, ws, ws_bytes, st);
+}
+
+namespace {
+int sim_topk_impl(const float* Q, const float* Cm, const int32_t* qg, const int32_t* cg, int64_t nq, int64_t nc, int dim, int k,
+                  int64_t c_index_offset, int64_t* out_idx, double* out_score, void* ws, size_t ws_bytes, hipStream_t st) {
     T2P_CHECK_ARG(k >= 1 && k <= KMAX, "sim_topk: k=%d outside [1,%d]", k, KMAX);
     T2P_CHECK_ARG(dim == 256 || dim == 128 || dim == 384, "sim_topk: dim=%d not instantiated (128, 256, 384)", dim);
     T2P_CHECK_ARG(nc < 0x7fffffff, "sim_topk: nc too large");
@@ -498,9 +583,10 @@ int launch_sim_topk(const float* Q, const float* Cm, int64_t nq, int64_t nc, int
                 cps = ((cps + CB - 1) / CB) * CB;
                 const dim3 grid((unsigned)((n + QB - 1) / QB), (unsigned)sp);
                 ProfScope ps_("sim_scores", st);
-                if (dim == 256) launch_scores<256>(grid, st, Q + qa * dim, Cm, n, nc, cps, S, ld_s);
-                else if (dim == 384) launch_scores<384>(grid, st, Q + qa * dim, Cm, n, nc, cps, S, ld_s);
-                else launch_scores<128>(grid, st, Q + qa * dim, Cm, n, nc, cps, S, ld_s);
+                const int32_t* qga = qg ? qg + qa : nullptr;
+                if (dim == 256) launch_scores<256>(grid, st, Q + qa * dim, Cm, qga, cg, n, nc, cps, S, ld_s);
+                else if (dim == 384) launch_scores<384>(grid, st, Q + qa * dim, Cm, qga, cg, n, nc, cps, S, ld_s);
+                else launch_scores<128>(grid, st, Q + qa * dim, Cm, qga, cg, n, nc, cps, S, ld_s);
             }
             T2P_CHECK_LAUNCH("sim_scores");
             ProfScope ps2_("topk_select", st);
@@ -519,12 +605,9 @@ int launch_sim_topk(const float* Q, const float* Cm, int64_t nq, int64_t nc, int
     dim3 grid((unsigned)((nq + QB - 1) / QB), (unsigned)sp);
     {
     ProfScope ps_("sim_partial", st);
-    if (dim == 256)
-        hipLaunchKernelGGL(k_sim_partial<256>, grid, dim3(256), 0, st, Q, Cm, nq, nc, cps, ps, pi, sp);
-    else if (dim == 384)
-        hipLaunchKernelGGL(k_sim_partial<384>, grid, dim3(256), 0, st, Q, Cm, nq, nc, cps, ps, pi, sp);
-    else
-        hipLaunchKernelGGL(k_sim_partial<128>, grid, dim3(256), 0, st, Q, Cm, nq, nc, cps, ps, pi, sp);
+    if (dim == 256) launch_partial<256>(grid, st, Q, Cm, qg, cg, nq, nc, cps, ps, pi, sp);
+    else if (dim == 384) launch_partial<384>(grid, st, Q, Cm, qg, cg, nq, nc, cps, ps, pi, sp);
+    else launch_partial<128>(grid, st, Q, Cm, qg, cg, nq, nc, cps, ps, pi, sp);
     }
     T2P_CHECK_LAUNCH("sim_partial");
     ProfScope ps2_("topk_merge", st);
@@ -533,5 +616,6 @@ int launch_sim_topk(const float* Q, const float* Cm, int64_t nq, int64_t nc, int
     T2P_CHECK_LAUNCH("topk_merge");
     return 0;
 }
+}  // namespace
 
 }  // namespace t2p

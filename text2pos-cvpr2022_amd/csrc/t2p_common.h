@@ -453,5 +453,9 @@ int launch_one_cell_index(int64_t n, int32_t* seg_ptr_local, int32_t* first, hip
 size_t sim_topk_workspace_bytes(int64_t nq, int64_t nc, int k);
 int launch_sim_topk(const float* Q, const float* C, int64_t nq, int64_t nc, int dim, int k, int64_t c_index_offset,
                     int64_t* out_idx, double* out_score, void* ws, size_t ws_bytes, hipStream_t st);
+// pairs whose groups differ score -inf (query_group [nq], cell_group [nc]); same workspace as launch_sim_topk
+int launch_sim_topk_grouped(const float* Q, const float* C, const int32_t* query_group, const int32_t* cell_group, int64_t nq,
+                            int64_t nc, int dim, int k, int64_t c_index_offset, int64_t* out_idx, double* out_score, void* ws,
+                            size_t ws_bytes, hipStream_t st);
 
 }  // namespace t2p

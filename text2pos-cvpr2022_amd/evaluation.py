@@ -73,6 +73,50 @@ def localisation_accuracies(poses, retrievals: List[Sequence[str]], cells_dict: 
                         [p.cell_id.split("_")[0] for p in poses], bbox, size, scene, np.asarray(pos_in_cells), top_k, threshs)
 
 
+def _scene_of(item) -> str:
+    name = getattr(item, "scene_name", None)
+    return name if name is not None else getattr(item, "cell_id", getattr(item, "id", "")).rsplit("_", 1)[0]
+
+
+def street_groups(cells, poses, street_centers):
+    """Street ids of the street oracle (evaluation/pipeline.py:86-88, 100-101), float64 on the host (Nc x S work, S in the
+    tens): a cell's id is the argmin over the street centres of the Euclidean distance from `cell.get_center()` (the 3-D
+    bbox centre), a pose's the argmin of the distance from `pose.pose_w`; the first minimum wins.
+    street_centers: one [S, 3] array for all cells and poses (the reference: one scene), or {scene name: [S, 3]} - then
+    every scene's streets get an id range of their own (in the dict's order), so cells of another scene never match.
+    Returns (cell_group int32 [Nc], query_group int32 [Nq]) for retrieve_topk(cell_groups=, query_groups=)."""
+    def nearest(points, centers):
+        points = np.asarray(points, dtype=np.float64).reshape(-1, 3)
+        d = np.sqrt(((points[:, None, :] - centers[None, :, :]) ** 2).sum(axis=2))
+        return np.argmin(d, axis=1)            # (argmin: the first minimum)
+
+    def as_centers(a):
+        a = np.asarray(a, dtype=np.float64)
+        if a.ndim != 2 or a.shape[1] != 3 or a.shape[0] < 1:
+            raise ValueError(f"street_groups: street centres must be an [S, 3] array with S >= 1, got shape {a.shape}")
+        return a
+
+    cell_xyz = np.array([np.asarray(c.get_center(), dtype=np.float64)[0:3] for c in cells], dtype=np.float64).reshape(-1, 3)
+    pose_xyz = np.array([np.asarray(p.pose_w, dtype=np.float64)[0:3] for p in poses], dtype=np.float64).reshape(-1, 3)
+    if not isinstance(street_centers, dict):
+        centers = as_centers(street_centers)
+        return nearest(cell_xyz, centers).astype(np.int32), nearest(pose_xyz, centers).astype(np.int32)
+    cell_group, query_group = np.zeros(len(cells), np.int32), np.zeros(len(poses), np.int32)
+    cell_scene, pose_scene = np.array([_scene_of(c) for c in cells], dtype=object), np.array([_scene_of(p) for p in poses], dtype=object)
+    missing = (set(cell_scene.tolist()) | set(pose_scene.tolist())) - set(street_centers)
+    if missing:
+        raise ValueError(f"street_groups: no street centres for scene(s) {sorted(missing)}")
+    first = 0
+    for name, centers in street_centers.items():
+        centers = as_centers(centers)
+        for xyz, scene, out in ((cell_xyz, cell_scene, cell_group), (pose_xyz, pose_scene, query_group)):
+            sel = np.flatnonzero(scene == name)
+            if len(sel):
+                out[sel] = first + nearest(xyz[sel], centers)
+        first += centers.shape[0]
+    return cell_group, query_group
+
+
 def eval_retrieval(cell_encodings, text_encodings, db_cell_ids, query_cell_ids, query_poses_w, cells_dict, cell_size,
                    top_k):
     """The tail of eval_epoch (training/coarse.py:133-167): top-k on the GPU, metrics on the host."""

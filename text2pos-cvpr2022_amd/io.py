@@ -126,6 +126,25 @@ def save_scene(base_path: str, scene_name: str, cells: List[D.Cell], poses: List
             pickle.dump(obj, f)
 
 
+def load_street_centers(base_path: str, scene_name: str) -> np.ndarray:
+    """`<base_path>/street_centers/<scene>.pkl`: the [S, 3] street centres the street oracle assigns cells and poses to
+    (evaluation/pipeline.py:77-80), as float64."""
+    centers = np.asarray(load_pickle(os.path.join(base_path, "street_centers", f"{scene_name}.pkl")), dtype=np.float64)
+    if centers.ndim != 2 or centers.shape[1] != 3 or centers.shape[0] < 1:
+        raise RuntimeError(f"street centres of {scene_name}: expected an [S, 3] array with S >= 1, got shape {centers.shape}")
+    return centers
+
+
+def save_street_centers(base_path: str, scene_name: str, street_centers) -> None:
+    """Counterpart of load_street_centers (synthetic scenes, tests): one pickled [S, 3] float64 array."""
+    centers = np.ascontiguousarray(street_centers, dtype=np.float64)
+    if centers.ndim != 2 or centers.shape[1] != 3 or centers.shape[0] < 1:
+        raise RuntimeError(f"street centres: expected an [S, 3] array with S >= 1, got shape {centers.shape}")
+    os.makedirs(os.path.join(base_path, "street_centers"), exist_ok=True)
+    with open(os.path.join(base_path, "street_centers", f"{scene_name}.pkl"), "wb") as f:
+        pickle.dump(centers, f)
+
+
 # ---- checkpoints --------------------------------------------------------------------------------------------------------
 class _Shell(nn.Module):
     """Stand-in for a module class that is not importable here; keeps whatever state the pickle assigns."""

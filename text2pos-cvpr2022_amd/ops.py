@@ -492,6 +492,32 @@ def sim_topk(queries: torch.Tensor, cells: torch.Tensor, k: int, index_offset: i
     return idx, score
 
 
+def sim_topk_grouped(queries: torch.Tensor, cells: torch.Tensor, query_group: torch.Tensor, cell_group: torch.Tensor, k: int,
+                     index_offset: int = 0):
+    """sim_topk over the effective score `cell_group[c] == query_group[q] ? score : -inf` (int32 group ids, [nq] and [nc]):
+    a query's own group first, then masked cells at -inf by ascending index.  Returns (idx int64 [nq,k], score f64 [nq,k])."""
+    _need(queries, "queries", torch.float32, 2)
+    _need(cells, "cells", torch.float32, 2, queries.device)
+    _need(query_group, "query_group", torch.int32, 1, queries.device)
+    _need(cell_group, "cell_group", torch.int32, 1, queries.device)
+    nq, dim = queries.shape
+    nc = cells.shape[0]
+    if cells.shape[1] != dim:
+        raise RuntimeError(f"sim_topk_grouped: queries have dim {dim}, cells {cells.shape[1]}")
+    if query_group.shape[0] != nq or cell_group.shape[0] != nc:
+        raise RuntimeError(f"sim_topk_grouped: {query_group.shape[0]} query groups for {nq} queries, "
+                           f"{cell_group.shape[0]} cell groups for {nc} cells")
+    dev = queries.device
+    idx = torch.empty((nq, k), dtype=torch.int64, device=dev)
+    score = torch.empty((nq, k), dtype=torch.float64, device=dev)
+    nbytes = L.lib().t2p_sim_topk_workspace_bytes(nq, nc, k)
+    ws = workspace(dev, nbytes, "sim_topk")
+    L.check(L.lib().t2p_sim_topk_grouped(_ptr(queries), _ptr(cells), _ptr(query_group), _ptr(cell_group), nq, nc, dim, k,
+                                         int(index_offset), _ptr(idx), _ptr(score), _ptr(ws), ws.numel(), _stream(dev)),
+            "t2p_sim_topk_grouped")
+    return idx, score
+
+
 # ---------------------------------------------------------------------------------------------------------------
 def make_cell_config(n_pts=256, embed_dim=256, pointnet_features=2, use_features=("class", "color", "position"),
                      self_loops=True, knn_k=8, variation=0, radius=(0.2, 0.3, 0.4), chunk_objects=0,

@@ -35,9 +35,42 @@ def _as_device_f32(x, device):
     return x.contiguous()
 
 
-def retrieve_topk(cell_encodings, text_encodings, k: int, device=None, index_offset: int = 0):
+def _as_device_groups(g, n: int, name: str, device):
+    """Integer group ids (torch or numpy, length n) as an int32 tensor on the device; values outside int32 are refused."""
+    if isinstance(g, torch.Tensor):
+        if g.dtype.is_floating_point or g.dtype.is_complex or g.dtype == torch.bool:
+            raise TypeError(f"retrieve_topk: {name} must be integers, got {g.dtype}")
+        t = g
+    else:
+        a = np.asarray(g)
+        if a.dtype.kind not in "iu":
+            raise TypeError(f"retrieve_topk: {name} must be integers, got {a.dtype}")
+        if a.dtype == np.uint64:      # (torch has no unsigned 64-bit arithmetic; the range check below needs signed values)
+            if a.size and int(a.max()) > 2 ** 31 - 1:
+                raise ValueError(f"retrieve_topk: {name} holds values outside int32")
+            a = a.astype(np.int64)
+        elif a.dtype.kind == "u":
+            a = a.astype(np.int64)
+        t = torch.from_numpy(np.ascontiguousarray(a))
+    if t.dim() != 1 or t.shape[0] != n:
+        raise ValueError(f"retrieve_topk: {name} has shape {tuple(t.shape)}, expected ({n},)")
+    if t.dtype != torch.int32:
+        if t.numel() and (int(t.min()) < -2 ** 31 or int(t.max()) > 2 ** 31 - 1):
+            raise ValueError(f"retrieve_topk: {name} holds values outside int32")
+        t = t.to(torch.int32)
+    return t.to(device=device).contiguous()
+
+
+def retrieve_topk(cell_encodings, text_encodings, k: int, device=None, index_offset: int = 0, cell_groups=None,
+                  query_groups=None):
     """cell_encodings [Nc, D], text_encodings [Nq, D] (torch or numpy) -> (indices int64 [Nq, k], scores f64 [Nq, k])
-    as torch tensors on the GPU."""
+    as torch tensors on the GPU.
+    cell_groups [Nc] / query_groups [Nq] (integer arrays, torch or numpy, both or neither): the group-restricted ranking
+    of the street oracle (evaluation/pipeline.py:93-108) - a pair whose groups differ scores -inf, so a query retrieves
+    its own group's cells first and, when those run out, masked cells at -inf by ascending index."""
+    if (cell_groups is None) != (query_groups is None):
+        raise ValueError("retrieve_topk: cell_groups and query_groups go together (got only "
+                         f"{'cell_groups' if query_groups is None else 'query_groups'})")
     if device is None:
         device = cell_encodings.device if isinstance(cell_encodings, torch.Tensor) and cell_encodings.is_cuda else \
             torch.device("cuda", torch.cuda.current_device())
@@ -48,6 +81,10 @@ def retrieve_topk(cell_encodings, text_encodings, k: int, device=None, index_off
         from .packing import kernel_embed_dim
         pad = kernel_embed_dim(d) - d
         c, q = torch.nn.functional.pad(c, (0, pad)).contiguous(), torch.nn.functional.pad(q, (0, pad)).contiguous()
+    if cell_groups is not None:
+        cg = _as_device_groups(cell_groups, c.shape[0], "cell_groups", device)
+        qg = _as_device_groups(query_groups, q.shape[0], "query_groups", device)
+        return ops.sim_topk_grouped(q, c, qg, cg, int(k), index_offset)
     return ops.sim_topk(q, c, int(k), index_offset)
 
 

@@ -297,6 +297,28 @@ int t2p_pack_scene_objects(const float* raw_xyz, const float* raw_rgb, const int
                            const uint64_t* key, const float* scene_center, const float* scene_color, int64_t n_out, int32_t n_pts,
                            float* xyz, float* rgb, float* center, float* mean_rgb, int32_t* sample_idx_out, t2p_stream_t stream);
 
+/* The same for TRAINING batches: the augmentation of Kitti360CoarseDataset.__getitem__ (dataloading/kitti360pose/cells.py:79-91)
+ * on the resident scene - the horizontal / vertical flip of the cell (flip_pose_in_cell, dataloading/kitti360pose/utils.py:13-86)
+ * and the T.RandomRotate(120, axis=2) of the training transform (training/coarse.py:192-198) - in the reference's order:
+ *   flip (on the RAW object) -> T.FixedPoints -> rotation -> T.NormalizeScale.
+ * flip: NULL, or uint8 [n_out]: bit 0 = the slot's object is mirrored in x, bit 1 = in y (only the two low bits are read).  The
+ *   reference mirrors the raw float64 points, `obj.xyz[:, a] = 1 - obj.xyz[:, a]`, and casts to fp32 afterwards; 1.f - x32 is not that
+ *   value, so the scene carries a second image of the two columns, raw_mirror_xy [n_points][2] = float32(1.0 - xyz64[:, 0:2]), and
+ *   scene_center_mirror_xy [n_scene_obj][2] = float32 of NumPy's float64 mean over the mirrored column (get_center() of the flipped
+ *   object).  A slot with bit a set reads coordinate a of its points from raw_mirror_xy and coordinate a of its centre from
+ *   scene_center_mirror_xy; z, the colours and mean_rgb are the plain call's.  The kernel selects pointers and computes nothing
+ *   here: exact.  A flip does not change an object's point count, so a slot draws the same indices flipped or not.
+ * rot_cos_sin: NULL, or [n_out][2] fp32 (cos, sin) per slot, applied as in t2p_pack_objects between the gather and
+ *   NormalizeScale: xr = x*c + y*(-s), yr = x*s + y*c.
+ * flip = NULL and rot_cos_sin = NULL give t2p_pack_scene_objects' outputs bit for bit.  Refused (T2P_E_ARG): flip without
+ * raw_mirror_xy; flip with center wanted and no scene_center_mirror_xy; n_pts > 1024; NULL required arguments.  Outputs and their
+ * NULL rules are the plain call's. */
+int t2p_pack_scene_objects_aug(const float* raw_xyz, const float* raw_rgb, const float* raw_mirror_xy, const int32_t* obj_ptr,
+                               const int32_t* obj_id, const uint64_t* key, const uint8_t* flip, const float* rot_cos_sin,
+                               const float* scene_center, const float* scene_center_mirror_xy, const float* scene_color,
+                               int64_t n_out, int32_t n_pts, float* xyz, float* rgb, float* center, float* mean_rgb,
+                               int32_t* sample_idx_out, t2p_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Fine stage: hint <-> object matching + offset regression.
  * Replaces SuperGlue.forward models/superglue.py:239-330 (GNN of ["self","cross"] x num_layers AttentionalPropagation

@@ -109,6 +109,8 @@ SYMBOLS = {
                                    c_void]),
     "t2p_pack_scene_objects": (C.c_int, [c_void, c_void, c_void, c_void, c_void, c_void, c_void, C.c_int64, C.c_int32, c_void, c_void,
                                          c_void, c_void, c_void, c_void]),
+    "t2p_pack_scene_objects_aug": (C.c_int, [c_void, c_void, c_void, c_void, c_void, c_void, c_void, c_void, c_void, c_void, c_void,
+                                             C.c_int64, C.c_int32, c_void, c_void, c_void, c_void, c_void, c_void]),
     "t2p_match_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
     "t2p_match": (C.c_int, [c_void, c_void, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(MatchWeights),
                             C.c_int32, C.c_float, c_void, c_void, c_void, c_void, c_void, c_void, c_void, C.c_size_t,

@@ -341,6 +341,36 @@ class CellRetrievalNetwork(Fp16RangeGuard, PicklableModule):
         out = self._with_guard(run)
         return (out, kept[0]) if want_inputs else out
 
+    def encode_scene_batch(self, scene, scene_batch: dict, want_inputs: bool = False):
+        """One training (or evaluation) batch of cells packed from a scene.DeviceScene -> [B, D] fp32, L2-normalised.
+        scene_batch (training.SceneCoarseFeed builds it): `obj_ids` int [n] scene objects of the batch's cells back to back, `keys`
+        uint64 [n], `cell_ptr` int32 [B + 1], and the augmentation `flip` (uint8 [n] or None: each slot carries its cell's two flip
+        bits) and `rot` (fp32 [n, 2] or None); `n_pts` (default args.pointnet_numpoints).  One launch of
+        t2p_pack_scene_objects_aug (t2p_pack_scene_objects without augmentation) replaces the dataloader chain of
+        dataloading/kitti360pose/cells.py:65-107.  train(): the batch-statistics path (train_cell.encode_objects_train), the result
+        carries a grad_fn; eval() under no_grad: the folded kernels behind the fp16-range guard.  No colours are packed when the
+        model does not use them.  want_inputs: also return the packed (xyz, rgb, center, mean_rgb, cell_ptr)."""
+        if not self.training:
+            self._check_forward_only()
+        ids = np.ascontiguousarray(scene_batch["obj_ids"], dtype=np.int64)
+        cp = np.ascontiguousarray(scene_batch["cell_ptr"], dtype=np.int32)
+        if cp.shape[0] < 1 or int(cp[-1]) != ids.shape[0]:
+            raise RuntimeError("encode_scene_batch: cell_ptr does not cover obj_ids")
+        n_pts = int(scene_batch.get("n_pts") or getattr(self.args, "pointnet_numpoints", 256))
+        want_rgb = "color" in self.args.use_features or bool(getattr(self.args, "class_embed", False))
+        xyz, rgb, center, mean_rgb = scene.pack(ids, scene_batch["keys"], n_pts, want_rgb=want_rgb, flip=scene_batch.get("flip"),
+                                                rot=scene_batch.get("rot"))
+        if rgb is None:
+            rgb = torch.zeros_like(xyz)      # models/object_encoder.py:86-90: the PointNet++ then sees x = 0
+        class_all, color_all = scene.feature_indices(self)
+        ci = co = None
+        if class_all is not None or color_all is not None:
+            sel = torch.from_numpy(ids).to(self.device)
+            ci = None if class_all is None else class_all[sel].contiguous()
+            co = None if color_all is None else color_all[sel].contiguous()
+        out = self.encode_objects_packed(xyz, rgb, center, mean_rgb, cp, class_idx=ci, color_idx=co)
+        return (out, (xyz, rgb, center, mean_rgb, cp)) if want_inputs else out
+
     encode_cells = encode_objects  # the name BASELINE.json uses for the same method
 
     def forward(self):

@@ -456,6 +456,26 @@ int t2p_pack_scene_objects(const float* raw_xyz, const float* raw_rgb, const int
                              mean_rgb, sample_idx_out, (hipStream_t)stream);
 }
 
+int t2p_pack_scene_objects_aug(const float* raw_xyz, const float* raw_rgb, const float* raw_mirror_xy, const int32_t* obj_ptr,
+                               const int32_t* obj_id, const uint64_t* key, const uint8_t* flip, const float* rot_cos_sin,
+                               const float* scene_center, const float* scene_center_mirror_xy, const float* scene_color,
+                               int64_t n_out, int32_t n_pts, float* xyz, float* rgb, float* center, float* mean_rgb,
+                               int32_t* sample_idx_out, t2p_stream_t stream) {
+    T2P_CHECK_ARG(n_out >= 0 && n_pts >= 1, "pack_scene_objects_aug: bad sizes");
+    T2P_CHECK_ARG(n_pts <= 1024, "pack_scene_objects_aug: n_pts=%d > 1024 (the sampled points of an object are staged in LDS)", n_pts);
+    T2P_CHECK_ARG(flip == nullptr || raw_mirror_xy != nullptr,
+                  "pack_scene_objects_aug: flip given but the scene has no mirror image (raw_mirror_xy is NULL)");
+    T2P_CHECK_ARG(flip == nullptr || center == nullptr || scene_center_mirror_xy != nullptr,
+                  "pack_scene_objects_aug: flip given and center wanted but scene_center_mirror_xy is NULL");
+    T2P_CHECK_ARG(n_out == 0 || (raw_xyz && obj_ptr && obj_id && key && xyz), "pack_scene_objects_aug: NULL argument");
+    T2P_CHECK_ARG(n_out == 0 || rgb == nullptr || raw_rgb != nullptr, "pack_scene_objects_aug: rgb wanted but raw_rgb is NULL");
+    T2P_CHECK_ARG(n_out == 0 || ((center == nullptr || scene_center != nullptr) && (mean_rgb == nullptr || scene_color != nullptr)),
+                  "pack_scene_objects_aug: center / mean_rgb wanted but the scene table is NULL");
+    return launch_pack_scene_aug(raw_xyz, raw_rgb, raw_mirror_xy, obj_ptr, obj_id, key, flip, rot_cos_sin, scene_center,
+                                 scene_center_mirror_xy, scene_color, n_out, n_pts, xyz, rgb, center, mean_rgb, sample_idx_out,
+                                 (hipStream_t)stream);
+}
+
 int t2p_dedup_rows(const float* xyz, const float* rgb, int64_t n_obj, int32_t n_pts, uint16_t* rows, uint16_t* n_rows,
                    t2p_stream_t stream) {
     T2P_CHECK_ARG(n_obj >= 0, "dedup_rows: negative size");

@@ -342,12 +342,23 @@ __global__ __launch_bounds__(256) void k_pack_objects(const float* __restrict__ 
 // so a slot's sample depends on its key only (the host derives it from (seed, global cell index, object slot):
 // pipeline.PerCellTransform), whichever rank, batch or stream packs it; centre / mean colour are gathered from the scene's
 // per-object tables (the reference's float64 means, computed once on the host: exact).
-__global__ __launch_bounds__(256) void k_pack_scene(const float* __restrict__ raw_xyz, const float* __restrict__ raw_rgb,
-                                                    const int32_t* __restrict__ obj_ptr, const int32_t* __restrict__ obj_id,
-                                                    const uint64_t* __restrict__ key, const float* __restrict__ scene_center,
-                                                    const float* __restrict__ scene_color, int64_t n_out, int n_pts,
-                                                    float* __restrict__ xyz, float* __restrict__ rgb, float* __restrict__ center,
-                                                    float* __restrict__ mean_rgb, int32_t* __restrict__ idx_out) {
+// AUG = the training variant (t2p_pack_scene_objects_aug): the flips of Kitti360CoarseDataset.__getitem__
+// (dataloading/kitti360pose/cells.py:79-91 -> flip_pose_in_cell, utils.py:13-86) and the T.RandomRotate of the training transform
+// (training/coarse.py:192-198).  The reference mirrors the raw float64 points (x <- 1 - x) BEFORE the cast to fp32, so the scene
+// carries that image ready-made: raw_mirror_xy [n_points][2] = float32(1 - xyz64[:, 0:2]), center_mirror_xy [n_scene_obj][2] =
+// float32 of the float64 mean of the mirrored column.  A slot whose flip bit a is set reads coordinate a of its points and of its
+// centre from those tables - a pointer is selected per slot and axis, nothing is computed - and draws the same indices as the
+// unflipped slot (the point count does not change).  The rotation is k_pack_objects' statement.  AUG = false is the plain kernel:
+// every added statement sits behind `if constexpr`.
+template <bool AUG>
+__device__ __forceinline__ void pack_scene_body(const float* __restrict__ raw_xyz, const float* __restrict__ raw_rgb,
+                                                const float* __restrict__ raw_mirror_xy, const int32_t* __restrict__ obj_ptr,
+                                                const int32_t* __restrict__ obj_id, const uint64_t* __restrict__ key,
+                                                const uint8_t* __restrict__ flip, const float* __restrict__ rot,
+                                                const float* __restrict__ scene_center, const float* __restrict__ center_mirror_xy,
+                                                const float* __restrict__ scene_color, int64_t n_out, int n_pts,
+                                                float* __restrict__ xyz, float* __restrict__ rgb, float* __restrict__ center,
+                                                float* __restrict__ mean_rgb, int32_t* __restrict__ idx_out) {
     extern __shared__ float pack_lds[];
     const int lane = threadIdx.x & 63;
     float* pts = pack_lds + (threadIdx.x >> 6) * n_pts * 3;
@@ -357,15 +368,46 @@ __global__ __launch_bounds__(256) void k_pack_scene(const float* __restrict__ ra
     const int64_t lo = obj_ptr[o];
     const uint64_t m = (uint64_t)(obj_ptr[o + 1] - obj_ptr[o]);
     const uint64_t k = key[s];
-    if (lane < 3) {
-        if (center != nullptr) center[s * 3 + lane] = scene_center[o * 3 + lane];
-        if (mean_rgb != nullptr) mean_rgb[s * 3 + lane] = scene_color[o * 3 + lane];
+    // AUG: where the slot's x and y come from (pointer to the column, floats per point)
+    const float *px = raw_xyz, *py = raw_xyz + 1;
+    int stx = 3, sty = 3;
+    float rc = 1.f, rs = 0.f;
+    bool rotate = false;
+    if constexpr (AUG) {
+        const int f = flip != nullptr ? (flip[s] & 3) : 0;
+        if (f & 1) { px = raw_mirror_xy; stx = 2; }
+        if (f & 2) { py = raw_mirror_xy + 1; sty = 2; }
+        rotate = rot != nullptr;
+        if (rotate) { rc = rot[s * 2]; rs = rot[s * 2 + 1]; }
+        if (lane < 3) {
+            if (center != nullptr) {
+                const bool mir = (lane == 0 && (f & 1)) || (lane == 1 && (f & 2));
+                center[s * 3 + lane] = mir ? center_mirror_xy[o * 2 + lane] : scene_center[o * 3 + lane];
+            }
+            if (mean_rgb != nullptr) mean_rgb[s * 3 + lane] = scene_color[o * 3 + lane];
+        }
+    } else {
+        if (lane < 3) {
+            if (center != nullptr) center[s * 3 + lane] = scene_center[o * 3 + lane];
+            if (mean_rgb != nullptr) mean_rgb[s * 3 + lane] = scene_color[o * 3 + lane];
+        }
     }
     for (int i = lane; i < n_pts; i += 64) {
         const uint32_t d = (uint32_t)(((pack_mix64(k ^ ((uint64_t)i * 0xD6E8FEB86659FD93ull)) >> 32) * m) >> 32);
         const int64_t j = lo + d;
-        pts[i * 3] = raw_xyz[j * 3];
-        pts[i * 3 + 1] = raw_xyz[j * 3 + 1];
+        if constexpr (AUG) {
+            float x = px[j * stx], y = py[j * sty];
+            if (rotate) {  // k_pack_objects' statement, term for term
+                const float xr = x * rc + y * -rs, yr = x * rs + y * rc;
+                x = xr;
+                y = yr;
+            }
+            pts[i * 3] = x;
+            pts[i * 3 + 1] = y;
+        } else {
+            pts[i * 3] = raw_xyz[j * 3];
+            pts[i * 3 + 1] = raw_xyz[j * 3 + 1];
+        }
         pts[i * 3 + 2] = raw_xyz[j * 3 + 2];
         if (rgb != nullptr) {
             float* c = rgb + (s * n_pts + i) * 3;
@@ -376,6 +418,29 @@ __global__ __launch_bounds__(256) void k_pack_scene(const float* __restrict__ ra
         if (idx_out != nullptr) idx_out[s * n_pts + i] = (int32_t)d;
     }
     normalize_scale_store(pts, n_pts, lane, xyz + s * n_pts * 3);
+}
+
+__global__ __launch_bounds__(256) void k_pack_scene(const float* __restrict__ raw_xyz, const float* __restrict__ raw_rgb,
+                                                    const int32_t* __restrict__ obj_ptr, const int32_t* __restrict__ obj_id,
+                                                    const uint64_t* __restrict__ key, const float* __restrict__ scene_center,
+                                                    const float* __restrict__ scene_color, int64_t n_out, int n_pts,
+                                                    float* __restrict__ xyz, float* __restrict__ rgb, float* __restrict__ center,
+                                                    float* __restrict__ mean_rgb, int32_t* __restrict__ idx_out) {
+    pack_scene_body<false>(raw_xyz, raw_rgb, nullptr, obj_ptr, obj_id, key, nullptr, nullptr, scene_center, nullptr, scene_color, n_out,
+                           n_pts, xyz, rgb, center, mean_rgb, idx_out);
+}
+
+__global__ __launch_bounds__(256) void k_pack_scene_aug(const float* __restrict__ raw_xyz, const float* __restrict__ raw_rgb,
+                                                        const float* __restrict__ raw_mirror_xy, const int32_t* __restrict__ obj_ptr,
+                                                        const int32_t* __restrict__ obj_id, const uint64_t* __restrict__ key,
+                                                        const uint8_t* __restrict__ flip, const float* __restrict__ rot,
+                                                        const float* __restrict__ scene_center,
+                                                        const float* __restrict__ center_mirror_xy,
+                                                        const float* __restrict__ scene_color, int64_t n_out, int n_pts,
+                                                        float* __restrict__ xyz, float* __restrict__ rgb, float* __restrict__ center,
+                                                        float* __restrict__ mean_rgb, int32_t* __restrict__ idx_out) {
+    pack_scene_body<true>(raw_xyz, raw_rgb, raw_mirror_xy, obj_ptr, obj_id, key, flip, rot, scene_center, center_mirror_xy, scene_color,
+                          n_out, n_pts, xyz, rgb, center, mean_rgb, idx_out);
 }
 
 // PairwiseRankingLoss (training/losses.py:126-164) on the score matrix S = im_n s_n^T [B][B]:
@@ -605,6 +670,20 @@ int launch_pack_scene(const float* raw_xyz, const float* raw_rgb, const int32_t*
     hipLaunchKernelGGL(k_pack_scene, dim3((unsigned)((n_out + 3) / 4)), dim3(256), (size_t)4 * n_pts * 3 * sizeof(float), st, raw_xyz,
                        raw_rgb, obj_ptr, obj_id, key, scene_center, scene_color, n_out, n_pts, xyz, rgb, center, mean_rgb, idx_out);
     T2P_CHECK_LAUNCH("pack_scene");
+    return 0;
+}
+
+int launch_pack_scene_aug(const float* raw_xyz, const float* raw_rgb, const float* raw_mirror_xy, const int32_t* obj_ptr,
+                          const int32_t* obj_id, const uint64_t* key, const uint8_t* flip, const float* rot, const float* scene_center,
+                          const float* center_mirror_xy, const float* scene_color, int64_t n_out, int n_pts, float* xyz, float* rgb,
+                          float* center, float* mean_rgb, int32_t* idx_out, hipStream_t st) {
+    T2P_CHECK_ARG(n_pts <= 1024, "pack_scene_objects_aug: n_pts=%d > 1024 (the sampled points of an object are staged in LDS)", n_pts);
+    if (n_out == 0) return 0;
+    ProfScope ps_("pack_scene_aug", st);
+    hipLaunchKernelGGL(k_pack_scene_aug, dim3((unsigned)((n_out + 3) / 4)), dim3(256), (size_t)4 * n_pts * 3 * sizeof(float), st, raw_xyz,
+                       raw_rgb, raw_mirror_xy, obj_ptr, obj_id, key, flip, rot, scene_center, center_mirror_xy, scene_color, n_out,
+                       n_pts, xyz, rgb, center, mean_rgb, idx_out);
+    T2P_CHECK_LAUNCH("pack_scene_aug");
     return 0;
 }
 

@@ -275,6 +275,10 @@ int launch_pack_objects(const float* raw_xyz, const float* raw_rgb, const int32_
 int launch_pack_scene(const float* raw_xyz, const float* raw_rgb, const int32_t* obj_ptr, const int32_t* obj_id, const uint64_t* key,
                       const float* scene_center, const float* scene_color, int64_t n_out, int n_pts, float* xyz, float* rgb,
                       float* center, float* mean_rgb, int32_t* idx_out, hipStream_t st);
+int launch_pack_scene_aug(const float* raw_xyz, const float* raw_rgb, const float* raw_mirror_xy, const int32_t* obj_ptr,
+                          const int32_t* obj_id, const uint64_t* key, const uint8_t* flip, const float* rot, const float* scene_center,
+                          const float* center_mirror_xy, const float* scene_color, int64_t n_out, int n_pts, float* xyz, float* rgb,
+                          float* center, float* mean_rgb, int32_t* idx_out, hipStream_t st);
 int launch_pairwise_ranking(const float* scores, int batch, float margin, float* row_loss, float* d_scores, float* row_cnt,
                             hipStream_t st);
 int launch_hardest_ranking(const float* scores, int batch, float margin, float* best, int32_t* where, float* d_scores,

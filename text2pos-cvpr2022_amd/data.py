@@ -170,6 +170,101 @@ class KeyedFixedPoints:
         return data
 
 
+# ---- training augmentation on the host: the chain the on-device feed (t2p_pack_scene_objects_aug) is tested against ----------------
+_ROT_SALT = np.uint64(0x726F74617465005A)     # keyed_rotations' salt: the angle's bits are not the bits that draw the points
+
+
+def keyed_rotations(keys, degrees: float) -> np.ndarray:
+    """T.RandomRotate(degrees, axis=2) (training/coarse.py:196) with a counter-based draw: one angle per sampling key, uniform in
+    [-degrees, degrees]: 53 bits of mix64(key ^ salt) -> float64 u in [0, 1), angle = degrees * (2u - 1).  Returns [n, 2] fp32
+    (cos, sin) of the float64 angle - the `rot_cos_sin` argument of the pack kernels; the trigonometry stays on the host, as with
+    draw_rotations."""
+    keys = np.atleast_1d(np.asarray(keys, dtype=np.uint64))
+    u = (mix64(keys ^ _ROT_SALT) >> np.uint64(11)).astype(np.float64) * (1.0 / 9007199254740992.0)
+    ang = np.pi * (abs(float(degrees)) * (2.0 * u - 1.0)) / 180.0
+    return np.stack([np.cos(ang), np.sin(ang)], axis=-1).astype(np.float32)
+
+
+class RotateZ:
+    """Rotation about z in fp32 with t2p_pack_objects' matrix convention: pos <- pos @ [[c, s, 0], [-s, c, 0], [0, 0, 1]].
+    cos / sin: scalars (every object the same angle), or arrays - then the k-th object this transform is applied to takes entry k
+    (batch_object_points applies a cell's transform to its objects in order, like KeyedFixedPoints)."""
+
+    def __init__(self, cos, sin):
+        self.cos = np.atleast_1d(np.asarray(cos, dtype=np.float32))
+        self.sin = np.atleast_1d(np.asarray(sin, dtype=np.float32))
+        self.slot = 0
+
+    def __call__(self, data):
+        k = self.slot if self.cos.shape[0] > 1 else 0
+        self.slot += 1
+        c, s = float(self.cos[k]), float(self.sin[k])
+        data.pos = data.pos @ torch.tensor([[c, s, 0.0], [-s, c, 0.0], [0.0, 0.0, 1.0]], dtype=torch.float32)
+        return data
+
+
+class KeyedRotateZ(RotateZ):
+    """RotateZ whose k-th angle is keyed_rotations' draw of slot k of sample `sample_index` under `seed`."""
+
+    def __init__(self, seed: int, sample_index: int, degrees: float):
+        self.seed, self.sample_index, self.degrees, self.slot = seed, sample_index, degrees, 0
+
+    def __call__(self, data):
+        cs = keyed_rotations(sample_keys(self.seed, self.sample_index, self.slot), self.degrees)[0]
+        self.cos, self.sin = cs[0:1], cs[1:2]
+        return RotateZ.__call__(self, data)
+
+
+def _swap_words(text: str, a: str, b: str) -> str:
+    """Every `a` becomes `b` and every `b` becomes `a`, at once."""
+    return b.join(part.replace(b, a) for part in text.split(a))
+
+
+def flip_cell(cell, text: str, direction: int):
+    """The cell flip of the coarse training set (Kitti360CoarseDataset.__getitem__, dataloading/kitti360pose/cells.py:85-89, through
+    flip_pose_in_cell, utils.py:13-86): direction +1 mirrors the cell horizontally (x <- 1 - x of every object's raw float64
+    points, "east" <-> "west" in the text), -1 vertically (y, "north" <-> "south").  Returns (flipped copy of the cell, text); the
+    cell handed in and its objects' arrays are untouched (the colours, which a flip does not change, are shared)."""
+    import copy
+    if direction not in (1, -1):
+        raise ValueError(f"flip_cell: direction must be +1 (horizontal) or -1 (vertical), got {direction!r}")
+    axis = 0 if direction == 1 else 1
+    flipped = copy.copy(cell)
+    objs = []
+    for o in cell.objects:
+        q = copy.copy(o)
+        q.xyz = np.array(o.xyz, dtype=np.float64, copy=True)
+        q.xyz[:, axis] = 1 - q.xyz[:, axis]
+        objs.append(q)
+    flipped.objects = objs
+    text = _swap_words(text, "east", "west") if direction == 1 else _swap_words(text, "north", "south")
+    return flipped, text
+
+
+def flip_cell_code(cell, text: str, code: int):
+    """flip_cell for a two-bit code: bit 0 = the horizontal flip, bit 1 = the vertical one (the reference's order of the two)."""
+    if code & 1:
+        cell, text = flip_cell(cell, text, 1)
+    if code & 2:
+        cell, text = flip_cell(cell, text, -1)
+    return cell, text
+
+
+def mirror_tables(flat: Sequence[Object3d]):
+    """(raw_mirror_xy f32 [R, 2], center_mirror_xy f32 [M, 2]) of a scene's objects: the two columns a flip rewrites, as the
+    reference would hand them to the model - float32(1.0 - xyz64[:, 0:2]) (mirrored in float64, then cast) and float32 of
+    get_center() of the flipped object (NumPy's float64 mean over its mirrored points)."""
+    pts, ctr = [], np.empty((len(flat), 2), dtype=np.float32)
+    for i, o in enumerate(flat):
+        f = np.array(o.xyz, dtype=np.float64, copy=True).reshape(-1, 3)
+        f[:, 0] = 1 - f[:, 0]
+        f[:, 1] = 1 - f[:, 1]
+        pts.append(f[:, 0:2].astype(np.float32))
+        ctr[i] = np.mean(f, axis=0)[0:2].astype(np.float32)
+    raw = np.ascontiguousarray(np.concatenate(pts, 0)) if pts else np.zeros((0, 2), np.float32)
+    return raw, ctr
+
+
 class NormalizeScale:
     def __call__(self, data):
         data.pos = data.pos - data.pos.mean(dim=-2, keepdim=True)

@@ -805,6 +805,49 @@ def pack_scene_objects(raw_xyz, raw_rgb, obj_ptr, obj_id, key, scene_center, sce
     return (xyz, rgb, center, mean_rgb, idx) if want_idx else (xyz, rgb, center, mean_rgb)
 
 
+def pack_scene_objects_aug(raw_xyz, raw_rgb, raw_mirror_xy, obj_ptr, obj_id, key, flip, rot, scene_center, scene_center_mirror_xy,
+                           scene_color, n_pts: int = 256, want_rgb: bool = True, want_idx: bool = False):
+    """pack_scene_objects with the training augmentation (t2p_pack_scene_objects_aug, include/t2p.h): flip None or uint8 [n_out]
+    (bit 0 = x mirrored, bit 1 = y mirrored; needs the scene's mirror tables raw_mirror_xy [R, 2] / scene_center_mirror_xy
+    [M, 2]), rot None or fp32 [n_out, 2] (cos, sin per slot, as pack_objects).  Returns what pack_scene_objects returns."""
+    _need(raw_xyz, "raw_xyz", torch.float32, 2)
+    dev = raw_xyz.device
+    _need(raw_rgb, "raw_rgb", torch.float32, 2, dev)
+    _need(obj_ptr, "obj_ptr", torch.int32, 1, dev)
+    _need(obj_id, "obj_id", torch.int32, 1, dev)
+    _need(key, "key", torch.int64, 1, dev)
+    _need(scene_center, "scene_center", torch.float32, 2, dev)
+    _need(scene_color, "scene_color", torch.float32, 2, dev)
+    n_out = obj_id.shape[0]
+    if key.shape[0] != n_out or tuple(raw_rgb.shape) != tuple(raw_xyz.shape) or raw_xyz.shape[1] != 3 or \
+            scene_center.shape[0] != obj_ptr.shape[0] - 1 or tuple(scene_color.shape) != tuple(scene_center.shape):
+        raise RuntimeError("pack_scene_objects_aug: inconsistent shapes")
+    if flip is not None:
+        if raw_mirror_xy is None or scene_center_mirror_xy is None:
+            raise RuntimeError("pack_scene_objects_aug: flip needs the scene's mirror tables (DeviceScene(..., mirror=True))")
+        _need(flip, "flip", torch.uint8, 1, dev)
+        _need(raw_mirror_xy, "raw_mirror_xy", torch.float32, 2, dev)
+        _need(scene_center_mirror_xy, "scene_center_mirror_xy", torch.float32, 2, dev)
+        if flip.shape[0] != n_out or tuple(raw_mirror_xy.shape) != (raw_xyz.shape[0], 2) or \
+                tuple(scene_center_mirror_xy.shape) != (scene_center.shape[0], 2):
+            raise RuntimeError("pack_scene_objects_aug: flip must be [n_out], the mirror tables [R, 2] and [M, 2]")
+    if rot is not None:
+        _need(rot, "rot", torch.float32, 2, dev)
+        if tuple(rot.shape) != (n_out, 2):
+            raise RuntimeError("pack_scene_objects_aug: rot must be [n_out, 2]")
+    xyz = torch.empty((n_out, n_pts, 3), dtype=torch.float32, device=dev)
+    rgb = torch.empty((n_out, n_pts, 3), dtype=torch.float32, device=dev) if want_rgb else None
+    center = torch.empty((n_out, 3), dtype=torch.float32, device=dev)
+    mean_rgb = torch.empty((n_out, 3), dtype=torch.float32, device=dev)
+    idx = torch.empty((n_out, n_pts), dtype=torch.int32, device=dev) if want_idx else None
+    opt = lambda t: _ptr(t) if t is not None else None
+    L.check(L.lib().t2p_pack_scene_objects_aug(_ptr(raw_xyz), _ptr(raw_rgb), opt(raw_mirror_xy), _ptr(obj_ptr), _ptr(obj_id), _ptr(key),
+                                               opt(flip), opt(rot), _ptr(scene_center), opt(scene_center_mirror_xy), _ptr(scene_color),
+                                               n_out, n_pts, _ptr(xyz), opt(rgb), _ptr(center), _ptr(mean_rgb), opt(idx), _stream(dev)),
+            "t2p_pack_scene_objects_aug")
+    return (xyz, rgb, center, mean_rgb, idx) if want_idx else (xyz, rgb, center, mean_rgb)
+
+
 def make_match_weights(packed: Dict[str, object]) -> L.MatchWeights:
     """packed: packing.pack_match_weights(...)"""
     w = L.MatchWeights()

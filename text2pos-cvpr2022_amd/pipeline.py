@@ -41,14 +41,27 @@ class PerCellTransform:
     rank, batch or device packs it: the sharded pipeline reproduces the single-process result bit for bit, and the on-device
     dataloader (scene.DeviceScene, csrc/small_kernels.hip::k_pack_scene) draws exactly what `for_cell`'s host chain draws.
     (`default_transform` keeps one sequential generator, like the reference's dataloader; its draws depend on the order in
-    which a process walks the cells.)"""
+    which a process walks the cells.)
+    rotate_degrees (None = the evaluation chain above): the training transform of training/coarse.py:192-198, FixedPoints ->
+    RandomRotate(rotate_degrees, axis=2) -> NormalizeScale, the angle of an object keyed like its points (data.keyed_rotations of
+    the same (seed, sample, slot) key): `rotations` gives the kernel's `rot_cos_sin`, `for_cell` the host chain with those angles."""
 
-    def __init__(self, n_pts: int = 256, seed: int = 0):
-        self.n_pts, self.seed = n_pts, seed
+    def __init__(self, n_pts: int = 256, seed: int = 0, rotate_degrees: Optional[float] = None):
+        self.n_pts, self.seed, self.rotate_degrees = n_pts, seed, rotate_degrees
 
     def for_cell(self, cell_index: int):
         """The host chain for one cell / sample (applied to its objects in order)."""
-        return D.Compose([D.KeyedFixedPoints(self.n_pts, self.seed, cell_index), D.NormalizeScale()])
+        if self.rotate_degrees is None:
+            return D.Compose([D.KeyedFixedPoints(self.n_pts, self.seed, cell_index), D.NormalizeScale()])
+        return D.Compose([D.KeyedFixedPoints(self.n_pts, self.seed, cell_index),
+                          D.KeyedRotateZ(self.seed, cell_index, self.rotate_degrees), D.NormalizeScale()])
+
+    def rotations(self, sample_index, slot) -> Optional[np.ndarray]:
+        """fp32 [n, 2] (cos, sin) of the (sample, slot) pairs' angles (arrays broadcast): the `rot_cos_sin` argument of
+        t2p_pack_scene_objects_aug; None without rotate_degrees."""
+        if self.rotate_degrees is None:
+            return None
+        return D.keyed_rotations(self.keys(sample_index, slot), self.rotate_degrees)
 
     def keys(self, sample_index, slot) -> np.ndarray:
         """uint64 sampling keys of (sample, slot) pairs (arrays broadcast): the `key` argument of t2p_pack_scene_objects."""

@@ -25,9 +25,13 @@ class DeviceScene:
     n_pad > 0 appends that many padding objects (Object3d.create_padding: dataloading/kitti360pose/eval.py:147-149 fills a
     sample's object list up to pad_size with them); their scene ids are `pad_ids`.  The padding objects' eight points (within 1 mm of
     the origin) are drawn from `pad_seed`, not from the process-global np.random the reference uses: every rank of a process group
-    builds its own scene, and the fine stage must see the same padding on each of them (and in the single-process run)."""
+    builds its own scene, and the fine stage must see the same padding on each of them (and in the single-process run).
+    mirror=True also builds and uploads the two tables the training flips read (t2p_pack_scene_objects_aug, include/t2p.h):
+    `raw_mirror_xy` [R, 2] = float32(1 - xyz64[:, 0:2]) and `center_mirror_xy` [M, 2] (the flipped objects' centres) - 8 more bytes
+    per raw point in HBM (20 instead of 12 for the coordinates), and one more pass over the float64 points on the host."""
 
-    def __init__(self, cells: Sequence, device, n_pad: int = 0, threads: Optional[int] = None, pad_seed: int = 0):
+    def __init__(self, cells: Sequence, device, n_pad: int = 0, threads: Optional[int] = None, pad_seed: int = 0,
+                 mirror: bool = False):
         self.device = torch.device(device)
         groups = [c.objects if isinstance(c.objects, list) else list(c.objects) for c in cells]
         counts = np.fromiter((len(g) for g in groups), dtype=np.int64, count=len(groups))
@@ -56,6 +60,10 @@ class DeviceScene:
         to = lambda a: torch.from_numpy(a).to(self.device)
         self.raw_xyz, self.raw_rgb, self.obj_ptr = to(raw_xyz), to(raw_rgb), to(obj_ptr)
         self.center, self.color = to(c32), to(k32)
+        self.raw_mirror_xy = self.center_mirror_xy = None
+        if mirror:
+            mirror_xy, center_mirror = D.mirror_tables(flat)
+            self.raw_mirror_xy, self.center_mirror_xy = to(mirror_xy), to(center_mirror)
         self._idx = {}
         self._padded = {}
 
@@ -90,13 +98,36 @@ class DeviceScene:
             self._padded[pad_size] = np.where(slot < n, self.cell_ptr[:-1, None] + slot, self.pad_ids[:pad_size][None, :])
         return self._padded[pad_size]
 
-    def pack(self, obj_ids: np.ndarray, keys: np.ndarray, n_pts: int = 256, want_rgb: bool = True, want_idx: bool = False):
+    def pack(self, obj_ids: np.ndarray, keys: np.ndarray, n_pts: int = 256, want_rgb: bool = True, want_idx: bool = False,
+             flip: Optional[np.ndarray] = None, rot: Optional[np.ndarray] = None):
         """Packed encoder inputs (xyz, rgb | None, center, mean_rgb[, sample_idx]) of the object slots (obj_ids int [n], keys
-        uint64 [n]); one kernel launch on the current stream."""
+        uint64 [n]); one kernel launch on the current stream.
+        flip (uint8 [n]: bit 0 = the slot's object mirrored in x, bit 1 = in y; needs a scene built with mirror=True) and rot (fp32
+        [n, 2]: cos, sin per slot) are the training augmentation: with either given the call goes to t2p_pack_scene_objects_aug,
+        otherwise to t2p_pack_scene_objects as before."""
         ids = torch.from_numpy(np.ascontiguousarray(obj_ids, dtype=np.int32)).to(self.device, non_blocking=True)
         k = torch.from_numpy(np.ascontiguousarray(keys, dtype=np.uint64).view(np.int64)).to(self.device, non_blocking=True)
-        return ops.pack_scene_objects(self.raw_xyz, self.raw_rgb, self.obj_ptr, ids, k, self.center, self.color, n_pts,
-                                      want_rgb, want_idx)
+        if flip is None and rot is None:
+            return ops.pack_scene_objects(self.raw_xyz, self.raw_rgb, self.obj_ptr, ids, k, self.center, self.color, n_pts,
+                                          want_rgb, want_idx)
+        n = ids.shape[0]
+        if n and (int(np.min(obj_ids)) < 0 or int(np.max(obj_ids)) >= self.n_objects):
+            raise RuntimeError(f"DeviceScene.pack: object ids outside [0, {self.n_objects})")
+        f = r = None
+        if flip is not None:
+            if self.raw_mirror_xy is None:
+                raise RuntimeError("DeviceScene.pack: flip needs the mirror tables; build the scene with mirror=True")
+            fl = np.ascontiguousarray(flip)
+            if fl.shape != (n,) or fl.dtype.kind not in "ui" or (n and (int(fl.min()) < 0 or int(fl.max()) > 3)):
+                raise RuntimeError("DeviceScene.pack: flip must be an integer code in 0..3 per slot")
+            f = torch.from_numpy(fl.astype(np.uint8)).to(self.device, non_blocking=True)
+        if rot is not None:
+            ro = np.ascontiguousarray(rot, dtype=np.float32)
+            if ro.shape != (n, 2):
+                raise RuntimeError("DeviceScene.pack: rot must be [n, 2] (cos, sin per slot)")
+            r = torch.from_numpy(ro).to(self.device, non_blocking=True)
+        return ops.pack_scene_objects_aug(self.raw_xyz, self.raw_rgb, self.raw_mirror_xy, self.obj_ptr, ids, k, f, r, self.center,
+                                          self.center_mirror_xy, self.color, n_pts, want_rgb, want_idx)
 
     def pack_cells(self, transform, lo: int, hi: int, cell_offset: int = 0, **kw):
         """Cells [lo, hi) of this scene under `transform` (pipeline.PerCellTransform; global index of scene cell i =

@@ -3,13 +3,17 @@ train_pointnet_epoch, val_pointnet_epoch below) and of the reference's coarse tr
 dictionary (`texts`, `objects`, `object_points` as the reference's Kitti360CoarseDataset.collate_fn yields them), same
 order of calls; the arithmetic is docs/notebook.md 4.8.  val_fine_epoch is the validation pass of the fine stage
 (training/fine.py:119-170, `eval_epoch`), which the reference runs in train() mode; train_fine_epoch is its training pass
-(training/fine.py:36-116, `train_epoch`), inside the opt-in fine_backward().  The data side (datasets, augmentation, plotting) stays with the caller."""
+(training/fine.py:36-116, `train_epoch`), inside the opt-in fine_backward().  SceneCoarseFeed is the coarse stage's training set
+(Kitti360CoarseDataset, dataloading/kitti360pose/cells.py:36-110: hint shuffle, cell flips, the rotating transform) with every draw
+counter-based, packed from a scene resident in HBM or built by the host chain; the fine stage's dataset and the plots stay with the
+caller."""
 import contextlib
 from typing import Iterable, Optional
 
 import numpy as np
 import torch
 
+from . import data as D
 from . import ops
 from .losses import HardestRankingLoss, MatchingLoss, MSELoss, PairwiseRankingLoss, calc_pose_error, calc_recall_precision
 
@@ -48,6 +52,15 @@ def train_epoch(model, dataloader: Iterable[dict], optimizer, criterion, max_bat
         if str(dev) not in _TEXT_STREAMS:
             _TEXT_STREAMS[str(dev)] = ops.concurrent_stream(dev)
         side = _TEXT_STREAMS[str(dev)]
+    scene = getattr(dataloader, "scene", None)           # SceneCoarseFeed hands over the DeviceScene its batches index
+
+    def encode_positive(batch):
+        if "scene_batch" in batch:                       # packed on the GPU from the resident scene (SceneCoarseFeed)
+            if scene is None:
+                raise RuntimeError("train_epoch: a batch carries `scene_batch` but the dataloader has no `scene` (scene.DeviceScene)")
+            return model.encode_scene_batch(scene, batch["scene_batch"])
+        return model.encode_objects(batch["objects"], batch["object_points"])
+
     for i_batch, batch in enumerate(dataloader):
         if max_batches is not None and i_batch >= max_batches:
             break
@@ -57,18 +70,159 @@ def train_epoch(model, dataloader: Iterable[dict], optimizer, criterion, max_bat
             side.wait_stream(main)                       # zero_grad / the previous optimizer step
             with torch.cuda.stream(side):
                 anchor = model.encode_text(batch["texts"])
-            positive = model.encode_objects(batch["objects"], batch["object_points"])
+            positive = encode_positive(batch)
             main.wait_stream(side)
             anchor.record_stream(main)                   # allocated on the side stream's pool, consumed by the loss on the main one
         else:
             anchor = model.encode_text(batch["texts"])
-            positive = model.encode_objects(batch["objects"], batch["object_points"])
+            positive = encode_positive(batch)
         loss = criterion(anchor, positive)
         loss.backward()
         optimizer.step()
         epoch_losses.append(loss.item())
         batches.append(batch)
     return float(np.mean(epoch_losses)) if epoch_losses else float("nan"), batches
+
+
+_ITEM_SALT = 0x6974656D5F6B6579      # SceneCoarseFeed: the per-item draws (flips, hint order) hash apart from the sampling keys
+_FLIP_SALT = np.uint64(0x666C69705F626974)
+_HINT_SALT = np.uint64(0x68696E745F6F7264)
+
+
+class SceneCoarseFeed:
+    """The coarse stage's training batches (Kitti360CoarseDataset.__getitem__ + collate_fn, dataloading/kitti360pose/cells.py:65-110,
+    behind a DataLoader): one item per pose - the pose's own cell, its hint sentences (evaluation.create_hint_description) shuffled
+    and joined with spaces, the cell flipped horizontally and / or vertically with probability 1/2 each (the text with it), every
+    object resampled to n_pts points, rotated about z by an angle in +-rotate_degrees and normalised (training/coarse.py:192-198).
+    Everything random about the item of pose p in epoch e is a function of (seed, e, p) alone - the sampling keys and angles of
+    sample index e * n_poses + p (pipeline.PerCellTransform), the two flip bits, the hint permutation - never of the batch size, the
+    batch order or what was drawn before; the epoch's order is a permutation seeded by (seed, e) when `shuffle`; the last short
+    batch is kept (DataLoader's default).
+    With `scene` (scene.DeviceScene of scenes.all_cells, built with mirror=True when flip_poses) a batch is {"texts", "cell_ids",
+    "pose_indices", "scene_batch"}: scene_batch = {obj_ids, keys, flip, rot, cell_ptr, n_pts}, which
+    CellRetrievalNetwork.encode_scene_batch packs with one kernel launch (train_epoch does that).  Without one, or with host=True,
+    a batch is the reference's dictionary {"texts", "objects" (the flipped copies), "object_points", "cell_ids", "pose_indices"} built
+    by the host chain (data.flip_cell, PerCellTransform.for_cell) from the same draws: the same packed arrays, bit for bit.
+    Not built: sample_close_cell."""
+
+    def __init__(self, scenes, scene=None, n_pts: int = 256, seed: int = 0, batch_size: int = 64, shuffle: bool = True,
+                 shuffle_hints: bool = True, flip_poses: bool = True, rotate_degrees: Optional[float] = 120.0, host: bool = False):
+        from .evaluation import create_hint_description
+        from .pipeline import PerCellTransform
+        self.scenes, self.scene, self.host = scenes, scene, bool(host) or scene is None
+        self.n_pts, self.seed, self.batch_size = int(n_pts), int(seed), int(batch_size)
+        self.shuffle, self.shuffle_hints, self.flip_poses = bool(shuffle), bool(shuffle_hints), bool(flip_poses)
+        self.transform = PerCellTransform(self.n_pts, self.seed, rotate_degrees)
+        self.poses = scenes.all_poses
+        self.hints = [create_hint_description(p) for p in self.poses]
+        self.epoch = 0
+        if self.batch_size < 1:
+            raise ValueError("SceneCoarseFeed: batch_size must be at least 1")
+        missing = [p.cell_id for p in self.poses if p.cell_id not in scenes.cells_dict]
+        if missing:
+            raise ValueError(f"SceneCoarseFeed: {len(missing)} poses lie in cells the scene does not hold (first: {missing[0]})")
+        if not self.host:
+            if self.flip_poses and scene.raw_mirror_xy is None:
+                raise RuntimeError("SceneCoarseFeed: flip_poses needs a DeviceScene built with mirror=True")
+            if len(scene.cell_ids) < len(scenes.all_cells) or any(a != c.id for a, c in zip(scene.cell_ids, scenes.all_cells)):
+                raise RuntimeError("SceneCoarseFeed: the DeviceScene does not hold scenes.all_cells in order")
+            self._row = np.array([scene.row_of[p.cell_id] for p in self.poses], dtype=np.int64)
+
+    def set_epoch(self, epoch: int):
+        self.epoch = int(epoch)
+
+    def __len__(self) -> int:
+        return (len(self.poses) + self.batch_size - 1) // self.batch_size
+
+    # ---- the draws of one item: functions of (seed, epoch, pose index) -----------------------------------------------------------
+    def sample_index(self, pose_index, epoch: Optional[int] = None):
+        """epoch * n_poses + pose: the PerCellTransform sample whose keys draw the item's points and angles."""
+        e = self.epoch if epoch is None else int(epoch)
+        return e * len(self.poses) + np.asarray(pose_index, dtype=np.int64)
+
+    def _item_key(self, pose_index, epoch=None) -> np.ndarray:
+        return D.sample_keys(self.seed ^ _ITEM_SALT, self.sample_index(pose_index, epoch), 0)
+
+    def flip_codes(self, pose_index, epoch: Optional[int] = None) -> np.ndarray:
+        """uint8 codes of the poses' items: bit 0 = horizontal flip, bit 1 = vertical flip; two independent fair draws."""
+        idx = np.atleast_1d(np.asarray(pose_index, dtype=np.int64))
+        if not self.flip_poses:
+            return np.zeros(idx.shape[0], dtype=np.uint8)
+        return (D.mix64(self._item_key(idx, epoch) ^ _FLIP_SALT) >> np.uint64(62)).astype(np.uint8)
+
+    def _hint_orders(self, idx: np.ndarray, item: np.ndarray) -> list:
+        """hint_order of the poses `idx` with item keys `item`, one hash matrix for all of them."""
+        counts = [len(self.hints[int(p)]) for p in idx]
+        if not self.shuffle_hints or not counts:
+            return [np.arange(c) for c in counts]
+        with np.errstate(over="ignore"):
+            h = D.mix64(item[:, None] ^ _HINT_SALT ^ (np.arange(max(counts), dtype=np.uint64) * D._KEY_MUL)[None, :])
+        if min(counts) == max(counts):
+            return list(np.argsort(h, axis=1, kind="stable"))
+        return [np.argsort(h[r, :c], kind="stable") for r, c in enumerate(counts)]
+
+    def hint_order(self, pose_index: int, epoch: Optional[int] = None) -> np.ndarray:
+        """The order the item's hints are joined in: a permutation (the ranks of one hash per hint), the identity without
+        shuffle_hints."""
+        idx = np.array([int(pose_index)], dtype=np.int64)
+        return self._hint_orders(idx, self._item_key(idx, epoch))[0]
+
+    def _texts(self, idx: np.ndarray, codes: np.ndarray, item: np.ndarray) -> list:
+        out = []
+        for p, code, order in zip(idx, codes, self._hint_orders(idx, item)):
+            hints = self.hints[int(p)]
+            text = " ".join(hints[int(j)] for j in order)
+            if code & 1:
+                text = D._swap_words(text, "east", "west")
+            if code & 2:
+                text = D._swap_words(text, "north", "south")
+            out.append(text)
+        return out
+
+    def text(self, pose_index: int, epoch: Optional[int] = None) -> str:
+        """The item's description: hints in hint_order joined with spaces (cells.py:79-82), then flipped like the cell."""
+        idx = np.array([int(pose_index)], dtype=np.int64)
+        return self._texts(idx, self.flip_codes(idx, epoch), self._item_key(idx, epoch))[0]
+
+    def epoch_order(self, epoch: Optional[int] = None) -> np.ndarray:
+        e = self.epoch if epoch is None else int(epoch)
+        n = len(self.poses)
+        return np.random.default_rng([self.seed & 0xFFFFFFFF, e, 0x6F72646572]).permutation(n) if self.shuffle else np.arange(n)
+
+    # ---- batches -----------------------------------------------------------------------------------------------------------------
+    def batch(self, pose_indices, epoch: Optional[int] = None) -> dict:
+        idx = np.asarray(pose_indices, dtype=np.int64)
+        codes, si = self.flip_codes(idx, epoch), self.sample_index(idx, epoch)
+        out = dict(texts=self._texts(idx, codes, self._item_key(idx, epoch)), cell_ids=[self.poses[int(p)].cell_id for p in idx],
+                   pose_indices=idx)
+        if self.host:
+            objects, points = [], []
+            for p, code, s in zip(idx, codes, si):
+                cell, _ = D.flip_cell_code(self.scenes.cells_dict[self.poses[int(p)].cell_id], "", int(code))
+                objs = cell.objects if isinstance(cell.objects, list) else list(cell.objects)
+                objects.append(objs)
+                points.append(D.batch_object_points(objs, self.transform.for_cell(int(s))))
+            out.update(objects=objects, object_points=points)
+            return out
+        cp_all = self.scene.cell_ptr
+        rows = self._row[idx]
+        n = cp_all[rows + 1] - cp_all[rows]
+        cell_ptr = np.zeros(idx.shape[0] + 1, dtype=np.int32)
+        np.cumsum(n, out=cell_ptr[1:])
+        start = np.repeat(cell_ptr[:-1].astype(np.int64), n)
+        slot = np.arange(int(cell_ptr[-1]), dtype=np.int64) - start
+        obj_ids = np.repeat(cp_all[rows], n) + slot
+        sample = np.repeat(si, n)
+        out["scene_batch"] = dict(obj_ids=obj_ids, keys=self.transform.keys(sample, slot),
+                                  flip=np.repeat(codes, n) if self.flip_poses else None,
+                                  rot=self.transform.rotations(sample, slot), cell_ptr=cell_ptr, n_pts=self.n_pts)
+        return out
+
+    def __iter__(self):
+        epoch = self.epoch
+        order = self.epoch_order(epoch)
+        for a in range(0, order.shape[0], self.batch_size):
+            yield self.batch(order[a: a + self.batch_size], epoch)
 
 
 def _hits(output, batch, criterion=None):

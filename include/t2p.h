@@ -187,9 +187,11 @@ typedef struct t2p_cell_config {
     /* A/B switch between equivalent execution plans (0 = the default plan):
      *   bit 0: keep the edge rows of repeated points in SA level 1's row lists (default: t2p_dedup_rows drops them; every
      *          output bit is the same either way)
-     *   bit 2: keep the edge rows of repeated centroids in the row list of SA level 2 (default: the centroids FPS
-     *          repeats once an object's distinct positions are used up share one copy of their rows, see
-     *          t2p_group_rows_shared; every output bit is the same either way)
+     *   bit 2: keep the FULL row lists of SA levels 2 and 3: the edge rows of repeated centroids at SA level 2 (default: the
+     *          centroids FPS repeats once an object's distinct positions are used up share one copy of their rows, see
+     *          t2p_group_rows_shared) and, at both levels, the rows whose source is a repeated dense point (default with
+     *          self_loops = 0 in the plan of bit 3 clear: they leave the lists, see t2p_group_rows_pruned); every output bit
+     *          is the same either way
      *   bit 3: SA level 1's rows listed by the scan kernel and pruned in place by t2p_dedup_rows, as before (default, at 256
      *          points per object and with bit 0 clear: the scan publishes each centroid's hit mask and one builder kernel
      *          writes the pruned list once, see t2p_group_rows_built; the list is the same bit for bit)
@@ -625,14 +627,29 @@ int t2p_group_rows_shared(const float* xyz, int64_t n_obj, int32_t n_pts, const 
                           int32_t share_mask, uint8_t* const* fps_idx /*[3]*/, uint16_t* const* rows /*[3]*/,
                           uint16_t* const* n_rows /*[3]*/, t2p_stream_t stream);
 /* t2p_group_rows_shared followed by t2p_dedup_rows on level 1's list, as t2p_encode_cells runs them by default: the same
- * fps_idx, lists, counts and terminators, bit for bit.  The scan kernel lists levels 2 and 3 as usual; of level 1 it writes only
- * each centroid's 256-bit hit mask (into rows[0], which is workspace until the call returns its list there) and stops at the
- * first tail centroid; a builder kernel then applies the 32-neighbour cap in point order, drops the rows of repeated points
- * (the repeat test of t2p_dedup_rows: rgb is compared too) and writes the list once.  n_pts must be 256; xyz, rgb and rows[0]
- * 16-byte aligned. */
+ * fps_idx, lists, counts and terminators, bit for bit.  Of level 1 the scan kernel writes only each centroid's 256-bit hit mask
+ * (into rows[0], which is workspace until the call returns its list there) and stops at the first tail centroid; a builder
+ * kernel then applies the 32-neighbour cap in point order, drops the rows of repeated points (the repeat test of
+ * t2p_dedup_rows: rgb is compared too) and writes the list once.  Levels 2 and 3 run no FPS: they pick the prefix of level 1's
+ * picks, and the builder runs their ball queries one lane per centroid.  n_pts must be 256; xyz, rgb and rows 16-byte aligned. */
 int t2p_group_rows_built(const float* xyz, const float* rgb, int64_t n_obj, int32_t n_pts, const float* radius_host /*[3]*/,
                          int32_t self_loops, int32_t share_mask, uint8_t* const* fps_idx /*[3]*/, uint16_t* const* rows /*[3]*/,
                          uint16_t* const* n_rows /*[3]*/, t2p_stream_t stream);
+/* t2p_group_rows_built with the lists of SA levels 2 and 3 as t2p_encode_cells consumes them when self_loops = 0: without the
+ * rows whose SOURCE is a repeated dense point.  Let k1 be level 1's first tail centroid (128: none).  Levels 2 and 3 pick the prefix of
+ * level 1's picks (fps_idx[l][c] = c below k1, 0 from there on), so dense point j >= k_prev - k_prev = k1 at level 2, min(k1, 64)
+ * at level 3 - is a tail centroid of the level below: it stands at dense point 0's position and carries row 0's features bit for
+ * bit.  Dense point 0 is in range whenever j is and is always inside the 32-neighbour cap, so the row of j repeats a row the
+ * centroid already has and the max-aggregate does not change.  The repeats are a suffix of the index order: a centroid's list
+ * holds its first 32 hits among the dense points below k_prev; the shared copy of level 2's tail rows is cut the same way.
+ * Self-loop rows, row order, tags, n_rows and the terminator are those of t2p_group_rows_built.  The premise holds only for
+ * a model WITHOUT self-loop rows: a self-loop row takes its source from another object's rows (row sbase + c of the cell's
+ * flattened batch, torch_geometric's index aliasing), which makes every tail centroid's output row its own - so
+ * t2p_encode_cells consumes these lists only when self_loops = 0; the export itself lists by geometry alone, whatever
+ * self_loops says.  Same arguments; for inspection and tests (t2p_edge_counts / t2p_edge_expand take full lists only). */
+int t2p_group_rows_pruned(const float* xyz, const float* rgb, int64_t n_obj, int32_t n_pts, const float* radius_host /*[3]*/,
+                          int32_t self_loops, int32_t share_mask, uint8_t* const* fps_idx /*[3]*/, uint16_t* const* rows /*[3]*/,
+                          uint16_t* const* n_rows /*[3]*/, t2p_stream_t stream);
 int t2p_edge_counts(const uint16_t* rows, const uint16_t* n_rows, const int32_t* first_obj, int64_t n_obj, int32_t n_dense,
                     int32_t n_cent, int32_t self_loops, int32_t* counts, t2p_stream_t stream);
 int t2p_edge_expand(const uint16_t* rows, const uint16_t* n_rows, const int32_t* first_obj, const int32_t* cent_ptr, int64_t n_obj,

@@ -10,6 +10,13 @@ NumPy FPS / ball query with the pinned semantics of csrc/sample_group.hip: fp32,
 first <= 32 hits in ascending index, one self-loop row per centroid.  Prints, per level: rows per object (level 1 also after the
 point dedup of t2p_dedup_rows), objects with a tail, tail centroids, the non-self rows of tail centroids, and the rows the
 specialised kernels execute with the tail shared (all rows - tail rows + one shared copy per object that has a tail).
+
+Duplicate sources (SA levels 2 and 3): a dense point j >= k_prev of level l + 1 is a tail centroid of level l - it stands at dense
+point 0's position and, in a model without self-loop rows, carries row 0's features - so its edge rows repeat rows their centroids
+already have and leave the lists (GroupTables::prune_dup; with self-loop rows a tail centroid's output row is its own and the
+encoder keeps the full lists).  k1 = the first tail centroid of level 1 (128: none); k_prev = k1 at level 2, min(k1, 64) at level 3.
+The last two columns count, cap first and then drop, the rows the kernels execute without them (SA2's tail sharing kept) and the
+objects that have such dense points.
 """
 import argparse
 import os
@@ -40,6 +47,23 @@ def level(pos: np.ndarray, r: float):
         mind = np.minimum(mind, d2)
         cur = int(np.argmax(mind))                                             # ties -> lowest index
     return fps, cnt
+
+
+def capped_hits(pos: np.ndarray, fps: np.ndarray, r: float):
+    """The kept hits of every centroid of one level: the first <= 32 in-range dense points in ascending index."""
+    r2 = np.float32(r) * np.float32(r)
+    out = []
+    for c in fps:
+        d = pos - pos[c]
+        d2 = (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
+        out.append(np.flatnonzero(d2 < r2)[:MAX_NBR])
+    return out
+
+
+def first_tail(fps: np.ndarray) -> int:
+    """The first tail centroid (c > 0, fps[c] == 0) of a level; len(fps) when it has none."""
+    t = np.flatnonzero((fps == 0) & (np.arange(len(fps)) > 0))
+    return int(t[0]) if len(t) else len(fps)
 
 
 def dedup_hits(pos: np.ndarray, rgb: np.ndarray, fps: np.ndarray, r: float) -> int:
@@ -74,6 +98,8 @@ def main():
     tail_rows = np.zeros(3)       # non-self rows of tail centroids
     executed = np.zeros(3)        # rows with the tail shared
     cents = np.zeros(3)
+    pruned = np.zeros(3)          # executed rows without the rows of repeated dense points (levels 2 and 3)
+    with_dup = np.zeros(3)        # objects with repeated dense points at the level
     for o in range(n):
         pos = xyz[o].astype(np.float32)
         for l in range(3):
@@ -90,13 +116,25 @@ def main():
             executed[l] += all_rows - t_rows + (cnt[0] if tail.any() else 0)
             if l == 0:
                 rows_dedup += dedup_hits(pos, rgb[o].astype(np.float32), fps, RADII[0]) + n_c
+                k1 = first_tail(fps)
+                pruned[0] += all_rows
+            else:
+                k_prev = min(k1, pos.shape[0])
+                hits = capped_hits(pos, fps, RADII[l])
+                shared = l == 1 and tail.any()      # SA2: the tail's hits are listed once
+                listed = [c for c in range(n_c) if not (shared and tail[c])] + ([first_tail(fps)] if shared else [])
+                pruned[l] += sum(int((hits[c] < k_prev).sum()) for c in listed) + n_c
+                with_dup[l] += k_prev < pos.shape[0]
             pos = pos[fps]
     print(f"{n} objects of seed {args.seed}")
-    print("level | rows/object | objects with a tail | tail centroids | tail rows (non-self) | rows/object, tail shared")
+    print("level | rows/object | objects with a tail | tail centroids | tail rows (non-self) | rows/object, tail shared | "
+          "rows/object, duplicate sources dropped | objects with repeated dense points")
     for l in range(3):
         extra = f" ({rows_dedup / n:.0f} after point dedup)" if l == 0 else ""
         print(f"SA{l + 1}   | {rows[l] / n:8.0f}{extra} | {100 * with_tail[l] / n:5.1f} % | {100 * tail_cent[l] / cents[l]:5.1f} % | "
-              f"{100 * tail_rows[l] / rows[l]:5.1f} % | {executed[l] / n:8.0f} ({100 * (executed[l] / rows[l] - 1):+.1f} %)")
+              f"{100 * tail_rows[l] / rows[l]:5.1f} % | {executed[l] / n:8.0f} ({100 * (executed[l] / rows[l] - 1):+.1f} %) | "
+              + (f"{pruned[l] / n:8.0f} ({100 * (pruned[l] / (executed[l] if l == 1 else rows[l]) - 1):+.1f} %) | {100 * with_dup[l] / n:5.1f} %"
+                 if l else "       - |     -"))
 
 
 if __name__ == "__main__":

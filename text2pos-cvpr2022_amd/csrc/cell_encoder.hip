@@ -251,9 +251,15 @@ int Chunk::group(const float* xyz, const float* rgb, bool want_nbr) const {
     // lists every hit and k_dedup_rows prunes the list in place, as before (the same list, bit for bit)
     const bool prune_l0 = !(cfg.tuning & 1) && cfg.n_pts == 256;
     gt.mask_l0 = prune_l0 && !(cfg.tuning & 8) && !want_nbr && gt.rows[0] && gt.rows[1] && gt.rows[2] ? 1 : 0;
+    // levels 2 and 3 of that plan: the rows whose source is a repeated dense point (a tail centroid of the level below) leave the
+    // lists too (GroupTables::prune_dup; -5.5 % / -6.6 % rows on the synthetic cells); tuning bit 2 keeps the full lists.
+    // WITHOUT self-loop rows only: a self-loop row takes its source from another object's rows (row sbase + c of the cell's
+    // flattened batch, PyG's index aliasing), so with them a tail centroid's output row is max(centroid 0's hits, a row of its
+    // own) - not centroid 0's row - and the dense point it becomes one level up repeats nothing
+    gt.prune_dup[1] = gt.prune_dup[2] = gt.mask_l0 && !(cfg.tuning & 4) && !cfg.self_loops ? 1 : 0;
     T2P_TRY(launch_sample_group(xyz, n, cfg.n_pts, cfg.radius, gt, st));
     if (gt.mask_l0)
-        T2P_TRY(launch_build_rows(xyz, rgb, gt.fps_idx[0], n, cfg.n_pts, gt.rows[0], gt.n_rows[0], gt.self_loops, st));
+        T2P_TRY(launch_build_rows(xyz, rgb, n, cfg.n_pts, cfg.radius, gt, st));
     else if (prune_l0)
         T2P_TRY(launch_dedup_rows(xyz, rgb, n, cfg.n_pts, gt.rows[0], gt.n_rows[0], g.nc[0], st));
     // the per-centroid row counts of all three levels exist now: cut every level's balanced object ranges at once
@@ -533,6 +539,24 @@ int group_rows(const char* what, const float* xyz, int64_t n_obj, int32_t n_pts,
     return launch_sample_group(xyz, n_obj, n_pts, radius_host, gt, (hipStream_t)stream);
 }
 
+// t2p_group_rows_built (prune_dup = 0) and t2p_group_rows_pruned
+int group_rows_built(const char* what, const float* xyz, const float* rgb, int64_t n_obj, int32_t n_pts, const float* radius_host,
+                     int32_t self_loops, int32_t share_mask, int prune_dup, uint8_t* const* fps_idx, uint16_t* const* rows,
+                     uint16_t* const* n_rows, t2p_stream_t stream) {
+    T2P_CHECK_ARG(xyz && rgb && radius_host && fps_idx && rows && n_rows, "%s: NULL argument", what);
+    T2P_CHECK_ARG(n_obj >= 0, "%s: negative size", what);
+    T2P_CHECK_ARG((share_mask & ~2) == 0, "%s: share_mask=%#x (bit 1: SA level 2; no other level has a shared form)", what, share_mask);
+    T2P_CHECK_ARG(n_pts == 256, "%s: built for 256 points per object (n_pts = %d)", what, n_pts);
+    GroupTables gt;
+    T2P_TRY(fill_group_tables(what, gt, n_pts, self_loops, share_mask, fps_idx, rows, n_rows, nullptr, nullptr));
+    gt.mask_l0 = 1;
+    gt.prune_dup[1] = gt.prune_dup[2] = prune_dup;
+    T2P_CHECK_ARG((((uintptr_t)xyz | (uintptr_t)rgb | (uintptr_t)rows[0] | (uintptr_t)rows[1] | (uintptr_t)rows[2]) & 15) == 0,
+                  "%s: xyz, rgb and rows must be 16-byte aligned", what);
+    T2P_TRY(launch_sample_group(xyz, n_obj, n_pts, radius_host, gt, (hipStream_t)stream));
+    return launch_build_rows(xyz, rgb, n_obj, n_pts, radius_host, gt, (hipStream_t)stream);
+}
+
 }  // namespace
 }  // namespace t2p
 
@@ -699,16 +723,13 @@ int t2p_group_rows_shared(const float* xyz, int64_t n_obj, int32_t n_pts, const 
 int t2p_group_rows_built(const float* xyz, const float* rgb, int64_t n_obj, int32_t n_pts, const float* radius_host,
                          int32_t self_loops, int32_t share_mask, uint8_t* const* fps_idx, uint16_t* const* rows,
                          uint16_t* const* n_rows, t2p_stream_t stream) {
-    T2P_CHECK_ARG(xyz && rgb && radius_host && fps_idx && rows && n_rows, "group_rows_built: NULL argument");
-    T2P_CHECK_ARG(n_obj >= 0, "group_rows_built: negative size");
-    T2P_CHECK_ARG((share_mask & ~2) == 0, "group_rows_built: share_mask=%#x (bit 1: SA level 2; no other level has a shared form)", share_mask);
-    T2P_CHECK_ARG(n_pts == 256, "group_rows_built: built for 256 points per object (n_pts = %d)", n_pts);
-    GroupTables gt;
-    T2P_TRY(fill_group_tables("group_rows_built", gt, n_pts, self_loops, share_mask, fps_idx, rows, n_rows, nullptr, nullptr));
-    gt.mask_l0 = 1;
-    T2P_CHECK_ARG((((uintptr_t)xyz | (uintptr_t)rgb | (uintptr_t)rows[0]) & 15) == 0, "group_rows_built: xyz, rgb and rows[0] must be 16-byte aligned");
-    T2P_TRY(launch_sample_group(xyz, n_obj, n_pts, radius_host, gt, (hipStream_t)stream));
-    return launch_build_rows(xyz, rgb, gt.fps_idx[0], n_obj, n_pts, gt.rows[0], gt.n_rows[0], gt.self_loops, (hipStream_t)stream);
+    return group_rows_built("group_rows_built", xyz, rgb, n_obj, n_pts, radius_host, self_loops, share_mask, 0, fps_idx, rows, n_rows, stream);
+}
+
+int t2p_group_rows_pruned(const float* xyz, const float* rgb, int64_t n_obj, int32_t n_pts, const float* radius_host,
+                          int32_t self_loops, int32_t share_mask, uint8_t* const* fps_idx, uint16_t* const* rows,
+                          uint16_t* const* n_rows, t2p_stream_t stream) {
+    return group_rows_built("group_rows_pruned", xyz, rgb, n_obj, n_pts, radius_host, self_loops, share_mask, 1, fps_idx, rows, n_rows, stream);
 }
 
 }  // extern "C"

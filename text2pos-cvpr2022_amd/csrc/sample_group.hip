@@ -23,6 +23,17 @@ namespace {
 #ifndef T2P_FPS_PK
 #define T2P_FPS_PK 1
 #endif
+// T2P_PREFIX_FPS: in the mask-mode plan levels 2 and 3 run no FPS: their picks are the prefix of level 1's, and k_build_rows runs
+// their ball queries one lane per centroid (0: the scan kernel runs level_fast for them, as in list mode)
+#ifndef T2P_PREFIX_FPS
+#define T2P_PREFIX_FPS 1
+#endif
+// T2P_PRUNE_ROWS: GroupTables::prune_dup is honoured (0: the field is ignored, levels 2 and 3 keep the rows of repeated dense
+// points).  The pruned form is written by k_build_rows only, so it needs T2P_PREFIX_FPS.
+#ifndef T2P_PRUNE_ROWS
+#define T2P_PRUNE_ROWS T2P_PREFIX_FPS
+#endif
+static_assert(T2P_PREFIX_FPS || !T2P_PRUNE_ROWS, "T2P_PRUNE_ROWS needs T2P_PREFIX_FPS");
 
 constexpr int kMaxPts = 256;
 constexpr int kMaxNbr = 32;
@@ -182,6 +193,7 @@ __device__ void level(const float* px, const float* py, const float* pz, int n_d
 // the scalar unit.  No hit ranks, no row stores: the four ballots go to `rows_out` as [centroid][PPL x u64] (lane 0, two
 // 16-byte stores).  The scan stops at the first tail centroid: the later ones are point 0 (argument above) and k_build_rows
 // gives them centroid 0's mask, so their slots are not written.  Same dist2 bits, same fps_idx, same centroid positions.
+// In mask mode *n_rows_out receives k1, the index of the first tail centroid (n_c when the level has no tail).
 template <int PPL, bool SHARE = false, bool MASK = false>
 __device__ void level_fast(const float* px, const float* py, const float* pz, int n_c, float r2, uint8_t* sel, float* qx,
                            float* qy, float* qz, uint16_t* __restrict__ rows_out, int self_loops, int* n_rows_out,
@@ -201,6 +213,7 @@ __device__ void level_fast(const float* px, const float* py, const float* pz, in
     }
     int cur = 0;
     int base = 0;
+    [[maybe_unused]] int k1 = n_c;   // MASK: the first tail centroid
     [[maybe_unused]] bool tail_open = false;   // SHARE: the tail's hits are in the list
     for (int c = 0; c < n_c; c++) {
         if constexpr (MASK) {
@@ -212,6 +225,7 @@ __device__ void level_fast(const float* px, const float* py, const float* pz, in
                     qy[t] = y0;
                     qz[t] = z0;
                 }
+                k1 = c;
                 break;
             }
         }
@@ -335,7 +349,10 @@ __device__ void level_fast(const float* px, const float* py, const float* pz, in
     if constexpr (!MASK) {
         if (lane < 4 && base + lane < n_c * (kMaxNbr + 1)) rows_out[base + lane] = 0xFFFF;
     }
-    *n_rows_out = base;
+    if constexpr (MASK)
+        *n_rows_out = k1;
+    else
+        *n_rows_out = base;
     __syncthreads();
 }
 
@@ -461,9 +478,32 @@ __global__ __launch_bounds__(64, T2P_SG_WAVES) void k_sample_group(const float* 
                             {p2, p2 + kMaxPts / 4, p2 + kMaxPts / 2},
                             {p3, p3 + kMaxPts / 8, p3 + kMaxPts / 4}};
         const float rr[3] = {r0 * r0, r1 * r1, r2 * r2};
+        [[maybe_unused]] int k1 = kMaxPts / 2;   // MASK: level 0's first tail centroid (128: no tail)
 #pragma unroll
         for (int l = 0; l < 3; l++) {
             const int n_d = gt.n_dense[l], n_c = gt.n_cent[l];
+            if (FAST && MASK && T2P_PREFIX_FPS && l > 0) {
+                // Levels 2 and 3 of the mask-mode plan run no FPS.  Level l + 1 samples from level l's picks in pick order, starting
+                // at index 0, and the running minimum of a subset member at step c is the set of dist2 bits level 1 held for that
+                // point at its step c: pick c of level 1 attains the maximum over the subset too, any member that ties with it has a
+                // higher subset index, and once level 1 is out of distinct positions (c >= k1) every minimum is 0 and the tie goes
+                // to index 0.  So fps_idx[l][c] = c below k1 and 0 from there on, and the centroid positions are the first n_c
+                // entries of level 1's (its tail entries hold point 0's position already).  The row lists and n_rows of these
+                // levels are written by k_build_rows.
+                uint8_t* g_sel = gt.fps_idx[l] + o * (int64_t)n_c;
+                for (int i = lane; i < n_c; i += 64) g_sel[i] = (uint8_t)(i < k1 ? i : 0);
+                if (gt.B[l] != nullptr || gt.tail[l] != nullptr) {
+                    const float* wpl = gt.wp[l];
+                    asm volatile("" : "+s"(wpl));
+                    const int t_rows = gt.tail_rows[l] > n_c ? gt.tail_rows[l] : n_c;
+                    emit_centroid_table(pin[1][0], pin[1][1], pin[1][2], n_c, wpl, gt.H[l],
+                                        gt.B[l] ? gt.B[l] + o * (int64_t)n_c * gt.H[l] : nullptr,
+                                        gt.tail[l] ? gt.tail[l] + o * (int64_t)t_rows * gt.ld_tail[l] : nullptr, gt.ld_tail[l],
+                                        gt.tail_col0[l], l == 2 ? 8 : 1, t_rows);
+                }
+                if (l == 2) __syncthreads();   // the next object's level 1 overwrites the positions
+                continue;
+            }
             if (want_nbr) {  // unused neighbour slots are zero-filled so that the table is deterministic
                 for (int i = lane; i < n_c * kMaxNbr / 4; i += 64) ((uint32_t*)nbr_lds)[i] = 0u;
             }
@@ -473,10 +513,11 @@ __global__ __launch_bounds__(64, T2P_SG_WAVES) void k_sample_group(const float* 
             // wave and capped the occupancy at 11 waves per CU, and this kernel is latency-bound (half the waves: +64 % time)
             uint16_t* g_rows16 = gt.rows[l] ? gt.rows[l] + o * (int64_t)(n_c * (kMaxNbr + 1)) : nullptr;
             if constexpr (FAST) {
-                if (l == 0 && MASK)
+                if (l == 0 && MASK) {
                     level_fast<4, false, MASK>(pin[l][0], pin[l][1], pin[l][2], n_c, rr[l], sel_lds, pin[l + 1][0], pin[l + 1][1],
                                                pin[l + 1][2], g_rows16, gt.self_loops, &n_rows);
-                else if (l == 0)
+                    k1 = n_rows;
+                } else if (l == 0)
                     level_fast<4>(pin[l][0], pin[l][1], pin[l][2], n_c, rr[l], sel_lds, pin[l + 1][0], pin[l + 1][1],
                                   pin[l + 1][2], g_rows16, gt.self_loops, &n_rows);
                 else if (l == 1 && gt.share_tail[1])
@@ -649,9 +690,58 @@ __device__ __forceinline__ int wave_inclusive_sum(int v) {
     return v;
 }
 
-__global__ __launch_bounds__(64) void k_build_rows(const float* __restrict__ xyz, const float* __restrict__ rgb,
+// Levels 2 and 3 in the builder (T2P_PREFIX_FPS): their centroids are the first 64 / 32 of level 1's picks (k_sample_group writes
+// fps_idx and the centroid tables by that rule), so no centroid waits for another: lane c measures centroid c against the dense
+// points j = 0, 1, .. (level 1's picks; one pass serves both levels, the pair (j, c) has the same positions in both) with the
+// operand order of the scan - point minus centroid, (xx + yy) + zz, strict < - and keeps a 128-bit and a 64-bit hit mask.
+// The pass stops at k1: the dense points from there on repeat dense point 0's position.
+struct BuildUpper {
+    uint16_t* rows[2];     // row lists of level index 1 and 2
+    uint16_t* n_rows[2];
+    float rr[2];           // squared radii
+    int share;             // GroupTables::share_tail[1]
+    int prune[2];          // GroupTables::prune_dup[1], [2]
+};
+
+// The list of one upper level from its per-lane capped hit masks (lane c = centroid c; lanes >= n_c pass n = 0): rows in centroid
+// order, hits ascending, the self-loop row behind them; assembled in LDS, stored in 16-byte pieces with the 0xFFFF terminator.
+// (the set bits are taken 32 at a time: a 64-bit ctz / clear-lowest is four times the VALU work, and this kernel is bound by VALU issue)
+template <int NW>
+__device__ __forceinline__ void store_lane_lists(uint16_t* img, uint16_t* list, uint16_t* n_rows_o, int max_rows, bool active,
+                                                 const uint32_t (&w)[NW], bool hits, int tag, int sl) {
+    const int lane = threadIdx.x;
+    int n = sl;
+#pragma unroll
+    for (int i = 0; i < NW; i++) n += hits ? __popc(w[i]) : 0;
+    n = active ? n : 0;
+    const int s = wave_inclusive_sum(n);
+    const int total = __builtin_amdgcn_readlane(s, 63);
+    int p = s - n;
+    if (active) {
+        const uint32_t t = (uint32_t)tag << 8;
+#pragma unroll
+        for (int i = 0; i < NW; i++) {
+            uint32_t x = hits ? w[i] : 0u;
+            while (x != 0) {
+                img[p++] = (uint16_t)(t | (uint32_t)(32 * i + __builtin_ctz(x)));
+                x &= x - 1;
+            }
+        }
+        if (sl) img[p] = (uint16_t)(((lane | 0x80) << 8) | lane);
+    }
+    if (lane < 12 && total + lane < max_rows) img[total + lane] = 0xFFFF;
+    __syncthreads();
+    int pieces = (total + 4 + 7) / 8;
+    pieces = pieces < max_rows / 8 ? pieces : max_rows / 8;
+    for (int i = lane; i < pieces; i += 64) ((uint4*)list)[i] = ((const uint4*)img)[i];
+    if (lane == 0) *n_rows_o = (uint16_t)total;
+    __syncthreads();
+}
+
+// (4 waves per SIMD: the 10.3 KB of LDS allow 15 waves per CU, the unrolled distance pass would otherwise take 130 registers)
+__global__ __launch_bounds__(64, 4) void k_build_rows(const float* __restrict__ xyz, const float* __restrict__ rgb,
                                                    const uint8_t* __restrict__ fps_idx, int64_t n_obj, uint16_t* rows,
-                                                   uint16_t* __restrict__ n_rows, int self_loops) {
+                                                   uint16_t* __restrict__ n_rows, int self_loops, BuildUpper up) {
     constexpr int NC = kMaxPts / 2, MAXR = NC * (kMaxNbr + 1);
     __shared__ __attribute__((aligned(16))) unsigned char smem[1024 * 4 + 2 * kMaxPts * 3 * 4];   // 10 KB >= the 8,448-byte list
     __shared__ uint8_t rep[kMaxPts];
@@ -670,6 +760,17 @@ __global__ __launch_bounds__(64) void k_build_rows(const float* __restrict__ xyz
         const uint8_t* const fo = fps_idx + o * (int64_t)NC;
         const unsigned long long ta = __ballot(lane > 0 && fo[lane] == 0), tb = __ballot(fo[lane + 64] == 0);
         const int t0 = ta != 0 ? (int)__builtin_ctzll(ta) : tb != 0 ? 64 + (int)__builtin_ctzll(tb) : NC;
+        // level 1's pick positions [3][128], behind the list image (inside the staged colours, dead by now)
+        float* const q = (float*)(smem + MAXR * 2);
+        if (T2P_PREFIX_FPS) {
+#pragma unroll
+            for (int h = 0; h < 2; h++) {
+                const int c = lane + 64 * h, i = fo[c];
+                q[c] = pxyz[i * 3];
+                q[NC + c] = pxyz[i * 3 + 1];
+                q[2 * NC + c] = pxyz[i * 3 + 2];
+            }
+        }
         const uint4* const mk = (const uint4*)list;
         int n[2], off[2];
         unsigned long long w[2][4];
@@ -722,6 +823,67 @@ __global__ __launch_bounds__(64) void k_build_rows(const float* __restrict__ xyz
         for (int i = lane; i < pieces; i += 64) ((uint4*)list)[i] = ((const uint4*)img)[i];
         if (lane == 0) n_rows[o] = (uint16_t)total;
         __syncthreads();
+        if (T2P_PREFIX_FPS) {
+            constexpr int NC1 = kMaxPts / 4, NC2 = kMaxPts / 8;
+            // t0 is k1.  Dense point j >= k1 of level 2 (and of level 3: its dense points are the prefix) stands at dense point 0's
+            // position - dist2 gives it dense point 0's bits - so the pass stops at k1 and either leaves those points out
+            // (prune_dup) or gives them dense point 0's verdict
+            const int e1 = t0, e2 = t0 < NC1 ? t0 : NC1;
+            typedef float f32x2 __attribute__((ext_vector_type(2)));
+            const float cx = q[lane], cy = q[NC + lane], cz = q[2 * NC + lane];
+            const f32x2 c2x = {cx, cx}, c2y = {cy, cy}, c2z = {cz, cz};
+            const float rr1 = up.rr[0], rr2 = up.rr[1];
+            uint32_t w1[4] = {0u, 0u, 0u, 0u}, w2[2] = {0u, 0u};
+#pragma unroll
+            for (int b = 0; b < 4; b++) {
+                if (32 * b < e1) {   // (uniform) 32 dense points per step, two per packed operation (see level_fast)
+#pragma unroll
+                    for (int u = 0; u < 32; u += 2) {
+#pragma clang fp contract(off)
+                        const int j = 32 * b + u;
+                        const f32x2 dx = *(const f32x2*)(q + j) - c2x, dy = *(const f32x2*)(q + NC + j) - c2y,
+                                    dz = *(const f32x2*)(q + 2 * NC + j) - c2z;
+                        const f32x2 xx = dx * dx, yy = dy * dy, zz = dz * dz;
+                        const f32x2 sxy = xx + yy;
+                        const f32x2 dd = sxy + zz;
+                        w1[b] |= (dd[0] < rr1 ? 1u << u : 0u) | (dd[1] < rr1 ? 2u << u : 0u);
+                        if (b < 2) w2[b] |= (dd[0] < rr2 ? 1u << u : 0u) | (dd[1] < rr2 ? 2u << u : 0u);
+                    }
+                }
+            }
+            // points from k1 on: out of the words (the last step ran past k1), then dense point 0's verdict where they are listed
+            const uint32_t v1 = !up.prune[0] && (w1[0] & 1u) ? ~0u : 0u, v2 = !up.prune[1] && (w2[0] & 1u) ? ~0u : 0u;
+#pragma unroll
+            for (int b = 0; b < 4; b++) {
+                const int live = e1 - 32 * b;   // (uniform)
+                const uint32_t keep = live >= 32 ? ~0u : live <= 0 ? 0u : (1u << live) - 1u;
+                w1[b] = (w1[b] & keep) | (v1 & ~keep);
+                if (b < 2) {
+                    const int live2 = e2 - 32 * b;
+                    const uint32_t keep2 = live2 >= 32 ? ~0u : live2 <= 0 ? 0u : (1u << live2) - 1u;
+                    w2[b] = (w2[b] & keep2) | (v2 & ~keep2);
+                }
+            }
+            // the cap: the first 32 hits in dense order
+            unsigned long long m1a = (unsigned long long)w1[0] | ((unsigned long long)w1[1] << 32);
+            unsigned long long m1b = (unsigned long long)w1[2] | ((unsigned long long)w1[3] << 32);
+            unsigned long long m2 = (unsigned long long)w2[0] | ((unsigned long long)w2[1] << 32);
+            int pc = __popcll(m1a);
+            if (pc > kMaxNbr) {
+                m1a = lowest_set_bits(m1a, kMaxNbr);
+                pc = kMaxNbr;
+            }
+            if (__popcll(m1b) > kMaxNbr - pc) m1b = lowest_set_bits(m1b, kMaxNbr - pc);
+            if (__popcll(m2) > kMaxNbr) m2 = lowest_set_bits(m2, kMaxNbr);
+            const uint32_t l1[4] = {(uint32_t)m1a, (uint32_t)(m1a >> 32), (uint32_t)m1b, (uint32_t)(m1b >> 32)};
+            const uint32_t l2[2] = {(uint32_t)m2, (uint32_t)(m2 >> 32)};
+            // level 2: with share_tail the first tail centroid lists its hits under the pseudo-centroid code, the later ones do not
+            const bool tail = up.share && lane >= t0;
+            store_lane_lists(img, up.rows[0] + o * (int64_t)(NC1 * (kMaxNbr + 1)), up.n_rows[0] + o, NC1 * (kMaxNbr + 1), true, l1,
+                             !tail || lane == t0, tail ? kSaTailCode : lane, sl);
+            store_lane_lists(img, up.rows[1] + o * (int64_t)(NC2 * (kMaxNbr + 1)), up.n_rows[1] + o, NC2 * (kMaxNbr + 1), lane < NC2, l2,
+                             true, lane, sl);
+        }
     }
 }
 
@@ -741,15 +903,30 @@ int launch_dedup_rows(const float* xyz, const float* rgb, int64_t n_obj, int n_p
     return 0;
 }
 
-int launch_build_rows(const float* xyz, const float* rgb, const uint8_t* fps_idx, int64_t n_obj, int n_pts, uint16_t* rows,
-                      uint16_t* n_rows, int self_loops, hipStream_t st) {
+int launch_build_rows(const float* xyz, const float* rgb, int64_t n_obj, int n_pts, const float radius[3], const GroupTables& gt,
+                      hipStream_t st) {
+    const uint8_t* fps_idx = gt.fps_idx[0];
+    uint16_t *rows = gt.rows[0], *n_rows = gt.n_rows[0];
+    const int self_loops = gt.self_loops;
     T2P_CHECK_ARG(n_pts == kMaxPts && xyz && rgb && fps_idx && rows && n_rows, "build_rows: built for %d points per object", kMaxPts);
     T2P_CHECK_ARG((((uintptr_t)xyz | (uintptr_t)rgb | (uintptr_t)rows) & 15) == 0, "build_rows: xyz, rgb and rows must be 16-byte aligned");
+    BuildUpper up{};
+    if (T2P_PREFIX_FPS) {
+        T2P_CHECK_ARG(gt.rows[1] && gt.rows[2] && gt.n_rows[1] && gt.n_rows[2] && (((uintptr_t)gt.rows[1] | (uintptr_t)gt.rows[2]) & 15) == 0,
+                      "build_rows: the row lists of levels 2 and 3 are written here, 16 bytes at a time");
+        for (int l = 1; l < 3; l++) {
+            up.rows[l - 1] = gt.rows[l];
+            up.n_rows[l - 1] = gt.n_rows[l];
+            up.rr[l - 1] = radius[l] * radius[l];
+            up.prune[l - 1] = T2P_PRUNE_ROWS && gt.prune_dup[l] ? 1 : 0;
+        }
+        up.share = gt.share_tail[1];
+    }
     if (n_obj == 0) return 0;
     const int64_t grid = n_obj < (int64_t)num_cus() * 64 ? n_obj : (int64_t)num_cus() * 64;
     // (not repeated under t2p_profile_repeat: the kernel consumes the masks it overwrites)
     ProfScope ps_("build_rows", st);
-    hipLaunchKernelGGL(k_build_rows, dim3((unsigned)grid), dim3(64), 0, st, xyz, rgb, fps_idx, n_obj, rows, n_rows, self_loops);
+    hipLaunchKernelGGL(k_build_rows, dim3((unsigned)grid), dim3(64), 0, st, xyz, rgb, fps_idx, n_obj, rows, n_rows, self_loops, up);
     T2P_CHECK_LAUNCH("build_rows");
     return 0;
 }
@@ -779,6 +956,8 @@ int launch_sample_group(const float* xyz, int64_t n_obj, int n_pts, const float 
                       gt.n_dense[0] == kMaxPts && gt.n_dense[1] == kMaxPts / 2 && gt.n_dense[2] == kMaxPts / 4;
     T2P_CHECK_ARG(!gt.mask_l0 || (fast && ((uintptr_t)gt.rows[0] & 15) == 0),
                   "sample_group: hit masks (mask_l0) exist for 256 points per object with all row lists wanted, rows 16-byte aligned");
+    T2P_CHECK_ARG(!(gt.prune_dup[0] || gt.prune_dup[1] || gt.prune_dup[2]) || (gt.mask_l0 && !gt.prune_dup[0]),
+                  "sample_group: prune_dup exists for levels 2 and 3 of the hit-mask plan (mask_l0)");
     if (fast && gt.mask_l0)
         T2P_REPEAT(ps_) hipLaunchKernelGGL((k_sample_group<true, true>), dim3((unsigned)grid), dim3(64), lds, st, xyz, n_obj, n_pts,
                            radius[0], radius[1], radius[2], gt);

@@ -223,6 +223,16 @@ struct GroupTables {
     // accumulator slot whose B row is centroid 0's), every tail centroid keeps its self-loop row, and the consumer's drain takes
     // max(acc[c], acc[code]) for tail centroids.  The list is then no longer sorted by centroid.
     int share_tail[3];
+    // prune_dup[l] != 0 (level index 1 and 2, mask-mode plan of the 256-point fast path only): rows whose SOURCE is a dense point
+    // j >= k_prev leave the list, the shared copy of level index 1's tail rows included; self-loop rows stay.  k1 = level 0's first
+    // tail centroid; k_prev = k1 at level index 1, min(k1, 64) at level index 2 (its dense points are the prefix of level 1's
+    // picks, so its tail starts at k1 too).  Such a point is a tail centroid of the level below: it stands at dense point 0's
+    // position and its feature row is row 0's bit for bit, so its table row A_j is A_0; dense point 0 is in range whenever j is
+    // and is first in index order, always inside the 32-cap, so relu(A_j - B_i) W2 repeats a row centroid i already has.  The
+    // repeats are a suffix of the index order: "first 32 hits, then drop them" is "first 32 hits among j < k_prev".
+    // "Row 0's features" holds WITHOUT self-loop rows only (a self-loop row reads another object's dense row, so with them every
+    // tail centroid's output row is its own): Chunk::group sets the field only then.
+    int prune_dup[3];
     // mask_l0 != 0 (256-point fast path only): level 0 leaves no list.  The kernel writes each centroid's point-ordered 256-bit
     // hit mask, [centroid][4 x u64], to the start of the object's rows[0] slice (4,096 of its 8,448 bytes) - up to the first
     // tail centroid, where it stops - and n_rows[0] is not written.  launch_build_rows turns the masks into the final list.
@@ -250,10 +260,12 @@ int launch_sample_group(const float* xyz, int64_t n_obj, int n_pts, const float 
 // (identical message, so the max-aggregate is unchanged); updates n_rows.  rows [n_obj][n_cent * 33], n_pts = 256.
 int launch_dedup_rows(const float* xyz, const float* rgb, int64_t n_obj, int n_pts, uint16_t* rows, uint16_t* n_rows,
                       int n_cent, hipStream_t st);
-// Level 0's final row lists from the hit masks of a launch_sample_group with mask_l0 (same stream, directly behind it): the
-// list launch_sample_group + launch_dedup_rows leave, bit for bit; writes n_rows.  fps_idx: level 0's.  n_pts = 256.
-int launch_build_rows(const float* xyz, const float* rgb, const uint8_t* fps_idx, int64_t n_obj, int n_pts, uint16_t* rows,
-                      uint16_t* n_rows, int self_loops, hipStream_t st);
+// Level 0's final row lists from the hit masks of a launch_sample_group with mask_l0 (same stream, directly behind it, same gt):
+// the list launch_sample_group + launch_dedup_rows leave, bit for bit; writes n_rows[0].  It also runs the ball queries of levels
+// 2 and 3, which the mask-mode scan leaves out (their centroids are the prefix of level 1's picks): rows / n_rows of level index
+// 1 and 2 in the form share_tail[1] and prune_dup ask for.  n_pts = 256.
+int launch_build_rows(const float* xyz, const float* rgb, int64_t n_obj, int n_pts, const float radius[3], const GroupTables& gt,
+                      hipStream_t st);
 
 // ---- tables.hip / small kernels ------------------------------------------------------------------------------
 // gather level-l centroid positions: out[(o*n_cent + c), 0..2]

@@ -260,10 +260,13 @@ def group_rows(xyz: torch.Tensor, radius=(0.2, 0.3, 0.4), self_loops: bool = Tru
     return out
 
 
-def group_rows_built(xyz: torch.Tensor, rgb: torch.Tensor, radius=(0.2, 0.3, 0.4), self_loops: bool = True, share_mask: int = 0):
-    """group_rows followed by dedup_rows on level 0, as the encoder runs them by default (t2p_group_rows_built): the scan
-    publishes level 0's hit masks and one builder kernel writes the pruned list.  xyz, rgb [n_obj, 256, 3] fp32.
-    Returns the dict of group_rows, bit for bit what the two calls leave."""
+def group_rows_built(xyz: torch.Tensor, rgb: torch.Tensor, radius=(0.2, 0.3, 0.4), self_loops: bool = True, share_mask: int = 0,
+                     prune_dup: bool = False):
+    """group_rows followed by dedup_rows on level 0 (t2p_group_rows_built): the scan publishes level 0's hit masks and one
+    builder kernel writes the pruned list.  xyz, rgb [n_obj, 256, 3] fp32.
+    Returns the dict of group_rows, bit for bit what the two calls leave.
+    prune_dup (t2p_group_rows_pruned): the lists the encoder consumes without self-loop rows - at SA levels 2 and 3 the rows whose source
+    is a repeated dense point (index >= k_prev, include/t2p.h) are left out as well."""
     _need(xyz, "xyz", torch.float32, 3)
     _need(rgb, "rgb", torch.float32, 3, xyz.device)
     dev = xyz.device
@@ -271,8 +274,9 @@ def group_rows_built(xyz: torch.Tensor, rgb: torch.Tensor, radius=(0.2, 0.3, 0.4
     if three != 3 or tuple(rgb.shape) != tuple(xyz.shape):
         raise RuntimeError(f"group_rows_built: xyz and rgb must both be [n_obj, n_pts, 3], got {tuple(xyz.shape)} and {tuple(rgb.shape)}")
     out, arr = _level_tables(n_obj, n_pts, dev, ("fps_idx", "rows", "n_rows"))
-    L.check(L.lib().t2p_group_rows_built(_ptr(xyz), _ptr(rgb), n_obj, n_pts, _radius(radius), int(bool(self_loops)), int(share_mask),
-                                         arr["fps_idx"], arr["rows"], arr["n_rows"], _stream(dev)), "t2p_group_rows_built")
+    name = "t2p_group_rows_pruned" if prune_dup else "t2p_group_rows_built"
+    L.check(getattr(L.lib(), name)(_ptr(xyz), _ptr(rgb), n_obj, n_pts, _radius(radius), int(bool(self_loops)), int(share_mask),
+                                   arr["fps_idx"], arr["rows"], arr["n_rows"], _stream(dev)), name)
     return out
 
 

@@ -413,6 +413,32 @@ int t2p_mse_loss_backward(const float* a, const float* b, int64_t n, const float
  * that is exactly zero: what is left of it is the rounding of the summands, and an fp32 sum would add its own on top. */
 int t2p_colsum(const float* x, int64_t rows, int32_t cols, float* out, t2p_stream_t stream);
 
+/* The statistics training/fine.py:77-112 takes from one step - calc_recall_precision (training/losses.py:33-62) and three calls of
+ * calc_pose_error (training/losses.py:81-123) with get_pos_in_cell (models/superglue_matcher.py:139-161) - in ONE launch on the
+ * model's outputs where they are: matches0 int64 [B][n_obj], matches1 int64 [B][n_hints], offsets fp32 [B][n_hints][2].  The ground
+ * truth comes from three device tables with n_rows rows (one per pose of the feed, training.SceneFineFeed), row pose_idx[b] for
+ * sample b: gt_hint int32 [n_rows][n_obj] (the hint matched to a slot, or -1), pose_xy float64 [n_rows][2], slot_center_xy float64
+ * [n_rows][n_obj][2] (the float64 object centres).  loss / loss_offsets: one fp32 value each on the device, or NULL.
+ * sample_stats float64 [B][5] = recall, precision, pose_mid, pose_mean, pose_offsets of every sample:
+ *   recall     (slots i with j = gt_hint[i] >= 0 and matches0[i] == j or matches1[j] == i) / (slots with gt_hint[i] >= 0); 0 without any
+ *   precision  (slots with matches0[i] >= 0 and gt_hint[i] == matches0[i]) / (slots with matches0[i] >= 0); 0 without any
+ *   pose_*     distance from pose_xy to the estimate: (0.5, 0.5) for pose_mid and when no slot is matched, else the mean over the
+ *              matched slots of slot_center_xy[i] (pose_mean) or of slot_center_xy[i] + double(offsets[matches0[i]]) (pose_offsets)
+ * step_row float64 [7] = double(loss), double(loss_offsets) (NaN for NULL), then the means over the samples of the five columns,
+ * summed in ascending sample order.  float64 throughout, wavefront reductions with a fixed tree, no atomics: the same bits from call
+ * to call; every output element is written.
+ * Refused before any launch (T2P_E_ARG): NULL pointers (the two losses excepted); batch, n_obj or n_hints < 1; n_obj or n_hints > 63
+ * (the token limit of t2p_match_attention); batch > T2P_FINE_STATS_MAX_BATCH (the per-sample rows of the batch reduction sit in
+ * LDS: 1024 x 5 doubles = 40 KiB); n_rows outside [1, 2^30).
+ * In the kernel a pose_idx outside [0, n_rows), a matches0 value outside [-1, n_hints), a matches1 value outside [-1, n_obj) or a
+ * gt_hint entry outside [-1, n_hints) turns the sample's row (and so the five means) into NaN; nothing is read through it -
+ * t2p_matching_loss's rule. */
+#define T2P_FINE_STATS_MAX_BATCH 1024
+int t2p_fine_step_stats(const int64_t* matches0, const int64_t* matches1, const float* offsets, const int32_t* pose_idx,
+                        int64_t batch, int32_t n_obj, int32_t n_hints, const int32_t* gt_hint, const double* pose_xy,
+                        const double* slot_center_xy, int64_t n_rows, const float* loss, const float* loss_offsets,
+                        double* sample_stats, double* step_row, t2p_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Text branch: CellRetrievalNetwork.encode_text (models/cell_retrieval.py:69-75) on token ids produced by the
  * host tokeniser of LanguageEncoder.forward (models/modules.py:60-72).

@@ -127,6 +127,8 @@ SYMBOLS = {
     "t2p_matching_loss_backward": (C.c_int, [c_void, C.c_int64, C.c_int32, C.c_int32, c_void, c_void, C.c_int64, c_void, c_void,
                                              c_void]),
     "t2p_mse_loss_backward": (C.c_int, [c_void, c_void, C.c_int64, c_void, c_void, c_void]),
+    "t2p_fine_step_stats": (C.c_int, [c_void, c_void, c_void, c_void, C.c_int64, C.c_int32, C.c_int32, c_void, c_void, c_void, C.c_int64,
+                                      c_void, c_void, c_void, c_void, c_void]),
     "t2p_colsum": (C.c_int, [c_void, C.c_int64, C.c_int32, c_void, c_void]),
     "t2p_profile_enable": (None, [C.c_int]),
     "t2p_profile_report": (C.c_int, [C.c_char_p, C.c_size_t]),

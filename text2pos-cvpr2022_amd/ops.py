@@ -1178,6 +1178,63 @@ def colsum(x: torch.Tensor) -> torch.Tensor:
     return out
 
 
+FINE_STATS_MAX_BATCH = 1024   # T2P_FINE_STATS_MAX_BATCH (include/t2p.h)
+
+
+def fine_step_row(step_row: torch.Tensor) -> np.ndarray:
+    """The host copy of fine_step_stats' step_row (ONE device-to-host copy of 56 bytes; it waits for the step): float64 [7] = loss,
+    loss_offsets, recall, precision, pose_mid, pose_mean, pose_offsets.  A NaN recall - a ratio of counts otherwise - is the
+    kernel's mark of an index it refused to read through: IndexError.  (NaN offsets of a diverged model show in pose_offsets alone.)"""
+    row = step_row.cpu().numpy()
+    if np.isnan(row[2]):
+        raise IndexError("fine_step_stats: a pose index outside the tables, or a matches0 / matches1 / gt_hint value outside its range "
+                         "(the kernel marks the sample with NaN instead of reading through it)")
+    return row
+
+
+def fine_step_stats(matches0: torch.Tensor, matches1: torch.Tensor, offsets: torch.Tensor, pose_idx: torch.Tensor,
+                    gt_hint: torch.Tensor, pose_xy: torch.Tensor, slot_center_xy: torch.Tensor, loss: Optional[torch.Tensor] = None,
+                    loss_offsets: Optional[torch.Tensor] = None, check: bool = True):
+    """training/fine.py:77-112's statistics of one step on the device (t2p_fine_step_stats): matches0 int64 [B, M], matches1 int64
+    [B, N], offsets fp32 [B, N, 2] (the model's outputs), pose_idx int32 [B] rows of the tables gt_hint int32 [n, M], pose_xy float64
+    [n, 2], slot_center_xy float64 [n, M, 2]; loss / loss_offsets: fp32 tensors of one element, or None.
+    Returns (sample_stats float64 [B, 5], step_row float64 [7]) on the device.  check (default): read step_row back and raise
+    IndexError when the kernel marked a sample (fine_step_row); a loop that reads the row anyway passes check=False and calls
+    fine_step_row itself."""
+    _need(matches0, "matches0", torch.int64, 2)
+    dev = matches0.device
+    _need(matches1, "matches1", torch.int64, 2, dev)
+    _need(offsets, "offsets", torch.float32, 3, dev)
+    _need(pose_idx, "pose_idx", torch.int32, 1, dev)
+    _need(gt_hint, "gt_hint", torch.int32, 2, dev)
+    _need(pose_xy, "pose_xy", torch.float64, 2, dev)
+    _need(slot_center_xy, "slot_center_xy", torch.float64, 3, dev)
+    b, m = matches0.shape
+    n = matches1.shape[1]
+    rows = gt_hint.shape[0]
+    if matches1.shape[0] != b or tuple(offsets.shape) != (b, n, 2) or pose_idx.shape[0] != b:
+        raise RuntimeError(f"fine_step_stats: matches0 {tuple(matches0.shape)}, matches1 {tuple(matches1.shape)}, offsets "
+                           f"{tuple(offsets.shape)} and pose_idx {tuple(pose_idx.shape)} do not describe one batch")
+    if gt_hint.shape[1] != m or tuple(pose_xy.shape) != (rows, 2) or tuple(slot_center_xy.shape) != (rows, m, 2):
+        raise RuntimeError(f"fine_step_stats: tables gt_hint {tuple(gt_hint.shape)}, pose_xy {tuple(pose_xy.shape)}, slot_center_xy "
+                           f"{tuple(slot_center_xy.shape)} must be [n, {m}], [n, 2], [n, {m}, 2]")
+    scalars = []
+    for t, name in ((loss, "loss"), (loss_offsets, "loss_offsets")):
+        if t is not None:
+            t = _need(t.detach().reshape(-1), name, torch.float32, 1, dev)
+            if t.numel() != 1:
+                raise RuntimeError(f"fine_step_stats: {name} must hold one value")
+        scalars.append(t)
+    sample_stats = torch.empty((b, 5), dtype=torch.float64, device=dev)
+    step_row = torch.empty((7,), dtype=torch.float64, device=dev)
+    L.check(L.lib().t2p_fine_step_stats(_ptr(matches0), _ptr(matches1), _ptr(offsets), _ptr(pose_idx), b, m, n, _ptr(gt_hint),
+                                        _ptr(pose_xy), _ptr(slot_center_xy), rows, _ptr(scalars[0]), _ptr(scalars[1]),
+                                        _ptr(sample_stats), _ptr(step_row), _stream(dev)), "t2p_fine_step_stats")
+    if check:
+        fine_step_row(step_row)
+    return sample_stats, step_row
+
+
 # ---------------------------------------------------------------------------------------------------------------
 def profile_enable(on: bool):
     """Bracket every kernel launch with hipEvents on its launch stream (bench.py's live per-kernel timing)."""

@@ -241,6 +241,34 @@ class SuperGlueMatch(PicklableModule):
                             matching_scores0=out["matching_scores0"], matching_scores1=out["matching_scores1"],
                             object_encodings=obj, hint_encodings=hint)
 
+    def forward_scene_batch(self, scene, scene_batch: dict, hints, want_inputs: bool = False):
+        """One batch of the fine stage packed from a scene.DeviceScene (training.SceneFineFeed builds scene_batch: `obj_ids` int
+        [B * pad_size] scene objects of the samples back to back, `keys` uint64 per slot, `cell_ptr` int32 [B + 1], the rotation
+        `rot` fp32 [n, 2] or None, `flip` None, `n_pts`): one launch of t2p_pack_scene_objects (t2p_pack_scene_objects_aug with
+        `rot`) replaces Kitti360FineDataset's host chain (dataloading/kitti360pose/poses.py:155), then forward_packed - in train()
+        with autograd inside training.fine_backward(), in train() or eval() under no_grad; its refusals are unchanged.
+        want_inputs: also return the packed (xyz, rgb, center, mean_rgb, cell_ptr)."""
+        self._check_forward_only()
+        ids = np.ascontiguousarray(scene_batch["obj_ids"], dtype=np.int64).reshape(-1)
+        cp = np.ascontiguousarray(scene_batch["cell_ptr"], dtype=np.int32)
+        if cp.shape[0] < 1 or int(cp[-1]) != ids.shape[0]:
+            raise RuntimeError("forward_scene_batch: cell_ptr does not cover obj_ids")
+        if scene_batch.get("flip") is not None:
+            raise NotImplementedError("forward_scene_batch: flips are not built for the fine stage (the reference trains it without)")
+        n_pts = int(scene_batch.get("n_pts") or getattr(self.args, "pointnet_numpoints", 256))
+        want_rgb = "color" in self.args.use_features or bool(getattr(self.args, "class_embed", False))
+        xyz, rgb, center, mean_rgb = scene.pack(ids, scene_batch["keys"], n_pts, want_rgb=want_rgb, rot=scene_batch.get("rot"))
+        if rgb is None:
+            rgb = torch.zeros_like(xyz)      # forward_packed's rule (models/object_encoder.py:86-90)
+        class_all, color_all = scene.feature_indices(self)
+        ci = co = None
+        if class_all is not None or color_all is not None:
+            sel = torch.from_numpy(ids).to(self.device)
+            ci = None if class_all is None else class_all[sel].contiguous()
+            co = None if color_all is None else color_all[sel].contiguous()
+        out = self.forward_packed(xyz, rgb, center, mean_rgb, cp, hints, ci, co)
+        return (out, (xyz, rgb, center, mean_rgb, cp)) if want_inputs else out
+
     def encode_hints(self, hints: List[List[str]]) -> torch.Tensor:
         """List[List[str]] (samples x num_hints sentences) -> [samples, num_hints, D] L2-normalised hint encodings
         (models/superglue_matcher.py:94-97)."""

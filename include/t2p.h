@@ -440,6 +440,46 @@ int t2p_fine_step_stats(const int64_t* matches0, const int64_t* matches1, const 
                         double* sample_stats, double* step_row, t2p_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Serving path (csrc/localize.hip): text queries against a database of cells that were encoded once.
+ * ---------------------------------------------------------------------------------------------------------- */
+/* t2p_match with its inputs addressed through tables: sample b matches the object tokens of database cell obj_row[b] against
+ * the hint tokens of query hint_row[b].  obj_table fp32 [n_cells][n_obj][D] and hint_table fp32 [n_queries][n_hints][D] (both
+ * 16-byte aligned), obj_row / hint_row int32 [batch] on the device.  Replaces the torch.stack of per-sample encodings of
+ * models/superglue_matcher.py:94-103 for encodings that already exist: the reference re-encodes a cell's objects for every
+ * (query, candidate) sample (dataloading/kitti360pose/eval.py:117-189, evaluation/pipeline.py:189-191).  One gather kernel
+ * copies the samples' token rows into dense desc0 / desc1 at the head of `workspace`; t2p_match then runs on the copies with
+ * the rest of it, so every output has the bits t2p_match gives on the gathered inputs.  Same limits and codes as t2p_match;
+ * n_cells, n_queries in [1, 2^30).  A sample whose obj_row or hint_row lies outside its table is never read through: its tokens
+ * are NaN, so its P is NaN and its matches are -1 (its offsets are not NaN: the offset MLP's ReLU maps NaN to 0 - a caller tells
+ * such a sample by its P, or hands the same row to t2p_localize_poses, which marks it); the other samples are unaffected. */
+size_t t2p_match_indexed_workspace_bytes(int64_t batch, int32_t n_obj, int32_t n_hints, int32_t embed_dim);
+int t2p_match_indexed(const float* obj_table, int64_t n_cells, const float* hint_table, int64_t n_queries, const int32_t* obj_row,
+                      const int32_t* hint_row, int64_t batch, int32_t n_obj, int32_t n_hints, int32_t embed_dim,
+                      const t2p_match_weights* w, int32_t sinkhorn_iters, float match_threshold, float* P, int64_t* matches0,
+                      int64_t* matches1, float* mscores0, float* mscores1, float* offsets, void* workspace, size_t workspace_bytes,
+                      t2p_stream_t stream);
+/* The pose estimates of n_queries x top_k samples (query-major: sample q top_k + c) in one launch: get_pos_in_cell
+ * (models/superglue_matcher.py:139-161), the world-coordinate step of calc_sample_accuracies (evaluation/utils.py:31-54,
+ * bbox_w + pos_in_cell * cell_size) and the confidence pick of evaluation/pipeline.py:196, :256, which the reference computes on
+ * host copies per query.  matches0 int64 [Q K][n_obj], offsets fp32 [Q K][n_hints][2] (the matcher's outputs, where they are),
+ * cell_row int32 [Q K]: the sample's row of the float64 tables center_xy [n_cells][n_obj][2] (object centres of the cell's padded
+ * slots), bbox_xy [n_cells][2], cell_size [n_cells].  Per sample: pos_mean [2] / pos_offset [2] float64 in cell units - the mean
+ * over the slots with matches0[i] >= 0 of center_xy[i] resp. center_xy[i] + double(offsets[matches0[i]]), (0.5, 0.5) when
+ * nothing matched - world_mean / world_offset [2] = bbox_xy + pos * cell_size, and matched int32 = the number of such slots.
+ * Per query: best int32 = the candidate with the largest `matched`, the first among equals.  float64 throughout, wavefront
+ * reductions with a fixed tree, no atomics: the same bits from call to call; every output element is written.
+ * Refused before any launch (T2P_E_ARG): NULL pointers; top_k outside [1, T2P_LOCALIZE_MAX_TOP_K] (the candidates' counts sit in
+ * LDS); n_obj or n_hints outside [1, 63]; n_cells outside [1, 2^30); n_queries < 0 (0 launches nothing).
+ * In the kernel a cell_row outside [0, n_cells), a matches0 value outside [-1, n_hints) or a NaN among the sample's offsets
+ * turns the sample's four rows into NaN and its `matched` into -1; nothing is read through it (t2p_fine_step_stats's rule).
+ * `best` passes such samples over and is -1 when the query has no other. */
+#define T2P_LOCALIZE_MAX_TOP_K 1024
+int t2p_localize_poses(const int64_t* matches0, const float* offsets, const int32_t* cell_row, int64_t n_queries, int32_t top_k,
+                       int32_t n_obj, int32_t n_hints, const double* center_xy, const double* bbox_xy, const double* cell_size,
+                       int64_t n_cells, double* pos_mean, double* pos_offset, double* world_mean, double* world_offset,
+                       int32_t* matched, int32_t* best, t2p_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Text branch: CellRetrievalNetwork.encode_text (models/cell_retrieval.py:69-75) on token ids produced by the
  * host tokeniser of LanguageEncoder.forward (models/modules.py:60-72).
  * ---------------------------------------------------------------------------------------------------------- */

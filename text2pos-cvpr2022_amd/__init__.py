@@ -13,3 +13,11 @@ from .object_encoder import ObjectEncoder  # noqa: F401
 from .pointnet2 import PointNet2  # noqa: F401
 from .retrieval import retrieve_topk  # noqa: F401
 from .superglue_matcher import SuperGlueMatch, get_pos_in_cell  # noqa: F401
+
+
+def __getattr__(name):
+    # CellDatabase / Localizer (localize.py, also a command: importing it here would precede `python -m text2pos_amd.localize`)
+    if name in ("CellDatabase", "Localizer"):
+        from . import localize
+        return getattr(localize, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

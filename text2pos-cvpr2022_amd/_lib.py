@@ -129,6 +129,12 @@ SYMBOLS = {
     "t2p_mse_loss_backward": (C.c_int, [c_void, c_void, C.c_int64, c_void, c_void, c_void]),
     "t2p_fine_step_stats": (C.c_int, [c_void, c_void, c_void, c_void, C.c_int64, C.c_int32, C.c_int32, c_void, c_void, c_void, C.c_int64,
                                       c_void, c_void, c_void, c_void, c_void]),
+    "t2p_match_indexed_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
+    "t2p_match_indexed": (C.c_int, [c_void, C.c_int64, c_void, C.c_int64, c_void, c_void, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                    C.POINTER(MatchWeights), C.c_int32, C.c_float, c_void, c_void, c_void, c_void, c_void, c_void,
+                                    c_void, C.c_size_t, c_void]),
+    "t2p_localize_poses": (C.c_int, [c_void, c_void, c_void, C.c_int64, C.c_int32, C.c_int32, C.c_int32, c_void, c_void, c_void,
+                                     C.c_int64, c_void, c_void, c_void, c_void, c_void, c_void, c_void]),
     "t2p_colsum": (C.c_int, [c_void, C.c_int64, C.c_int32, c_void, c_void]),
     "t2p_profile_enable": (None, [C.c_int]),
     "t2p_profile_report": (C.c_int, [C.c_char_p, C.c_size_t]),

@@ -1,0 +1,384 @@
+"""Text queries against a saved cell database: the serving path of Text2Pos on the MI355X.
+
+    python -m text2pos_amd.localize build --base_path ./data/k360_30-10_scG_pd10_pc4_spY_all/ --scenes 2013_05_28_drive_0010_sync \\
+        --path_coarse ./checkpoints/coarse.pth --path_fine ./checkpoints/fine.pth --out db.pt
+    python -m text2pos_amd.localize query --db db.pt --path_coarse ./checkpoints/coarse.pth --path_fine ./checkpoints/fine.pth \\
+        --hints "The pose is north of a gray road." "The pose is east of a green tree."
+
+The reference has no such path: the only code that chains text encoding, top-k, the fine matcher and the pose estimate is its
+evaluation (evaluation/pipeline.py:60-137, :172-279), which needs ground-truth poses and the raw scene, and re-encodes every
+candidate cell's objects per (query, candidate) sample (dataloading/kitti360pose/eval.py:117-189).  A deployed localiser's cells
+are fixed, so here they are encoded ONCE:
+
+  CellDatabase   the coarse embedding of every cell (CellRetrievalNetwork.encode_scene_cells), the fine model's object tokens of
+                 every cell's padded object list (SuperGlueMatch.encode_cell_objects), and the float64 geometry the pose estimate
+                 needs (object centres, cell corner, cell size); saved and reloaded without the scene.
+  Localizer      hints -> encode_text -> retrieve_topk on the resident embeddings -> encode_hints once per query ->
+                 t2p_match_indexed (the matcher on the database's tokens, addressed by row) -> t2p_localize_poses (get_pos_in_cell,
+                 models/superglue_matcher.py:139-161, the world coordinates and the most confident candidate, on the device).
+                 No raw points, no PointNet++, one device-to-host copy per call.
+
+The deliberate difference from the evaluation: a database cell has ONE T.FixedPoints draw, `transform.keys(row, slot)` of its
+database row, where run_fine draws once per (query, candidate) sample as the reference's dataloader does.
+"""
+import argparse
+import hashlib
+import json
+import sys
+from types import SimpleNamespace
+from typing import Dict, List, Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import ops
+from .retrieval import check_top_k, retrieve_topk
+from .superglue_matcher import MATCH_THRESHOLD
+
+FORMAT = 1
+MAX_HINTS = 63           # t2p_match's token limit
+_TENSORS = ("coarse", "fine", "center_xy", "bbox_xy", "cell_size")
+_RESULT_FIELDS = ("cell_rows", "cell_ids", "scores", "pos_in_cell_mean", "pos_in_cell", "world_xy_mean", "world_xy", "matched", "best",
+                  "best_world_xy")
+
+
+def state_hash(model) -> str:
+    """sha256 over a model's state_dict: every key in sorted order with its dtype, shape and bytes."""
+    h = hashlib.sha256()
+    sd = model.state_dict()
+    for k in sorted(sd):
+        t = sd[k].detach().cpu().contiguous()
+        h.update(k.encode())
+        h.update(f"{t.dtype}{tuple(t.shape)}".encode())
+        h.update(t.reshape(-1).view(torch.uint8).numpy().tobytes() if t.numel() else b"")
+    return h.hexdigest()
+
+
+def model_meta(model_coarse, model_fine) -> Dict[str, object]:
+    """The part of CellDatabase.meta the two models determine."""
+    return dict(hash_coarse=state_hash(model_coarse), hash_fine=state_hash(model_fine),
+                dim_coarse=int(model_coarse.embed_dim), dim_fine=int(model_fine.embed_dim),
+                precision_coarse=str(model_coarse.precision), precision_fine=str(model_fine.precision))
+
+
+def check_models(meta: Dict[str, object], model_coarse, model_fine, what: str):
+    """ValueError naming the first field of `meta` the models do not match."""
+    own = model_meta(model_coarse, model_fine)
+    for k in ("dim_coarse", "dim_fine", "precision_coarse", "precision_fine", "hash_coarse", "hash_fine"):
+        if meta.get(k) != own[k]:
+            raise ValueError(f"{what}: the database was built with {k}={meta.get(k)!r}, the model has {k}={own[k]!r}")
+
+
+def _check_transform(transform):
+    if not all(hasattr(transform, a) for a in ("keys", "n_pts", "seed")) or getattr(transform, "rotate_degrees", None) is not None:
+        raise TypeError("CellDatabase needs a pipeline.PerCellTransform without rotation: a cell's draw must depend on "
+                        "(seed, database row, slot) only")
+
+
+class CellDatabase:
+    """coarse fp32 [Nc, D_coarse], fine fp32 [Nc, pad_size, D_fine], center_xy float64 [Nc, pad_size, 2] (the object centres of
+    every cell's padded slots), bbox_xy float64 [Nc, 2], cell_size float64 [Nc], cell_ids / scene_names (lists of str), meta (plain
+    values: format, seed, n_pts, pad_size, the models' dimensions, precisions and state hashes).  A plain container: it holds CPU
+    or GPU tensors alike; only Localizer.localize needs them on the GPU."""
+
+    def __init__(self, coarse, fine, center_xy, bbox_xy, cell_size, cell_ids: Sequence[str], scene_names: Sequence[str], meta: dict):
+        self.coarse, self.fine, self.center_xy, self.bbox_xy, self.cell_size = coarse, fine, center_xy, bbox_xy, cell_size
+        self.cell_ids, self.scene_names, self.meta = [str(c) for c in cell_ids], [str(s) for s in scene_names], dict(meta)
+        n, pad = len(self.cell_ids), int(self.meta["pad_size"])
+        want = dict(coarse=((n, int(self.meta["dim_coarse"])), torch.float32), fine=((n, pad, int(self.meta["dim_fine"])), torch.float32),
+                    center_xy=((n, pad, 2), torch.float64), bbox_xy=((n, 2), torch.float64), cell_size=((n,), torch.float64))
+        for k, (shape, dtype) in want.items():
+            t = getattr(self, k)
+            if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype != dtype:
+                got = (tuple(t.shape), t.dtype) if isinstance(t, torch.Tensor) else type(t).__name__
+                raise ValueError(f"CellDatabase: {k} must be {dtype} {shape} (pad_size, dim_coarse and dim_fine from meta), got {got}")
+        if len(self.scene_names) != n:
+            raise ValueError(f"CellDatabase: scene_names has {len(self.scene_names)} entries for {n} cells")
+        if len(set(self.cell_ids)) != n:
+            raise ValueError("CellDatabase: cell_ids repeat")
+
+    def __len__(self) -> int:
+        return len(self.cell_ids)
+
+    @property
+    def device(self):
+        return self.coarse.device
+
+    # ---- building -----------------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _encode(model_coarse, model_fine, cells, transform, pad_size: int, cells_per_call: int, cell_offset: int):
+        from .scene import DeviceScene
+        scene = DeviceScene(cells, model_coarse.device, n_pad=pad_size, pad_seed=transform.seed)
+        n = scene.n_cells
+        with torch.no_grad():
+            coarse = model_coarse.encode_scene_cells(scene, transform, 0, n, cell_offset=cell_offset, cells_per_call=cells_per_call)
+            fine = [model_fine.encode_cell_objects(scene, transform, a, min(a + cells_per_call, n), pad_size, cell_offset=cell_offset)
+                    for a in range(0, n, cells_per_call)]
+        fine = fine[0] if len(fine) == 1 else torch.cat(fine)
+        dev = model_coarse.device
+        ids = scene.padded_object_ids(pad_size)
+        center = torch.from_numpy(np.ascontiguousarray(scene.center64[ids][:, :, 0:2], dtype=np.float64)).to(dev)
+        bbox = torch.from_numpy(np.array([np.asarray(c.bbox_w, dtype=np.float64)[0:2] for c in cells], dtype=np.float64).reshape(n, 2)).to(dev)
+        size = torch.from_numpy(np.array([float(c.cell_size) for c in cells], dtype=np.float64)).to(dev)
+        return coarse.contiguous(), fine.contiguous(), center, bbox, size
+
+    @classmethod
+    def build(cls, model_coarse, model_fine, cells, transform, pad_size: int = 16, cells_per_call: int = 2048) -> "CellDatabase":
+        """Uploads `cells` once (scene.DeviceScene with the fine stage's padding objects, seeded with the transform's seed) and
+        encodes them with both models in eval() mode; row i draws `transform.keys(i, slot)`.  cells_per_call: the memory knob (a
+        call packs cells_per_call x pad_size objects for the fine model); the result does not depend on it."""
+        _check_transform(transform)
+        pad_size, cells_per_call = int(pad_size), max(1, int(cells_per_call))
+        if not 1 <= pad_size <= MAX_HINTS:
+            raise ValueError(f"CellDatabase.build: pad_size={pad_size} outside [1, {MAX_HINTS}], the matcher's token limit")
+        if model_fine.embed_dim not in (64, 128, 256):
+            raise ValueError(f"CellDatabase.build: dim_fine={model_fine.embed_dim} is not built (the matcher takes 64, 128, 256)")
+        cells = list(cells)
+        if not cells:
+            raise ValueError("CellDatabase.build: no cells")
+        meta = dict(format=FORMAT, seed=int(transform.seed), n_pts=int(transform.n_pts), pad_size=pad_size,
+                    **model_meta(model_coarse, model_fine))
+        tensors = cls._encode(model_coarse, model_fine, cells, transform, pad_size, cells_per_call, 0)
+        return cls(*tensors, [c.id for c in cells], [getattr(c, "scene_name", "") for c in cells], meta)
+
+    def extend(self, model_coarse, model_fine, new_cells, cells_per_call: int = 2048) -> "CellDatabase":
+        """Appends cells (in place; returns self).  A new cell's draw index is its database row, so the result equals a fresh
+        build over all cells.  The models must be the ones the database was built with; duplicate ids are refused."""
+        from .pipeline import PerCellTransform
+        check_models(self.meta, model_coarse, model_fine, "CellDatabase.extend")
+        new_cells = list(new_cells)
+        ids = [str(c.id) for c in new_cells]
+        dup = sorted(set(ids) & set(self.cell_ids)) or sorted(i for i in set(ids) if ids.count(i) > 1)
+        if dup:
+            raise ValueError(f"CellDatabase.extend: cell_ids repeat (first: {dup[0]!r})")
+        if not new_cells:
+            return self
+        tf = PerCellTransform(int(self.meta["n_pts"]), int(self.meta["seed"]))
+        new = self._encode(model_coarse, model_fine, new_cells, tf, int(self.meta["pad_size"]), max(1, int(cells_per_call)), len(self))
+        for k, t in zip(_TENSORS, new):
+            setattr(self, k, torch.cat([getattr(self, k), t.to(self.device)]).contiguous())
+        self.cell_ids += ids
+        self.scene_names += [str(getattr(c, "scene_name", "")) for c in new_cells]
+        return self
+
+    # ---- storage ------------------------------------------------------------------------------------------------------------
+    def to(self, device) -> "CellDatabase":
+        return CellDatabase(*(getattr(self, k).to(device) for k in _TENSORS), self.cell_ids, self.scene_names, self.meta)
+
+    def save(self, path: str):
+        """One torch.save of tensors (moved to the host) and plain Python values: no pickled classes."""
+        torch.save(dict({k: getattr(self, k).detach().cpu().contiguous() for k in _TENSORS}, cell_ids=list(self.cell_ids),
+                        scene_names=list(self.scene_names), meta=dict(self.meta)), path)
+
+    @classmethod
+    def load(cls, path: str, device="cpu") -> "CellDatabase":
+        d = torch.load(path, map_location="cpu", weights_only=True)
+        missing = [k for k in _TENSORS + ("cell_ids", "scene_names", "meta") if k not in d]
+        if missing:
+            raise ValueError(f"CellDatabase.load: {path} lacks {missing}")
+        if d["meta"].get("format") != FORMAT:
+            raise ValueError(f"CellDatabase.load: format={d['meta'].get('format')!r}, this package reads format={FORMAT}")
+        return cls(*(d[k].to(device) for k in _TENSORS), d["cell_ids"], d["scene_names"], d["meta"])
+
+
+class Localization(SimpleNamespace):
+    """What Localizer.localize returns, host NumPy, Q queries x K candidates (best first): cell_rows int64 [Q, K], cell_ids
+    (Q lists of K ids), scores float64 [Q, K], pos_in_cell_mean / pos_in_cell float64 [Q, K, 2] (cell units: the mean of the matched
+    objects' centres / of centre + offset; (0.5, 0.5) without matches), world_xy_mean / world_xy [Q, K, 2] (bbox + pos * cell_size),
+    matched int32 [Q, K] (matched objects per candidate), best int32 [Q] (the candidate with the most, first on ties) and
+    best_world_xy float64 [Q, 2] = world_xy[q, best[q]]."""
+
+    def to_json(self, q: int) -> dict:
+        return {k: (getattr(self, k)[q].tolist() if isinstance(getattr(self, k), np.ndarray) else list(getattr(self, k)[q]))
+                for k in _RESULT_FIELDS}
+
+
+def check_hints(hints) -> List[List[str]]:
+    """The query list of Localizer.localize, checked before anything is launched."""
+    if isinstance(hints, str) or not isinstance(hints, (list, tuple)):
+        raise TypeError("localize: hints must be a list of queries, each a list of hint sentences")
+    out = []
+    for q, h in enumerate(hints):
+        if isinstance(h, str) or not isinstance(h, (list, tuple)) or not all(isinstance(s, str) for s in h):
+            raise TypeError(f"localize: query {q} must be a list of hint sentences (str)")
+        if not 1 <= len(h) <= MAX_HINTS:
+            raise ValueError(f"localize: query {q} has {len(h)} hints; a query needs 1 to {MAX_HINTS} (the matcher's token limit)")
+        out.append(list(h))
+    return out
+
+
+def group_by_hint_count(hints: List[List[str]]) -> Dict[int, List[int]]:
+    """{number of hints: the queries that have it, in the caller's order}, keys ascending."""
+    groups: Dict[int, List[int]] = {}
+    for q, h in enumerate(hints):
+        groups.setdefault(len(h), []).append(q)
+    return dict(sorted(groups.items()))
+
+
+class Localizer:
+    def __init__(self, model_coarse, model_fine, database: CellDatabase):
+        for name, m in (("model_coarse", model_coarse), ("model_fine", model_fine)):
+            if m.training:
+                raise NotImplementedError(f"Localizer: {name} is in train() mode; the serving path runs the folded eval() kernels: "
+                                          "call .eval()")
+        check_models(database.meta, model_coarse, model_fine, "Localizer")
+        self.model_coarse, self.model_fine, self.database = model_coarse, model_fine, database
+
+    def _require_device(self):
+        db = self.database
+        for name, dev in (("database", db.device), ("model_coarse", self.model_coarse.device), ("model_fine", self.model_fine.device)):
+            if torch.device(dev).type != "cuda":
+                raise RuntimeError(f"Localizer.localize: {name} must live on the GPU (got device {dev}); there is no CPU path")
+        if not (torch.device(db.device) == torch.device(self.model_coarse.device) == torch.device(self.model_fine.device)):
+            raise RuntimeError("Localizer.localize: database and models are on different devices")
+
+    def _run_chunk(self, hints: List[List[str]], top_k: int) -> torch.Tensor:
+        """Queries with the same number of hints -> float64 [Q, 11 K + 1] on the device: cell rows | scores | pos_mean | pos_offset |
+        world_mean | world_offset (K x 2 each) | matched | best.  (Rows and counts are small integers: exact in float64.)"""
+        db, mc, mf = self.database, self.model_coarse, self.model_fine
+        nq, k = len(hints), int(top_k)
+        for m in (mc, mf):
+            if m.training:
+                raise NotImplementedError("Localizer.localize: a model was put into train() mode; call .eval()")
+        with torch.no_grad():
+            text = mc.encode_text([" ".join(h) for h in hints])                      # io.Scenes.texts (cells.py:82)
+            rows, scores = retrieve_topk(db.coarse, text, k)
+            hint_enc = mf.encode_hints(hints).contiguous()                           # once per query, not per candidate
+            obj_row = rows.reshape(-1).to(torch.int32)
+            hint_row = torch.arange(nq, dtype=torch.int32, device=rows.device).repeat_interleave(k)
+            out = ops.match_indexed(db.fine, hint_enc, obj_row, hint_row, mf._match_pack(), mf.sinkhorn_iters, MATCH_THRESHOLD)
+            pose = ops.localize_poses(out["matches0"], out["offsets"], obj_row, nq, k, db.center_xy, db.bbox_xy, db.cell_size,
+                                      check=False)
+        flat = lambda t: t.reshape(nq, -1).to(torch.float64)
+        return torch.cat([flat(rows), flat(scores), flat(pose["pos_mean"]), flat(pose["pos_offset"]), flat(pose["world_mean"]),
+                          flat(pose["world_offset"]), flat(pose["matched"]), flat(pose["best"])], dim=1)
+
+    def localize(self, hints: List[List[str]], top_k: int = 10, queries_per_call: Optional[int] = None) -> Localization:
+        """hints: one list of hint sentences per query (1 to 63 each; the coarse text of a query is " ".join(hints)).  Queries are
+        grouped by their number of hints, run in calls of queries_per_call (None = min(256, 4096 // top_k), evaluation.run_fine's
+        device default) and returned in the caller's order.  One device-to-host copy at the end; a sample either kernel refused to
+        read through (a row outside the database, a NaN offset) raises IndexError naming query and candidate there."""
+        hints = check_hints(hints)
+        k = check_top_k(top_k)
+        if np.ndim(top_k) != 0:
+            raise ValueError("localize: top_k is one number (the candidates per query)")
+        if k > len(self.database):
+            raise ValueError(f"localize: top_k={k} exceeds the {len(self.database)} cells of the database")
+        per_call = min(256, 4096 // k) if queries_per_call is None else int(queries_per_call)
+        per_call = max(1, per_call)
+        self._require_device()
+        nq = len(hints)
+        order, parts = [], []
+        for _, qs in group_by_hint_count(hints).items():
+            for a in range(0, len(qs), per_call):
+                chunk = qs[a: a + per_call]
+                parts.append(self._run_chunk([hints[q] for q in chunk], k))
+                order += chunk
+        width = 11 * k + 1
+        packed = torch.cat(parts).cpu().numpy() if parts else np.zeros((0, width))       # the call's one device-to-host copy
+        res = np.empty((nq, width), dtype=np.float64)
+        res[np.asarray(order, dtype=np.int64)] = packed
+        cut = lambda i, n=1: res[:, i * k: (i + n) * k]
+        matched = cut(10).astype(np.int32)
+        ops.localize_check(matched, "Localizer.localize")
+        rows = cut(0).astype(np.int64)
+        best = res[:, 11 * k].astype(np.int32)
+        world = cut(8, 2).reshape(nq, k, 2).copy()
+        return Localization(cell_rows=rows, cell_ids=[[self.database.cell_ids[j] for j in r] for r in rows], scores=cut(1).copy(),
+                            pos_in_cell_mean=cut(2, 2).reshape(nq, k, 2).copy(), pos_in_cell=cut(4, 2).reshape(nq, k, 2).copy(),
+                            world_xy_mean=cut(6, 2).reshape(nq, k, 2).copy(), world_xy=world, matched=matched, best=best,
+                            best_world_xy=world[np.arange(nq), best] if nq else np.zeros((0, 2)))
+
+    def localize_poses(self, poses, top_k: int = 10, queries_per_call: Optional[int] = None) -> Localization:
+        """localize() on the hint sentences of data.Pose objects (evaluation.create_hint_description)."""
+        from .evaluation import create_hint_description
+        return self.localize([create_hint_description(p) for p in poses], top_k, queries_per_call)
+
+
+# ---- command line ---------------------------------------------------------------------------------------------------------------
+def _load_models(a, scenes=None, words=None, classes=None):
+    from . import CellRetrievalNetwork, SuperGlueMatch
+    from . import data as D, io as IO
+    from .pipeline import _model_args, args_from_checkpoint
+    dev = torch.device("cuda", 0)
+    sd, ck = IO.load_reference_checkpoint(a.path_coarse, return_args=True)
+    ca = args_from_checkpoint(_model_args(a.coarse_embed_dim, use_features=a.use_features), ck, "coarse")
+    coarse = CellRetrievalNetwork(classes, D.COLOR_NAMES, words, ca)
+    coarse.load_state_dict(sd)
+    sd, ck = IO.load_reference_checkpoint(a.path_fine, return_args=True)
+    fa = args_from_checkpoint(_model_args(a.fine_embed_dim, a.fine_num_layers, a.sinkhorn_iters, a.use_features), ck, "fine")
+    fine = SuperGlueMatch(classes, D.COLOR_NAMES, words, fa)
+    fine.load_state_dict(sd)
+    return coarse.to(dev).eval(), fine.to(dev).eval(), int(getattr(ca, "pointnet_numpoints", 256))
+
+
+def read_queries(hints: Optional[List[str]], queries_file: Optional[str]) -> List[List[str]]:
+    """--hints: the sentences of one query; --queries_file: one query per line, its hints separated by '|'."""
+    queries = []
+    if hints:
+        queries.append([h.strip() for h in hints])
+    if queries_file:
+        with open(queries_file) as f:
+            for line in f:
+                if line.strip():
+                    queries.append([h.strip() for h in line.strip().split("|") if h.strip()])
+    if not queries:
+        raise ValueError("query: give --hints or --queries_file")
+    return queries
+
+
+def main(argv: Optional[List[str]] = None):
+    from . import data as D, io as IO
+    from .pipeline import SCENE_NAMES_VAL, PerCellTransform
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    sub = ap.add_subparsers(dest="command", required=True)
+    for name in ("build", "query"):
+        p = sub.add_parser(name)
+        p.add_argument("--path_coarse", required=True)
+        p.add_argument("--path_fine", required=True)
+        p.add_argument("--coarse_embed_dim", type=int, default=256)
+        p.add_argument("--fine_embed_dim", type=int, default=128)
+        p.add_argument("--fine_num_layers", type=int, default=6)
+        p.add_argument("--sinkhorn_iters", type=int, default=50)
+        p.add_argument("--use_features", nargs="+", default=["class", "color", "position"])
+        if name == "build":
+            p.add_argument("--base_path", required=True)
+            p.add_argument("--scenes", nargs="*", default=SCENE_NAMES_VAL)
+            p.add_argument("--out", required=True)
+            p.add_argument("--pad_size", type=int, default=16)
+            p.add_argument("--seed", type=int, default=0, help="seed of the cells' T.FixedPoints draws")
+            p.add_argument("--cells_per_call", type=int, default=2048)
+        else:
+            p.add_argument("--db", required=True)
+            p.add_argument("--hints", nargs="+", default=None, help="the hint sentences of one query")
+            p.add_argument("--queries_file", default=None, help="one query per line, its hints separated by '|'")
+            p.add_argument("--top_k", type=int, default=10)
+            p.add_argument("--vocab_base_path", default=None, help="dataset the models' vocabulary comes from (with --vocab_scenes)")
+            p.add_argument("--vocab_scenes", nargs="*", default=SCENE_NAMES_VAL)
+    a = ap.parse_args(argv)
+    if a.command == "build":
+        scenes = IO.load_scenes(a.base_path, a.scenes)
+        coarse, fine, n_pts = _load_models(a, words=scenes.get_known_words(), classes=scenes.get_known_classes())
+        db = CellDatabase.build(coarse, fine, scenes.all_cells, PerCellTransform(n_pts, a.seed), a.pad_size, a.cells_per_call)
+        db.meta["known_words"] = [str(w) for w in scenes.get_known_words()]     # the query command rebuilds the models' vocabulary
+        db.save(a.out)
+        print(json.dumps(dict(out=a.out, cells=len(db), pad_size=a.pad_size, dim_coarse=db.meta["dim_coarse"], dim_fine=db.meta["dim_fine"])))
+        return db
+    check_top_k(a.top_k)                                                          # before the checkpoints are read
+    queries = check_hints(read_queries(a.hints, a.queries_file))
+    db = CellDatabase.load(a.db)
+    if a.vocab_base_path:
+        words = IO.load_scenes(a.vocab_base_path, a.vocab_scenes).get_known_words()
+    elif "known_words" in db.meta:
+        words = list(db.meta["known_words"])
+    else:
+        raise ValueError("query: the database carries no vocabulary; give --vocab_base_path")
+    coarse, fine, _ = _load_models(a, words=words, classes=list(D.KNOWN_CLASSES))
+    res = Localizer(coarse, fine, db.to(coarse.device)).localize(queries, a.top_k)
+    for q in range(len(queries)):
+        print(json.dumps(res.to_json(q)))
+    return res
+
+
+if __name__ == "__main__":
+    main(sys.argv[1:])

@@ -1235,6 +1235,92 @@ def fine_step_stats(matches0: torch.Tensor, matches1: torch.Tensor, offsets: tor
     return sample_stats, step_row
 
 
+LOCALIZE_MAX_TOP_K = 1024    # T2P_LOCALIZE_MAX_TOP_K (include/t2p.h)
+
+
+def match_indexed(obj_table: torch.Tensor, hint_table: torch.Tensor, obj_row: torch.Tensor, hint_row: torch.Tensor,
+                  weights: L.MatchWeights, sinkhorn_iters: int, threshold: float = 0.2):
+    """match() with its inputs addressed through tables (t2p_match_indexed): obj_table fp32 [n_cells, M, D], hint_table fp32
+    [n_queries, N, D], obj_row / hint_row int32 [B] on the GPU - sample b matches cell obj_row[b] against query hint_row[b].
+    Returns match()'s dict, bit for bit what match() gives on the index_select'ed tables.  A row outside its table is not read
+    through: that sample's P is NaN and its matches are -1 (localize_poses marks a sample whose cell row is outside the database),
+    its neighbours are unaffected."""
+    _need(obj_table, "obj_table", torch.float32, 3)
+    dev = obj_table.device
+    _need(hint_table, "hint_table", torch.float32, 3, dev)
+    _need(obj_row, "obj_row", torch.int32, 1, dev)
+    _need(hint_row, "hint_row", torch.int32, 1, dev)
+    n_cells, m, d = obj_table.shape
+    n_queries, n = hint_table.shape[0], hint_table.shape[1]
+    b = obj_row.shape[0]
+    if hint_table.shape[2] != d or hint_row.shape[0] != b:
+        raise RuntimeError(f"match_indexed: obj_table {tuple(obj_table.shape)} / hint_table {tuple(hint_table.shape)} / obj_row "
+                           f"{tuple(obj_row.shape)} / hint_row {tuple(hint_row.shape)} disagree")
+    out = dict(P=torch.empty((b, m + 1, n + 1), dtype=torch.float32, device=dev),
+               matches0=torch.empty((b, m), dtype=torch.int64, device=dev),
+               matches1=torch.empty((b, n), dtype=torch.int64, device=dev),
+               matching_scores0=torch.empty((b, m), dtype=torch.float32, device=dev),
+               matching_scores1=torch.empty((b, n), dtype=torch.float32, device=dev),
+               offsets=torch.empty((b, n, 2), dtype=torch.float32, device=dev))
+    if b == 0:      # (empty tensors have no address to hand over; the entry point launches nothing for batch 0 either)
+        return out
+    ws = workspace(dev, L.lib().t2p_match_indexed_workspace_bytes(b, m, n, d), "match_indexed")
+    rc = L.lib().t2p_match_indexed(_ptr(obj_table), n_cells, _ptr(hint_table), n_queries, _ptr(obj_row), _ptr(hint_row), b, m, n, d,
+                                   C.byref(weights), int(sinkhorn_iters), float(threshold), _ptr(out["P"]), _ptr(out["matches0"]),
+                                   _ptr(out["matches1"]), _ptr(out["matching_scores0"]), _ptr(out["matching_scores1"]),
+                                   _ptr(out["offsets"]), _ptr(ws), ws.numel(), _stream(dev))
+    L.check(rc, "t2p_match_indexed")
+    return out
+
+
+def localize_check(matched: np.ndarray, what: str = "localize_poses", query_offset: int = 0):
+    """IndexError naming the first (query, candidate) the kernel marked with matched = -1 (host array [Q, K])."""
+    bad = np.argwhere(np.asarray(matched) < 0)
+    if len(bad):
+        q, c = int(bad[0][0]), int(bad[0][1])
+        raise IndexError(f"{what}: query {q + query_offset}, candidate {c}: a cell row outside the database, a matches0 value outside "
+                         f"its range or a NaN offset ({len(bad)} such samples; the kernel marks them instead of reading through them)")
+
+
+def localize_poses(matches0: torch.Tensor, offsets: torch.Tensor, cell_row: torch.Tensor, n_queries: int, top_k: int,
+                   center_xy: torch.Tensor, bbox_xy: torch.Tensor, cell_size: torch.Tensor, check: bool = True):
+    """get_pos_in_cell (models/superglue_matcher.py:139-161), the world step of evaluation._sample_hits and run_fine's argmax over
+    the candidates' matched counts for n_queries x top_k samples (query-major) in one launch (t2p_localize_poses).  matches0 int64
+    [Q K, M], offsets fp32 [Q K, N, 2], cell_row int32 [Q K]; float64 tables center_xy [n_cells, M, 2], bbox_xy [n_cells, 2],
+    cell_size [n_cells].  Returns a dict of device tensors: pos_mean, pos_offset, world_mean, world_offset float64 [Q, K, 2],
+    matched int32 [Q, K], best int32 [Q].  check (default): read `matched` back and raise IndexError when the kernel marked a
+    sample (localize_check); a caller that copies the results anyway passes check=False and calls localize_check itself."""
+    _need(matches0, "matches0", torch.int64, 2)
+    dev = matches0.device
+    _need(offsets, "offsets", torch.float32, 3, dev)
+    _need(cell_row, "cell_row", torch.int32, 1, dev)
+    _need(center_xy, "center_xy", torch.float64, 3, dev)
+    _need(bbox_xy, "bbox_xy", torch.float64, 2, dev)
+    _need(cell_size, "cell_size", torch.float64, 1, dev)
+    q, k = int(n_queries), int(top_k)
+    b, m = matches0.shape
+    n = offsets.shape[1]
+    rows = center_xy.shape[0]
+    if q < 0 or k < 1 or b != q * k or tuple(offsets.shape) != (b, n, 2) or cell_row.shape[0] != b:
+        raise RuntimeError(f"localize_poses: matches0 {tuple(matches0.shape)}, offsets {tuple(offsets.shape)} and cell_row "
+                           f"{tuple(cell_row.shape)} do not describe {q} queries x {k} candidates")
+    if tuple(center_xy.shape) != (rows, m, 2) or tuple(bbox_xy.shape) != (rows, 2) or tuple(cell_size.shape) != (rows,):
+        raise RuntimeError(f"localize_poses: tables center_xy {tuple(center_xy.shape)}, bbox_xy {tuple(bbox_xy.shape)}, cell_size "
+                           f"{tuple(cell_size.shape)} must be [n, {m}, 2], [n, 2], [n]")
+    f64 = lambda: torch.empty((q, k, 2), dtype=torch.float64, device=dev)
+    out = dict(pos_mean=f64(), pos_offset=f64(), world_mean=f64(), world_offset=f64(),
+               matched=torch.empty((q, k), dtype=torch.int32, device=dev), best=torch.empty((q,), dtype=torch.int32, device=dev))
+    if q == 0:
+        return out
+    L.check(L.lib().t2p_localize_poses(_ptr(matches0), _ptr(offsets), _ptr(cell_row), q, k, m, n, _ptr(center_xy), _ptr(bbox_xy),
+                                       _ptr(cell_size), rows, _ptr(out["pos_mean"]), _ptr(out["pos_offset"]), _ptr(out["world_mean"]),
+                                       _ptr(out["world_offset"]), _ptr(out["matched"]), _ptr(out["best"]), _stream(dev)),
+            "t2p_localize_poses")
+    if check:
+        localize_check(out["matched"].cpu().numpy())
+    return out
+
+
 # ---------------------------------------------------------------------------------------------------------------
 def profile_enable(on: bool):
     """Bracket every kernel launch with hipEvents on its launch stream (bench.py's live per-kernel timing)."""

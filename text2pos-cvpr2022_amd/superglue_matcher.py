@@ -269,6 +269,49 @@ class SuperGlueMatch(PicklableModule):
         out = self.forward_packed(xyz, rgb, center, mean_rgb, cp, hints, ci, co)
         return (out, (xyz, rgb, center, mean_rgb, cp)) if want_inputs else out
 
+    def encode_cell_objects(self, scene, transform, lo: int, hi: int, pad_size: int, cell_offset: int = 0,
+                            check_overflow: bool = True) -> torch.Tensor:
+        """The object half of forward_packed for the cells [lo, hi) of a scene.DeviceScene -> [hi - lo, pad_size, D] fp32,
+        L2-normalised object tokens (models/superglue_matcher.py:99-103) of every cell's padded object list
+        (scene.padded_object_ids(pad_size): dataloading/kitti360pose/eval.py:141-149): pack, t2p_encode_cells(objects_only),
+        t2p_rownorm.  Cell i draws transform.keys(cell_offset + i, slot) - ONE draw per cell (localize.CellDatabase), where the
+        evaluation draws once per (query, candidate) sample.  eval() only; the f16x3 guard word is checked (check_overflow)."""
+        if self.training:
+            raise NotImplementedError("encode_cell_objects: the database is encoded in eval() mode (folded BatchNorm); call .eval()")
+        self._check_forward_only()
+        a, d, dev = self.args, self.embed_dim, self.device
+        n = int(hi) - int(lo)
+        if n <= 0:
+            return torch.empty((0, int(pad_size), d), dtype=torch.float32, device=dev)
+        ids = scene.padded_object_ids(int(pad_size))[lo:hi]                                  # [n, pad]
+        cell = np.arange(lo, hi, dtype=np.int64) + int(cell_offset)
+        keys = transform.keys(cell[:, None], np.arange(int(pad_size), dtype=np.int64)[None, :])
+        want_rgb = "color" in a.use_features or bool(getattr(a, "class_embed", False))
+        xyz, rgb, center, mean_rgb = scene.pack(ids.reshape(-1), keys.reshape(-1), transform.n_pts, want_rgb=want_rgb)
+        if rgb is None:
+            rgb = torch.zeros_like(xyz)      # forward_packed's rule (models/object_encoder.py:86-90)
+        class_all, color_all = scene.feature_indices(self)
+        ci = co = None
+        if class_all is not None or color_all is not None:
+            sel = torch.from_numpy(np.ascontiguousarray(ids.reshape(-1))).to(dev)
+            ci = None if class_all is None else class_all[sel].contiguous()
+            co = None if color_all is None else color_all[sel].contiguous()
+        cfg = ops.make_cell_config(n_pts=xyz.shape[1], embed_dim=d, pointnet_features=a.pointnet_features,
+                                   use_features=tuple(a.use_features), self_loops=self.add_self_loops,
+                                   radius=self.object_encoder.pointnet.radii, precision=self.precision,
+                                   class_idx=ci, color_idx=co, objects_only=True)
+        if self.precision == "f16x3":
+            if self._overflow is None or self._overflow.device != dev:
+                self._overflow = torch.zeros(1, dtype=torch.int32, device=dev)
+            cfg.overflow_flag = self._overflow.data_ptr()
+        cp = np.arange(n + 1, dtype=np.int32) * int(pad_size)
+        obj = ops.encode_cells(xyz, rgb, center, mean_rgb, cp, torch.from_numpy(cp).to(dev), self._object_pack(), cfg)
+        obj = ops.rownorm(obj).view(n, int(pad_size), d)
+        if check_overflow and self.overflow_detected():
+            raise FloatingPointError("f16x3 path: an object-encoder activation left fp16's range; construct the model "
+                                     "with precision=\"fp32\"")
+        return obj
+
     def encode_hints(self, hints: List[List[str]]) -> torch.Tensor:
         """List[List[str]] (samples x num_hints sentences) -> [samples, num_hints, D] L2-normalised hint encodings
         (models/superglue_matcher.py:94-97)."""

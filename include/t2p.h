@@ -331,7 +331,10 @@ int t2p_pack_scene_objects_aug(const float* raw_xyz, const float* raw_rgb, const
  *   wqkv [D][3D] = attn.proj.{0,1,2} side by side (q | k | v), bqkv [3D];  wm [D][D], bm [D] = attn.merge;
  *   w1 [2D][2D], b1 [2D] = mlp.0 + mlp.1 (BN);  w2 [2D][D], b2 [D] = mlp.3;   cross[l] (HOST array) 0 = self, 1 = cross.
  * Outputs: P [B][n_obj+1][n_hints+1] fp32; matches0 [B][n_obj], matches1 [B][n_hints] int64 (-1 = no match);
- * matching_scores0/1 fp32; offsets [B][n_hints][2] fp32.
+ * matching_scores0/1 fp32; offsets [B][n_hints][2] fp32.  The optimal-transport part (scores, the log-Sinkhorn iterations, the
+ * log couplings the matches are read from) is float64 inside and rounds P and the scores once, as t2p_match_head does.
+ * With GNN layers a sample's (n_obj + n_hints)(3 D + 4) + 4 (n_obj + n_hints) max(n_obj, n_hints) floats must fit 160 KiB of
+ * LDS (T2P_E_UNSUPPORTED otherwise, before any launch); without a layer every 1 <= n_obj, n_hints <= 63 runs.
  * ---------------------------------------------------------------------------------------------------------- */
 typedef struct t2p_match_weights {
     int32_t n_layers;

@@ -1617,6 +1617,12 @@ def test_match_other_shapes_vs_oracle(b, m, n, d, layers, precision):
     assert torch.equal(out["matches0"].cpu(), want["matches0"]) and torch.equal(out["matches1"].cpu(), want["matches1"])
     assert (out["matching_scores0"].cpu() - want["matching_scores0"]).abs().max().item() < TOL
     assert abs(float(out["P"].sum()) - b * (m + n)) < 1e-2 * b      # couplings sum to M + N per sample
+    # offsets = Linear(ReLU(Linear(hint))) against float64, within the worst-case bound of its two fma chains (fine_forward_ref.py)
+    import fine_forward_ref as FF
+    from train_ops_ref import within
+    ow = FF.holder_offset_weights(h)
+    x = d1.reshape(-1, d)
+    assert within(out["offsets"].cpu().numpy().reshape(-1, 2), FF.offsets_ref64(x, *ow), FF.offsets_bounds(x, *ow), 1.0)
 
 
 def test_pipeline_end_to_end_on_a_synthetic_scene(tmp_path, vocab):

@@ -207,7 +207,7 @@ int t2p_match_indexed(const float* obj_table, int64_t n_cells, const float* hint
     T2P_CHECK_ARG(sinkhorn_iters >= 0, "match_indexed: sinkhorn_iters < 0");
     {   // t2p_match's own refusal, ahead of the gather: a sample's attention rows (4 heads) must fit the LDS a workgroup may use
         const size_t T = (size_t)M + N, lds_attn = (T * (3 * D + 4) + T * 4 * (M > N ? M : N)) * sizeof(float);
-        if (lds_attn > 160 * 1024) {
+        if (w->n_layers > 0 && lds_attn > 160 * 1024) {
             set_error("match: %d tokens x D=%d need %zu B of LDS per sample (> 160 KiB)", (int)T, D, lds_attn);
             return T2P_E_UNSUPPORTED;
         }

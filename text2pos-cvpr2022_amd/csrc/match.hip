@@ -12,7 +12,8 @@
 //   CAT[:, D:] = MSG Wm;   H = relu(CAT W1) (BatchNorm folded);   X += H W2 (residual in the GEMM epilogue)
 // X lives in the left half of CAT [T][2D], so the concat of AttentionalPropagation is free.  The optimal-transport
 // part (score matrix, 50 log-Sinkhorn iterations on (M+1) x (N+1), exp, mutual nearest neighbours, threshold) and the
-// offset MLP run in one wavefront per sample with the matrix in LDS (k_match_final).  fp32 throughout.
+// offset MLP run in one wavefront per sample with the matrix in LDS (k_match_final).  fp32 throughout, except the optimal-transport
+// part, which is float64 and rounds P once.
 #include "t2p_common.h"
 
 #include "../../include/t2p.h"
@@ -91,70 +92,77 @@ __global__ __launch_bounds__(256) void k_attn(const float* __restrict__ qkv, int
 }
 
 // One wavefront per sample: score matrix, log-space Sinkhorn with dustbins, exp, mutual NN + threshold, offsets.
+// The scores, u, v and the log couplings are float64, as in k_head_sets (match_train.hip), and P is rounded to fp32 once: |u| and
+// |v| reach 5 to 8, where one fp32 rounding is 5e-7 to 1e-6 of log P, and a fp32 recurrence left the dustbin couplings (P of 4 to 6)
+// 2.5e-6 from the float64 matcher - four times the fp32 oracle's own distance (docs/notebook.md, "The fine matcher's forward kernels
+// against float64").  The offset MLP stays fp32.
 __global__ __launch_bounds__(64) void k_match_final(const float* __restrict__ md /*[B T][D] final_proj outputs*/,
                                                     const float* __restrict__ d1 /*[B N][D] hint encodings*/,
-                                                    int M, int N, int D, float alpha, int iters, float thresh,
+                                                    int M, int N, int D, float alpha_f, int iters, float thresh,
                                                     const float* __restrict__ wo1, const float* __restrict__ bo1,
                                                     const float* __restrict__ wo2, const float* __restrict__ bo2,
                                                     float* __restrict__ P, int64_t* __restrict__ matches0,
                                                     int64_t* __restrict__ matches1, float* __restrict__ ms0,
                                                     float* __restrict__ ms1, float* __restrict__ offsets) {
-    extern __shared__ float sm[];
+    extern __shared__ double smd[];
     const int lane = threadIdx.x;
     const int T = M + N, M1 = M + 1, N1 = N + 1;
-    float* Z = sm;                  // [M1][N1]
-    float* u = Z + M1 * N1;         // [M1]
-    float* v = u + M1;              // [N1]
-    float* rmax = v + N1;           // [M] row max (inner), [N] col max
+    double* Z = smd;                 // [M1][N1]
+    double* u = Z + M1 * N1;         // [M1]
+    double* v = u + M1;              // [N1]
+    double* rmax = v + N1;           // [M] row max (inner), [N] col max
     int* ridx = (int*)(rmax + M + N);  // [M] + [N]
     float* hid = (float*)(ridx + M + N);  // [D/2]
     const int64_t b = blockIdx.x;
     const float* m0 = md + b * T * (int64_t)D;
     const float* m1 = m0 + M * (int64_t)D;
-    const float inv = 1.0f / sqrtf((float)D);
+    const double alpha = (double)alpha_f;
+    const double inv = 1.0 / sqrt((double)D);
     for (int e = lane; e < M1 * N1; e += 64) {
         const int i = e / N1, j = e % N1;
-        float a = alpha;
+        double a = alpha;
         if (i < M && j < N) {
-            a = 0.f;
-            for (int k = 0; k < D; k++) a = fmaf(m0[i * (int64_t)D + k], m1[j * (int64_t)D + k], a);
+            a = 0.0;
+            const float* x = m0 + i * (int64_t)D;
+            const float* y = m1 + j * (int64_t)D;
+            for (int k = 0; k < D; k++) a = fma((double)x[k], (double)y[k], a);
             a *= inv;
         }
         Z[e] = a;
     }
-    const float norm = -logf((float)(M + N));
-    const float lmu_bin = logf((float)N) + norm, lnu_bin = logf((float)M) + norm;
-    if (lane < M1) u[lane] = 0.f;
-    if (lane < N1) v[lane] = 0.f;
+    const double norm = -log((double)(M + N));
+    const double lmu_bin = log((double)N) + norm, lnu_bin = log((double)M) + norm;
+    if (lane < M1) u[lane] = 0.0;
+    if (lane < N1) v[lane] = 0.0;
     __syncthreads();
     for (int it = 0; it < iters; it++) {
         if (lane < M1) {  // u = log_mu - logsumexp_j(Z + v)
-            float mx = -INFINITY;
-            for (int j = 0; j < N1; j++) mx = fmaxf(mx, Z[lane * N1 + j] + v[j]);
-            float s = 0.f;
-            for (int j = 0; j < N1; j++) s += expf(Z[lane * N1 + j] + v[j] - mx);
-            u[lane] = (lane < M ? norm : lmu_bin) - (mx + logf(s));
+            double mx = -INFINITY;
+            for (int j = 0; j < N1; j++) mx = fmax(mx, Z[lane * N1 + j] + v[j]);
+            double s = 0.0;
+            for (int j = 0; j < N1; j++) s += exp(Z[lane * N1 + j] + v[j] - mx);
+            u[lane] = (lane < M ? norm : lmu_bin) - (mx + log(s));
         }
         __syncthreads();
         if (lane < N1) {  // v = log_nu - logsumexp_i(Z + u)
-            float mx = -INFINITY;
-            for (int i = 0; i < M1; i++) mx = fmaxf(mx, Z[i * N1 + lane] + u[i]);
-            float s = 0.f;
-            for (int i = 0; i < M1; i++) s += expf(Z[i * N1 + lane] + u[i] - mx);
-            v[lane] = (lane < N ? norm : lnu_bin) - (mx + logf(s));
+            double mx = -INFINITY;
+            for (int i = 0; i < M1; i++) mx = fmax(mx, Z[i * N1 + lane] + u[i]);
+            double s = 0.0;
+            for (int i = 0; i < M1; i++) s += exp(Z[i * N1 + lane] + u[i] - mx);
+            v[lane] = (lane < N ? norm : lnu_bin) - (mx + log(s));
         }
         __syncthreads();
     }
     for (int e = lane; e < M1 * N1; e += 64) {
         const int i = e / N1, j = e % N1;
-        const float z = Z[e] + u[i] + v[j] - norm;
+        const double z = Z[e] + u[i] + v[j] - norm;
         Z[e] = z;
-        P[b * M1 * N1 + e] = expf(z);
+        P[b * M1 * N1 + e] = (float)exp(z);
     }
     __syncthreads();
     // maxima over the inner (non-dustbin) block; ties -> first index
     if (lane < M) {
-        float mx = -INFINITY;
+        double mx = -INFINITY;
         int bi = 0;
         for (int j = 0; j < N; j++)
             if (Z[lane * N1 + j] > mx) { mx = Z[lane * N1 + j]; bi = j; }
@@ -162,7 +170,7 @@ __global__ __launch_bounds__(64) void k_match_final(const float* __restrict__ md
         ridx[lane] = bi;
     }
     if (lane < N) {
-        float mx = -INFINITY;
+        double mx = -INFINITY;
         int bi = 0;
         for (int i = 0; i < M; i++)
             if (Z[i * N1 + lane] > mx) { mx = Z[i * N1 + lane]; bi = i; }
@@ -173,15 +181,15 @@ __global__ __launch_bounds__(64) void k_match_final(const float* __restrict__ md
     if (lane < M) {
         const int j = ridx[lane];
         const bool mutual = ridx[M + j] == lane;
-        const float s = mutual ? expf(rmax[lane]) : 0.f;
+        const float s = mutual ? (float)exp(rmax[lane]) : 0.f;
         ms0[b * M + lane] = s;
         matches0[b * M + lane] = (mutual && s > thresh) ? j : -1;
     }
     if (lane < N) {
         const int i = ridx[M + lane];
         const bool mutual1 = ridx[i] == lane;
-        const bool mutual0 = ridx[M + ridx[i]] == i;                 // mutual0[i]
-        const float s0 = mutual0 ? expf(rmax[i]) : 0.f;              // mscores0[i]
+        const bool mutual0 = ridx[M + ridx[i]] == i;                       // mutual0[i]
+        const float s0 = mutual0 ? (float)exp(rmax[i]) : 0.f;             // mscores0[i]
         const float s = mutual1 ? s0 : 0.f;
         ms1[b * N + lane] = s;
         const bool valid0 = mutual0 && s0 > thresh;
@@ -258,7 +266,7 @@ int t2p_match(const float* desc0, const float* desc1, int64_t batch, int32_t n_o
     if (batch == 0) return 0;
     const int T = M + N;
     const size_t lds_attn = ((size_t)T * (3 * D + 4) + (size_t)T * kHeads * (M > N ? M : N)) * sizeof(float);
-    if (lds_attn > 160 * 1024) {
+    if (w->n_layers > 0 && lds_attn > 160 * 1024) {   // (without a GNN layer k_attn never runs: nothing to refuse)
         set_error("match: %d tokens x D=%d need %zu B of LDS per sample (> 160 KiB)", T, D, lds_attn);
         return T2P_E_UNSUPPORTED;
     }
@@ -304,7 +312,9 @@ int t2p_match(const float* desc0, const float* desc1, int64_t batch, int32_t n_o
     }
     T2P_TRY(launch_dense(ws.cat, 2 * D, DenseW{w->wf, w->wf_x3, w->scale_f}, w->bf, ws.md, D, 0, rows, D, D, 0, st));
     {
-        const size_t lds = ((size_t)(M + 1) * (N + 1) + (M + 1) + (N + 1) + 2 * (M + N) + D / 2 + 8) * sizeof(float);
+        // float64: Z, u, v, the maxima; then the winners' indices and the offset MLP's hidden row (35 KiB at 63 + 63 tokens)
+        const size_t lds = ((size_t)(M + 1) * (N + 1) + (M + 1) + (N + 1) + (M + N)) * sizeof(double) +
+                           ((size_t)(M + N) + D / 2 + 8) * sizeof(float);
         ProfScope ps_("match_final", st);
         hipLaunchKernelGGL(k_match_final, dim3((unsigned)batch), dim3(64), lds, st, ws.md, desc1, M, N, D, w->bin_score,
                            sinkhorn_iters, match_threshold, w->wo1, w->bo1, w->wo2, w->bo2, P, matches0, matches1,

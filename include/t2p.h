@@ -517,10 +517,15 @@ int t2p_encode_text(const int32_t* tokens, const int32_t* lengths, int64_t batch
  * (query, cell) pair, and the order (score descending, ties and -0.0 / +0.0 to the lower cell index), do not depend on k:
  * the first j columns of a k-result are the j-result, bit for bit.  A NaN score is never retrieved; when fewer than k
  * cells qualify the tail is -1 / -inf.
- *   k <= T2P_SIM_TOPK_REG_K: per-lane candidate lists in registers, scores never leave the chip.  Workspace:
+ * Two selection paths.  Which one runs depends on the problem size for every k <= T2P_SIM_TOPK_REG_K, never on k within 1..16
+ * (so the workspace of a shape is one number for all of them):
+ *     register lists:  k <= T2P_SIM_TOPK_REG_K and nq * nc <  T2P_SIM_TOPK_TILE_MIN_PAIRS
+ *     score tile:      k >  T2P_SIM_TOPK_REG_K, or nq * nc >= T2P_SIM_TOPK_TILE_MIN_PAIRS
+ * (k <= T2P_SIM_TOPK_REG_K with nc > 33,554,400, one query's scores beyond the tile, stays on the lists whatever nq * nc).
+ *   Register lists: per-lane candidate lists in registers, scores never leave the chip.  Workspace:
  *     nq * splits * 4 * 16 * 12 + 256 bytes, splits = the cell ranges the launch divides the database into (it depends on
  *     nq, nc and the device's CU count, not on k).
- *   k >  T2P_SIM_TOPK_REG_K: the call walks the queries in chunks; per chunk one kernel writes the chunk's float64 scores
+ *   Score tile: the call walks the queries in chunks; per chunk one kernel writes the chunk's float64 scores
  *     into the workspace and one workgroup per query selects its k exactly (radix selection on order-preserving keys,
  *     lowest-index ties by an ascending sweep, sort in LDS).  Workspace = one chunk's score tile, never more than
  *     T2P_SIM_TOPK_TILE_BYTES whatever nq, nc and k:
@@ -529,10 +534,11 @@ int t2p_encode_text(const int32_t* tokens, const int32_t* lengths, int64_t batch
  *         chunk = min(nq, cap)                             queries per chunk
  *         bytes = chunk * 8 * ld + 256
  *     cap == 0, i.e. one query's scores (8 * nc bytes, nc > 33,554,400) exceed the tile: T2P_E_ARG with a message that
- *     says so (the k <= T2P_SIM_TOPK_REG_K path has no such limit besides nc < 2^31).  The workspace must be 16-byte aligned.
+ *     says so (k <= T2P_SIM_TOPK_REG_K has no such limit besides nc < 2^31: the lists).  The workspace must be 16-byte aligned.
  * ---------------------------------------------------------------------------------------------------------- */
 #define T2P_SIM_TOPK_MAX_K 1024
 #define T2P_SIM_TOPK_REG_K 16
+#define T2P_SIM_TOPK_TILE_MIN_PAIRS 256000 /* k <= T2P_SIM_TOPK_REG_K: nq * nc from which the score-tile path runs (profiles/t04_topk_route_sweep.md) */
 #define T2P_SIM_TOPK_TILE_BYTES ((size_t)256 << 20) /* the MI355X's Infinity Cache: the selection re-reads the tile from it */
 size_t t2p_sim_topk_workspace_bytes(int64_t nq, int64_t nc, int32_t k);
 int t2p_sim_topk(const float* queries, const float* cells, int64_t nq, int64_t nc, int32_t dim, int32_t k,
@@ -719,6 +725,13 @@ int t2p_group_rows_built(const float* xyz, const float* rgb, int64_t n_obj, int3
 int t2p_group_rows_pruned(const float* xyz, const float* rgb, int64_t n_obj, int32_t n_pts, const float* radius_host /*[3]*/,
                           int32_t self_loops, int32_t share_mask, uint8_t* const* fps_idx /*[3]*/, uint16_t* const* rows /*[3]*/,
                           uint16_t* const* n_rows /*[3]*/, t2p_stream_t stream);
+/* The range balancing of the SA edge kernels on its own (the device code t2p_encode_cells runs between the row builder and SA1):
+ *   prefix[i] = sum over g < i of ceil(n_rows[g] / tile_rows) for i in [0, n], so prefix[n] = total tiles;
+ *   bounds[b] = the first m in [0, n] with prefix[m] >= floor(b * total / n_wg) (b * total in 64 bits) for b < n_wg, bounds[n_wg] = n:
+ * workgroup b of n_wg owns the objects [bounds[b], bounds[b + 1]).  n_rows uint16 [n]; prefix int32 [n + 1]; bounds int32 [n_wg + 1];
+ * n >= 0, tile_rows >= 1, n_wg >= 1.  Integers only: the result does not depend on the launch. */
+int t2p_sa_balance(const uint16_t* n_rows, int32_t n, int32_t tile_rows, int32_t n_wg, int32_t* prefix /*[n+1]*/,
+                   int32_t* bounds /*[n_wg+1]*/, t2p_stream_t stream);
 int t2p_edge_counts(const uint16_t* rows, const uint16_t* n_rows, const int32_t* first_obj, int64_t n_obj, int32_t n_dense,
                     int32_t n_cent, int32_t self_loops, int32_t* counts, t2p_stream_t stream);
 int t2p_edge_expand(const uint16_t* rows, const uint16_t* n_rows, const int32_t* first_obj, const int32_t* cent_ptr, int64_t n_obj,

@@ -5,6 +5,11 @@
 # --groups G adds the group-restricted call (t2p_sim_topk_grouped; cells and queries uniform over G ids) timed in windows that
 # alternate with windows of the unrestricted call: `grouped_ms` and the per-pair ratios grouped / unrestricted.
 # --skip-torch leaves the float64 GEMM + topk yardstick out (A/B runs of two builds of the library: T2P_LIB).
+# --shapes route is the grid the k <= 16 routing threshold (csrc/sim_topk.hip: kTileMinPairs) was chosen on: nq in {64, 130, 256, 1000,
+# 1250} x nc in {1000, 4000, 12000, 100000}, to be run at --ks 1,10,16 once per forced path - two A/B builds of the library,
+#   python text2pos-cvpr2022_amd/build.py --variant lists T2P_SIM_TILE_MIN_PAIRS=4000000000000000000
+#   python text2pos-cvpr2022_amd/build.py --variant tile T2P_SIM_TILE_MIN_PAIRS=1
+# each selected with T2P_LIB; profiles/t04_topk_route_sweep.md holds the table.
 import argparse
 import json
 import os
@@ -53,6 +58,9 @@ def timed_pairs(fn_a, fn_b, steps, warmup, calls):
     return float(np.median(a_ms)), float(np.median(b_ms)), [b / a for a, b in zip(a_ms, b_ms)]
 
 
+ROUTE_SHAPES = ",".join(f"{nq}x{nc}" for nq in (64, 130, 256, 1000, 1250) for nc in (1000, 4000, 12000, 100000))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", default="1000x12000,1250x100000")
@@ -66,7 +74,7 @@ def main():
     a = ap.parse_args()
     assert torch.cuda.is_available(), "topk_sweep needs cuda:0: there is no CPU path to time"
     dev = torch.device("cuda:0")
-    for shape in a.shapes.split(","):
+    for shape in (ROUTE_SHAPES if a.shapes == "route" else a.shapes).split(","):
         nq, nc = (int(x) for x in shape.split("x"))
         g = torch.Generator().manual_seed(nq * 31 + nc)
         c = torch.nn.functional.normalize(torch.randn(nc, a.dim, generator=g), dim=-1).to(dev)

@@ -149,6 +149,7 @@ SYMBOLS = {
                                        C.POINTER(c_void), C.POINTER(c_void), c_void]),
     "t2p_group_rows_pruned": (C.c_int, [c_void, c_void, C.c_int64, C.c_int32, c_float_p, C.c_int32, C.c_int32, C.POINTER(c_void),
                                         C.POINTER(c_void), C.POINTER(c_void), c_void]),
+    "t2p_sa_balance": (C.c_int, [c_void, C.c_int32, C.c_int32, C.c_int32, c_void, c_void, c_void]),
     "t2p_edge_counts": (C.c_int, [c_void, c_void, c_void, C.c_int64, C.c_int32, C.c_int32, C.c_int32, c_void, c_void]),
     "t2p_edge_expand": (C.c_int, [c_void, c_void, c_void, c_void, C.c_int64, C.c_int32, C.c_int32, C.c_int32, c_void, c_void, c_void]),
     "t2p_dedup_rows": (C.c_int, [c_void, c_void, C.c_int64, C.c_int32, c_void, c_void, c_void]),

@@ -423,6 +423,14 @@ int t2p_sim_topk_grouped(const float* queries, const float* cells, const int32_t
                                    workspace, workspace_bytes, (hipStream_t)stream);
 }
 
+int t2p_sa_balance(const uint16_t* n_rows, int32_t n, int32_t tile_rows, int32_t n_wg, int32_t* prefix, int32_t* bounds,
+                   t2p_stream_t stream) {
+    T2P_CHECK_ARG(n >= 0 && tile_rows >= 1 && n_wg >= 1, "sa_balance: n=%d tile_rows=%d n_wg=%d (n >= 0, tile_rows >= 1, n_wg >= 1)", n,
+                  tile_rows, n_wg);
+    T2P_CHECK_ARG((n_rows != nullptr || n == 0) && prefix != nullptr && bounds != nullptr, "sa_balance: NULL argument");
+    return launch_sa_balance_arrays(n_rows, n, tile_rows, n_wg, prefix, bounds, (hipStream_t)stream);
+}
+
 int t2p_edge_counts(const uint16_t* rows, const uint16_t* n_rows, const int32_t* first_obj, int64_t n_obj, int32_t n_dense,
                     int32_t n_cent, int32_t self_loops, int32_t* counts, t2p_stream_t stream) {
     T2P_CHECK_ARG(n_obj >= 0 && (n_obj == 0 || (rows && n_rows && first_obj && counts)), "edge_counts: NULL argument");

@@ -1,4 +1,4 @@
-// All-pairs cosine scores in float64 + ordered top-k; up to k = 16 the scores never leave the chip.
+// All-pairs cosine scores in float64 + ordered top-k; small calls at k <= 16 keep the scores on the chip.
 //
 // Replaces the host loop of training/coarse.py:134-140 (per query: `scores = cell_encodings[:] @ text_encodings[q]`
 // on float64 arrays, `np.argsort(-scores)[0:max(top_k)]`).  The reference ranks in float64 (np.zeros arrays,
@@ -6,13 +6,24 @@
 // fly and every score is an fp64 fma chain -- ranking ties are then only exact duplicates, which are ordered by
 // ascending cell index (the pinned stable order, oracle/model.py::retrieve_topk_f64).
 //
-// k <= KREG:
+// Two paths.  Which one runs is a function of the problem size for every k in 1..KREG, never of k within that range:
+//     k <= KREG and nq * nc <  kTileMinPairs  -> register lists  (k_sim_partial + k_topk_merge)
+//     k <= KREG and nq * nc >= kTileMinPairs  -> score tile      (k_sim_scores + k_topk_select, with the caller's k)
+//     k >  KREG                               -> score tile
+// (a database so large that one query's scores exceed the tile, nc > 33,554,400, stays on the lists at k <= KREG).  The insertion
+// network of the lists sits inside the MFMA loop and halves its fp64 rate, and the merge walks 4 x splits x 16 candidates with one
+// wave per query: writing the scores once and selecting from the Infinity Cache was faster at every swept shape (64..1,250 queries
+// x 1,000..100,000 cells), 1.1 to 7 times, except k = 1 at 10^8 pairs and more, +2 % and +12 % (profiles/topk_sweep.py --shapes
+// route; profiles/t04_topk_route_sweep.md).  kTileMinPairs is the smallest swept product above the 130 x 1,000 call that the tests
+// pin to the lists.  Both paths give a pair the same score bits and order by better(): the result does not depend on the route.
+//
+// Register lists:
 // Pass 1  (grid = query blocks x cell splits): a workgroup keeps 128 queries as MFMA B operands in registers
 //         (fp32, widened at use), streams its cell range through LDS in 32-row blocks (register-prefetched) and
 //         every lane maintains a private sorted top-KCAP list per query in registers.
 // Pass 2  (one wave per query): k-round ordered selection over the 4 x splits partial lists.
 //
-// k > KREG (up to KMAX) cannot keep a list per lane.  The same product loop (sim_product_loop: the score bits of a pair do
+// Score tile (any k up to KMAX; k > KREG cannot keep a list per lane).  The same product loop (sim_product_loop: the score bits of a pair do
 // not depend on k) then writes a chunk of queries' float64 scores to the workspace (k_sim_scores), and one workgroup per
 // query selects exactly (k_topk_select): MSB-first radix passes over order-preserving 64-bit keys find the k-th key and
 // the number of keys above it, an ascending-index sweep with a scan collects everything above and the lowest-index ties,
@@ -30,6 +41,10 @@ namespace {
 constexpr int KREG = 16;     // per-lane list capacity == largest k of the register-list path
 constexpr int KCAP = KREG;
 constexpr int KMAX = 1024;   // largest supported k (the select kernel's LDS candidate array)
+#ifndef T2P_SIM_TILE_MIN_PAIRS   // (an A/B build of the sweep forces one path: profiles/topk_sweep.py)
+#define T2P_SIM_TILE_MIN_PAIRS 256000
+#endif
+constexpr int64_t kTileMinPairs = T2P_SIM_TILE_MIN_PAIRS;   // k <= KREG: nq * nc from which the score-tile path runs
 constexpr int QB = 128;      // queries per workgroup (4 waves x 2 tiles x 16)
 constexpr int CB = 32;       // cells staged per iteration
 typedef double f64x2 __attribute__((ext_vector_type(2)));
@@ -530,6 +545,13 @@ void launch_partial(dim3 grid, hipStream_t st, const float* Q, const float* Cm, 
     else hipLaunchKernelGGL((k_sim_partial<DIM, false>), grid, dim3(256), 0, st, Q, Cm, qg, cg, nq, nc, cps, ps, pi, sp);
 }
 
+// The route (the rule at the top of the file): a function of (nq, nc) alone for every k <= KREG
+bool use_score_tile(int64_t nq, int64_t nc, int k) {
+    if (k > KREG) return true;
+    const bool large = nq > 0 && nc > 0 && (nq >= kTileMinPairs || nc >= (kTileMinPairs + nq - 1) / nq);   // nq * nc >= kTileMinPairs
+    return large && score_chunk(1, nc) > 0;
+}
+
 // both entry points: qg / cg are nullptr for the unrestricted call
 int sim_topk_impl(const float* Q, const float* Cm, const int32_t* qg, const int32_t* cg, int64_t nq, int64_t nc, int dim, int k,
                   int64_t c_index_offset, int64_t* out_idx, double* out_score, void* ws, size_t ws_bytes, hipStream_t st);
@@ -537,7 +559,7 @@ int sim_topk_impl(const float* Q, const float* Cm, const int32_t* qg, const int3
 }  // namespace
 
 size_t sim_topk_workspace_bytes(int64_t nq, int64_t nc, int k) {
-    if (k > KREG) return (size_t)score_chunk(nq, nc) * score_ld(nc) * sizeof(double) + 256;
+    if (use_score_tile(nq, nc, k)) return (size_t)score_chunk(nq, nc) * score_ld(nc) * sizeof(double) + 256;
     const int sp = pick_splits(nq, nc);
     return (size_t)nq * sp * 4 * KCAP * (sizeof(double) + sizeof(int)) + 256;
 }
@@ -571,7 +593,7 @@ int sim_topk_impl(const float* Q, const float* Cm, const int32_t* qg, const int3
         set_error("sim_topk: workspace %zu B < required %zu B", ws_bytes, need);
         return T2P_E_WORKSPACE;
     }
-    if (k > KREG) {
+    if (use_score_tile(nq, nc, k)) {
         T2P_CHECK_ARG((((uintptr_t)ws) & 15) == 0, "sim_topk: workspace must be 16-byte aligned");
         const int64_t chunk = score_chunk(nq, nc), ld_s = score_ld(nc);
         double* S = (double*)ws;

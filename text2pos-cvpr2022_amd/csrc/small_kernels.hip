@@ -143,7 +143,7 @@ __global__ __launch_bounds__(256) void k_knn(const float* __restrict__ x, int di
 // Linear+BN+ReLU, then F.normalize.  A block owns 32 objects: the hidden layer goes to LDS, every thread then owns one
 // (or two) output columns for all 32 objects, so a W2 element is fetched once per 32 objects (one wave per object
 // re-read the whole 64 x D matrix per object: 12 GB of L2 traffic per call at 192 k objects).
-// ROWS = 32 for large batches; 8 for small ones (round 6): a thread's 64-step fma chain per row is serial, so a block of 32 rows takes
+// ROWS = 8 (round 6; batches of 16,384 rows and more run k_mlp3_rows below, ROWS = 32 before it): a thread's 64-step fma chain per row is serial, so a block of 32 rows takes
 // ~32 us whatever the batch, and a 1,000-object call (the reference's 64-cell batches) filled 31 of the 256 CUs with it.  The
 // summation order of an output does not depend on ROWS: same bits.
 template <int kMlp3Rows>
@@ -208,6 +208,158 @@ __global__ __launch_bounds__(256) void k_mlp3_norm(const float* __restrict__ in3
             out[(row0 + r) * ld_out + col0 + c] = o[j][r] / (nrm > 1e-12f ? nrm : 1e-12f);
         }
     }
+}
+
+// The same encoders for large batches (n_rows >= 16,384), the bits of k_mlp3_norm.  That kernel issues one broadcast LDS read of
+// hid[r][k] per fma; here a LANE owns a row: its 64 hidden values sit in registers, and every weight is wave-uniform, so an fma
+// takes its weight from an SGPR (v_fmac_f32 v, s, v; W1, b1, b2 through the scalar cache, W2 through mlp3_k8) - no LDS read at all.
+// A block is 64 rows x min(4, D / 64) waves; wave w computes the columns c = 256 j + 64 w + l (l = 0..63, j < NJ) of its rows, which
+// is the set of columns k_mlp3_norm's wave w holds, so the partial sums of squares are the same four:
+//   * an output is the same fmaf chain (from b2[c] over k = 0..63 ascending, then the ReLU);
+//   * v[l] = fmaf(o, o, 0) for column 64 w + l, then fmaf(o', o', v[l]) for column 256 + 64 w + l where D has it;
+//   * the xor butterfly 32, 16, .., 1 over l pairs (l, l + 32), then (l, l + 16), ..: the same tree, rebuilt in registers
+//     (a + b == b + a bit for bit); a wave the block does not have (D < 256) contributes the +0.0 its butterfly gave;
+//   * sqrtf((ss0 + ss1) + (ss2 + ss3)), the clamp and the true division are the expressions above.
+// The normalised rows leave through LDS, 32 columns at a time, so that a store instruction writes eight whole 128-byte lines
+// (a lane writing its own row would touch 64 lines with 16 bytes each).
+// Eight k of a lane's row against the wave's 64 columns: lane l loads W2[k][cbase + l] (one coalesced 256-byte vector load per k,
+// many in flight), and the fma of column c takes its weight from lane c through v_readlane - an SGPR operand, no LDS read.
+// (Scalar loads of the weights were tried first: 16 of them per s_load, but the 64 KB of W2 do not fit the scalar cache and a wave
+// waits ~1,200 cycles per load with nothing to overlap it: 125 us per launch against k_mlp3_norm<32>'s 92.)
+// (One function per eight k and no loop around the calls: the unroller stops short of a body this large, and a rolled loop would
+// index hid[] dynamically.)
+template <int K0>
+__device__ __forceinline__ void mlp3_k8(const float (&hid)[64], const float* __restrict__ wl, int D, float (&o)[64]) {
+    float wv[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) wv[i] = wl[(K0 + i) * D];
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+#pragma unroll
+        for (int c0 = 0; c0 < 64; c0 += 8) {   // eight broadcasts, then their eight fmas: no wait between a v_readlane and its use
+            float w[8];
+#pragma unroll
+            for (int e = 0; e < 8; e++) w[e] = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, wv[i]), c0 + e));
+#pragma unroll
+            for (int e = 0; e < 8; e++) o[c0 + e] = fmaf(hid[K0 + i], w[e], o[c0 + e]);
+        }
+    }
+}
+
+// columns cbase .. cbase + 63 of the lane's row
+__device__ __forceinline__ void mlp3_slice(const float (&hid)[64], const float* __restrict__ w2, const float* __restrict__ b2, int D,
+                                           int cbase, int lane, float (&o)[64]) {
+#pragma unroll
+    for (int c = 0; c < 64; c++) o[c] = b2[cbase + c];
+    const float* wl = w2 + cbase + lane;
+    mlp3_k8<0>(hid, wl, D, o);
+    mlp3_k8<8>(hid, wl, D, o);
+    mlp3_k8<16>(hid, wl, D, o);
+    mlp3_k8<24>(hid, wl, D, o);
+    mlp3_k8<32>(hid, wl, D, o);
+    mlp3_k8<40>(hid, wl, D, o);
+    mlp3_k8<48>(hid, wl, D, o);
+    mlp3_k8<56>(hid, wl, D, o);
+#pragma unroll
+    for (int c = 0; c < 64; c++) o[c] = fmaxf(o[c], 0.f);
+}
+
+// o / den of 64 rows x 64 columns to out through the wave's LDS tile, 32 columns at a time.  Every wave of the block calls it
+// (the barriers), whether it has these columns or not.
+__device__ __forceinline__ void mlp3_store(const float (&o)[64], float den, bool have, float (*tile)[36], int lane, int64_t row0,
+                                           int64_t n_rows, float* __restrict__ out, int ld_out, int c_first, bool vec_out) {
+#pragma unroll
+    for (int half = 0; half < 2; half++) {
+        if (have) {
+#pragma unroll
+            for (int q = 0; q < 8; q++) {
+                f32x4 t;
+#pragma unroll
+                for (int e = 0; e < 4; e++) t[e] = o[half * 32 + q * 4 + e] / den;
+                *(f32x4*)&tile[lane][q * 4] = t;
+            }
+        }
+        __syncthreads();
+        if (have) {
+#pragma unroll
+            for (int it = 0; it < 8; it++) {
+                const int r = it * 8 + (lane >> 3), c4 = (lane & 7) * 4;
+                const f32x4 t = *(const f32x4*)&tile[r][c4];
+                if (row0 + r < n_rows) {
+                    float* dst = out + (row0 + r) * ld_out + c_first + half * 32 + c4;
+                    if (vec_out) *(f32x4*)dst = t;
+                    else {
+#pragma unroll
+                        for (int e = 0; e < 4; e++) dst[e] = t[e];
+                    }
+                }
+            }
+        }
+        __syncthreads();
+    }
+}
+
+template <int NJ>
+__global__ __launch_bounds__(256) void k_mlp3_rows(const float* __restrict__ in3, int64_t n_rows,
+                                                   const float* __restrict__ w1, const float* __restrict__ b1,
+                                                   const float* __restrict__ w2, const float* __restrict__ b2, int D,
+                                                   float* __restrict__ out, int ld_out, int col0) {
+    constexpr int TLD = 36;   // 32 columns + 4: 16-byte LDS accesses of 16 consecutive rows fall on distinct banks
+    __shared__ __attribute__((aligned(16))) float tile[4][64][TLD];
+    __shared__ float ss[4][64];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int n_wave = blockDim.x >> 6;
+    const int64_t row0 = (int64_t)blockIdx.x * 64;
+    const int64_t row = row0 + lane;
+    float x0 = 0.f, x1 = 0.f, x2 = 0.f;
+    if (row < n_rows) {
+        x0 = in3[row * 3];
+        x1 = in3[row * 3 + 1];
+        x2 = in3[row * 3 + 2];
+    }
+    float hid[64];
+#pragma unroll
+    for (int u = 0; u < 64; u++) {
+        float a = b1[u];
+        a = fmaf(x0, w1[u], a);
+        a = fmaf(x1, w1[64 + u], a);
+        a = fmaf(x2, w1[128 + u], a);
+        hid[u] = fmaxf(a, 0.f);
+    }
+    const int cbase = 64 * wave;                       // < D: the block has min(4, D / 64) waves
+    const bool have1 = NJ > 1 && 256 + cbase < D;      // (wave-uniform)
+    float o0[64];
+    [[maybe_unused]] float o1[NJ > 1 ? 64 : 1];
+    mlp3_slice(hid, w2, b2, D, cbase, lane, o0);
+    // (a wave without a second slice, D = 320 or 384, repeats its first one and drops it: the block's other waves are at work on
+    // theirs, it would wait for them at the barrier anyway, and the kernel stays one straight line)
+    if constexpr (NJ > 1) mlp3_slice(hid, w2, b2, D, have1 ? 256 + cbase : cbase, lane, o1);
+    // this wave's partial sum of squares of the lane's row: k_mlp3_norm's butterfly tree over l
+    {
+        float v[64];
+#pragma unroll
+        for (int l = 0; l < 64; l++) {
+            v[l] = fmaf(o0[l], o0[l], 0.f);
+            if constexpr (NJ > 1) {
+                if (have1) v[l] = fmaf(o1[l], o1[l], v[l]);
+            }
+        }
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) {
+#pragma unroll
+            for (int l = 0; l < off; l++) v[l] = v[l] + v[l + off];
+        }
+        ss[wave][lane] = v[0];
+    }
+    __syncthreads();
+    const float p0 = ss[0][lane], p1 = n_wave > 1 ? ss[1][lane] : 0.f, p2 = n_wave > 2 ? ss[2][lane] : 0.f,
+                p3 = n_wave > 3 ? ss[3][lane] : 0.f;
+    const float nrm = sqrtf((p0 + p1) + (p2 + p3));
+    const float den = nrm > 1e-12f ? nrm : 1e-12f;
+    const bool vec_out = ((((uintptr_t)out) & 15) == 0) && (ld_out & 3) == 0 && (col0 & 3) == 0;
+    mlp3_store(o0, den, true, tile[wave], lane, row0, n_rows, out, ld_out, col0 + cbase, vec_out);
+    if constexpr (NJ > 1) mlp3_store(o1, den, have1, tile[wave], lane, row0, n_rows, out, ld_out, col0 + 256 + cbase, vec_out);
 }
 
 // ---- on-device dataloader ---------------------------------------------------------------------------
@@ -639,10 +791,11 @@ int launch_mlp3_norm(const float* in3, int64_t n_rows, const float* w1, const fl
     T2P_CHECK_ARG(D % 64 == 0 && D <= 512, "mlp3_norm: D=%d must be a multiple of 64, <= 512", D);
     if (n_rows == 0) return 0;
     ProfScope ps_("mlp3_norm", st);
-    if (n_rows >= 16384)
-        hipLaunchKernelGGL(k_mlp3_norm<32>, dim3((unsigned)((n_rows + 31) / 32)), dim3(256), 0, st, in3, n_rows, w1, b1, w2, b2, D, out, ld_out,
-                           col0);
-    else
+    if (n_rows >= 16384) {   // a lane per row, weights from SGPRs: 64 rows x min(4, D / 64) waves per block
+        const dim3 grid((unsigned)((n_rows + 63) / 64)), block(64 * (D >= 256 ? 4 : D / 64));
+        if (D > 256) hipLaunchKernelGGL(k_mlp3_rows<2>, grid, block, 0, st, in3, n_rows, w1, b1, w2, b2, D, out, ld_out, col0);
+        else hipLaunchKernelGGL(k_mlp3_rows<1>, grid, block, 0, st, in3, n_rows, w1, b1, w2, b2, D, out, ld_out, col0);
+    } else
         hipLaunchKernelGGL(k_mlp3_norm<8>, dim3((unsigned)((n_rows + 7) / 8)), dim3(256), 0, st, in3, n_rows, w1, b1, w2, b2, D, out, ld_out,
                            col0);
     T2P_CHECK_LAUNCH("mlp3_norm");

@@ -396,6 +396,8 @@ struct SaParams {
 int launch_ws_sa(int H, int C, const SaParams& p, hipStream_t st);
 // k_balance alone, for a kernel launched outside launch_sa_balance_levels (p.balanced == 0)
 int launch_sa_balance(const SaParams& p, int tile_rows, int n_wg, hipStream_t st);
+// the same launch on bare arrays (t2p_sa_balance): prefix [n + 1], bounds [n_wg + 1]
+int launch_sa_balance_arrays(const uint16_t* n_rows, int n, int tile_rows, int n_wg, int32_t* prefix, int32_t* bounds, hipStream_t st);
 // Pseudo-centroid code of the shared tail rows (GroupTables::share_tail) in the centroid byte of a row of SA level 2: 64, the
 // first free value of the 7-bit field behind its 64 centroids; 64 * C * 4 fits the u16 accumulator offsets of k_sa_rows.
 constexpr int kSaTailCode = 64;

@@ -63,44 +63,121 @@ struct SaCfg {
     }
 };
 
-// Tile-count prefix sums over the objects and balanced contiguous ranges for n_wg workgroups.  One block.
+// Tile-count prefix sums over the objects and balanced contiguous ranges for n_wg workgroups.  One block of kBalT threads.
+//   prefix[i] = sum over g < i of ceil(n_rows[g] / tile_rows), prefix[n] = total;
+//   bounds[b] = first m in [0, n] with prefix[m] >= floor(b * total / n_wg) (b * total in 64 bits), bounds[n_wg] = n.
+// The objects go through in chunks of kBalT * 8: a thread reads its 8 consecutive u16 counts as one 16-byte load (the next chunk's
+// load is issued before this chunk's scan), the chunk is scanned with wave shuffles and one LDS level of 16 wave totals, and the
+// thread writes its 8 prefixes as two 16-byte stores.  Every S-th prefix (S = 8 << sh, the smallest step whose table fits) is kept
+// in LDS; a bound is a binary search over that table and one batch of at most S independent loads of the prefixes in between.
+constexpr int kBalT = 1024;        // threads of the balancing block
+constexpr int kBalCoarse = 8192;   // largest index of the LDS prefix table (n <= 65,536: every 8th prefix)
+
 __device__ __forceinline__ void balance_body(const uint16_t* __restrict__ n_rows, int n, int tile_rows, int n_wg,
                                              int32_t* __restrict__ prefix, int32_t* __restrict__ bounds) {
-    __shared__ int part[1024];
-    const int tid = threadIdx.x;
-    const int per = (n + 1023) / 1024;
-    const int lo = tid * per, hi = (lo + per) < n ? (lo + per) : n;
-    int s = 0;
-    for (int i = lo; i < hi; i++) s += ((int)n_rows[i] + tile_rows - 1) / tile_rows;
-    part[tid] = s;
-    __syncthreads();
-    for (int off = 1; off < 1024; off <<= 1) {
-        int v = tid >= off ? part[tid - off] : 0;
-        __syncthreads();
-        part[tid] += v;
-        __syncthreads();
+    __shared__ int coarse[kBalCoarse + 1];
+    __shared__ int wtot[2][kBalT / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int sh = 3;   // log2 of the table step
+    while ((n >> sh) > kBalCoarse) sh++;
+    const bool vec_in = (((uintptr_t)n_rows) & 15) == 0, vec_out = (((uintptr_t)prefix) & 15) == 0;
+    const unsigned tr = (unsigned)tile_rows;
+
+    typedef uint16_t u16x8 __attribute__((ext_vector_type(8)));
+    typedef int i32x4 __attribute__((ext_vector_type(4)));
+    auto load8 = [&](int i0) -> u16x8 {   // counts i0 .. i0 + 7, zero past n
+        u16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
+        if (i0 + 8 <= n && vec_in) v = *(const u16x8*)(n_rows + i0);
+        else {
+#pragma unroll
+            for (int e = 0; e < 8; e++)
+                if (i0 + e < n) v[e] = n_rows[i0 + e];
+        }
+        return v;
+    };
+
+    int carry = 0;   // tiles of the chunks before this one (the same in every thread)
+    u16x8 cur = load8(tid * 8);
+    for (int base = 0, it = 0; base < n; base += kBalT * 8, it++) {
+        const int i0 = base + tid * 8;
+        u16x8 nxt = {0, 0, 0, 0, 0, 0, 0, 0};
+        if (base + kBalT * 8 < n) nxt = load8(i0 + kBalT * 8);
+        int t[8], s = 0;
+#pragma unroll
+        for (int e = 0; e < 8; e++) {
+            t[e] = (int)(((unsigned)cur[e] + tr - 1) / tr);
+            s += t[e];
+        }
+        int inc = s;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const int up = __shfl_up(inc, o, 64);
+            if (lane >= o) inc += up;
+        }
+        if (lane == 63) wtot[it & 1][wave] = inc;
+        __syncthreads();   // (one barrier per chunk: the wave totals alternate between two buffers)
+        int before = 0, all = 0;
+#pragma unroll
+        for (int w = 0; w < kBalT / 64; w++) {
+            const int v = wtot[it & 1][w];
+            before += w < wave ? v : 0;
+            all += v;
+        }
+        int run = carry + before + inc - s;   // exclusive prefix of object i0
+        carry += all;
+        if (i0 < n && (i0 & ((1 << sh) - 1)) == 0) coarse[i0 >> sh] = run;
+        int p[8];
+#pragma unroll
+        for (int e = 0; e < 8; e++) {
+            p[e] = run;
+            run += t[e];
+        }
+        if (i0 + 8 <= n && vec_out) {
+            *(i32x4*)(prefix + i0) = i32x4{p[0], p[1], p[2], p[3]};
+            *(i32x4*)(prefix + i0 + 4) = i32x4{p[4], p[5], p[6], p[7]};
+        } else {
+#pragma unroll
+            for (int e = 0; e < 8; e++)
+                if (i0 + e < n) prefix[i0 + e] = p[e];
+        }
+        cur = nxt;
     }
-    int run = part[tid] - s;  // exclusive
-    for (int i = lo; i < hi; i++) {
-        prefix[i] = run;
-        run += ((int)n_rows[i] + tile_rows - 1) / tile_rows;
+    const int total = carry;
+    if (tid == 0) {
+        prefix[n] = total;
+        if ((n & ((1 << sh) - 1)) == 0) coarse[n >> sh] = total;
     }
-    if (tid == 1023) prefix[n] = part[1023];
-    __syncthreads();
-    const int total = part[1023];
-    for (int b = tid; b <= n_wg; b += 1024) {
+    __syncthreads();   // the table, and this block's prefix stores for the loads below
+    const int n_coarse = (n >> sh) + 1;   // table entries: prefix[j << sh], (j << sh) <= n
+    for (int b = tid; b <= n_wg; b += kBalT) {
         // first object whose prefix >= b * total / n_wg
         const long long target = ((long long)b * total) / n_wg;
-        int l = 0, r = n;
+        int l = 0, r = n_coarse;   // first table entry >= target (n_coarse: none)
         while (l < r) {
             const int m = (l + r) >> 1;
-            if (prefix[m] < target) l = m + 1; else r = m;
+            if (coarse[m] < target) l = m + 1; else r = m;
         }
-        bounds[b] = b == n_wg ? n : l;
+        int ans = 0;
+        if (l > 0) {
+            // prefix[lo - 1] < target, and prefix[hi] >= target (the table entry, or prefix[n] = total): the answer is lo + the
+            // number of prefixes below the target in [lo, hi) - they are non-decreasing
+            const int lo = ((l - 1) << sh) + 1;
+            const int hi = l < n_coarse ? (l << sh) : n;
+            int cnt = 0;
+            for (int x0 = lo; x0 < hi; x0 += 8) {
+                int v[8];
+#pragma unroll
+                for (int e = 0; e < 8; e++) v[e] = prefix[(x0 + e) < hi ? (x0 + e) : hi];
+#pragma unroll
+                for (int e = 0; e < 8; e++) cnt += ((x0 + e) < hi && v[e] < target) ? 1 : 0;
+            }
+            ans = lo + cnt;
+        }
+        bounds[b] = b == n_wg ? n : ans;
     }
 }
 
-__global__ __launch_bounds__(1024) void k_balance(const uint16_t* __restrict__ n_rows, int n, int tile_rows, int n_wg,
+__global__ __launch_bounds__(kBalT) void k_balance(const uint16_t* __restrict__ n_rows, int n, int tile_rows, int n_wg,
                                                   int32_t* __restrict__ prefix, int32_t* __restrict__ bounds) {
     balance_body(n_rows, n, tile_rows, n_wg, prefix, bounds);
 }
@@ -112,7 +189,7 @@ struct BalanceJobs {
     int tile_rows[3], n_wg[3];
     int n;
 };
-__global__ __launch_bounds__(1024) void k_balance_levels(BalanceJobs j) {  // one block per level
+__global__ __launch_bounds__(kBalT) void k_balance_levels(BalanceJobs j) {  // one block per level
     const int l = blockIdx.x;
     balance_body(j.n_rows[l], j.n, j.tile_rows[l], j.n_wg[l], j.prefix[l], j.bounds[l]);
 }
@@ -409,12 +486,15 @@ __global__ __launch_bounds__(NT, 2) void k_sa_stream(SaParams p) {
 
 }  // namespace
 
-int launch_sa_balance(const SaParams& p, int tile_rows, int n_wg, hipStream_t st) {
+int launch_sa_balance_arrays(const uint16_t* n_rows, int n, int tile_rows, int n_wg, int32_t* prefix, int32_t* bounds, hipStream_t st) {
     ProfScope ps_("sa_balance", st);
-    hipLaunchKernelGGL(k_balance, dim3(1), dim3(1024), 0, st, p.n_rows, (int)p.n_obj, tile_rows, n_wg, p.prefix_ws,
-                       p.bounds_ws);
+    hipLaunchKernelGGL(k_balance, dim3(1), dim3(kBalT), 0, st, n_rows, n, tile_rows, n_wg, prefix, bounds);
     T2P_CHECK_LAUNCH("sa_balance");
     return 0;
+}
+
+int launch_sa_balance(const SaParams& p, int tile_rows, int n_wg, hipStream_t st) {
+    return launch_sa_balance_arrays(p.n_rows, (int)p.n_obj, tile_rows, n_wg, p.prefix_ws, p.bounds_ws, st);
 }
 
 namespace {
@@ -520,7 +600,7 @@ int launch_sa_balance_levels(const SaParams p[3], const int H[3], const int C[3]
         T2P_TRY(sa_launch_shape(H[l], C[l], p[l], p[l].n_obj, &j.tile_rows[l], &j.n_wg[l]));
     }
     ProfScope ps_("sa_balance", st);
-    hipLaunchKernelGGL(k_balance_levels, dim3(3), dim3(1024), 0, st, j);
+    hipLaunchKernelGGL(k_balance_levels, dim3(3), dim3(kBalT), 0, st, j);
     T2P_CHECK_LAUNCH("sa_balance");
     return 0;
 }

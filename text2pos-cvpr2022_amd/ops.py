@@ -244,6 +244,19 @@ def group_edges(xyz: torch.Tensor, first_obj: torch.Tensor, radius=(0.2, 0.3, 0.
     return out
 
 
+def sa_balance(n_rows: torch.Tensor, tile_rows: int, n_wg: int):
+    """The SA edge kernels' range balancing (t2p_sa_balance): n_rows int16 [n] (uint16 bits, as group_rows returns them).
+    Returns (prefix int32 [n + 1]: exclusive sums of ceil(n_rows / tile_rows); bounds int32 [n_wg + 1]: workgroup b owns the
+    objects [bounds[b], bounds[b + 1]))."""
+    _need(n_rows, "n_rows", torch.int16, 1)
+    dev, n = n_rows.device, n_rows.shape[0]
+    prefix = torch.empty((n + 1,), dtype=torch.int32, device=dev)
+    bounds = torch.empty((int(n_wg) + 1,), dtype=torch.int32, device=dev)
+    L.check(L.lib().t2p_sa_balance(_ptr(n_rows), n, int(tile_rows), int(n_wg), _ptr(prefix), _ptr(bounds), _stream(dev)),
+            "t2p_sa_balance")
+    return prefix, bounds
+
+
 def group_rows(xyz: torch.Tensor, radius=(0.2, 0.3, 0.4), self_loops: bool = True, share_mask: int = 0):
     """k_sample_group's compact edge-row lists of the three SA levels (t2p_group_rows_shared).  xyz [n_obj, n_pts, 3] fp32.
     share_mask: bit 1 = SA level 2 in the shared form its f16x3 kernel consumes (the hits of the centroids that repeat

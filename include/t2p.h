@@ -7,6 +7,14 @@
  * training/coarse.py::eval_epoch.  The entry points below are what a ctypes binding of that class calls
  * (INTEGRATION.md shows the stub); each one names the reference interface it replaces.
  *
+ * This file is the ONE statement of the ABI.  The C++ compiler holds every definition to it (each .hip that defines an export
+ * includes it) and the Python binding is generated from it at import (text2pos-cvpr2022_amd/_lib.py parses the prototypes, the
+ * typedef structs and the integer #define T2P_* below; tests/test_abi_host.py checks the result against the host C compiler).
+ * So it stays within the C that parser reads: scalar types int, int32_t, int64_t, uint32_t, size_t, float; pointers to those, to
+ * void, char, double, uint8_t, uint16_t, uint64_t and to the structs; members `T name`, `T name[n]`, `T a, b` and `T *a, *b`; no
+ * function pointers, bit-fields, nested structs or array parameters.  Anything else fails the import, naming the declaration.
+ * Change a signature or a struct: bump T2P_ABI_VERSION and regenerate tests/golden/abi.json.
+ *
  * Conventions
  *   - Every pointer is a DEVICE pointer (HBM) unless its name ends in _host.  Buffers are owned by the caller;
  *     the library never allocates or frees device memory and keeps no global mutable state besides the

@@ -5,7 +5,6 @@ tests/test_gpu_fine_stats.py and tests/test_gpu_fine_feed.py."""
 import ctypes as C
 import io
 import os
-import re
 import sys
 
 import numpy as np
@@ -18,7 +17,6 @@ from fine_scene import make_fine_scene  # noqa: E402
 from text2pos_amd import _lib, data as D, io as IO, ops, training as T  # noqa: E402
 from text2pos_amd.scene import DeviceScene  # noqa: E402
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAME = "t2p_fine_step_stats"
 COMBOS = [(c, l) for c in ("pose", "best") for l in ("center", "closest")]
 PAD, HINTS = 8, 6
@@ -26,14 +24,11 @@ PAD, HINTS = 8, 6
 
 # ---- header, binding, exports, refusals -------------------------------------------------------------------------------------------
 def test_entry_point_is_declared_bound_and_exported():
-    header = open(os.path.join(ROOT, "include", "t2p.h")).read()
-    m = re.search(r"int\s+" + NAME + r"\s*\(([^;]*)\)\s*;", header)
-    assert m, f"{NAME} is not declared in include/t2p.h"
-    params = [p for p in m.group(1).split(",") if p.strip()]
-    assert NAME in _lib.SYMBOLS and len(params) == 16 == len(_lib.SYMBOLS[NAME][1])
+    header = open(_lib.HEADER).read()
+    assert NAME in _lib.SYMBOLS and len(_lib.SYMBOLS[NAME][1]) == 16       # (types and layouts: tests/test_abi_host.py)
     assert hasattr(_lib.lib(), NAME) and callable(ops.fine_step_stats)
-    assert int(re.search(r"#define T2P_ABI_VERSION (\d+)", header).group(1)) == _lib.ABI_VERSION == _lib.lib().t2p_abi_version()
-    assert int(re.search(r"#define T2P_FINE_STATS_MAX_BATCH (\d+)", header).group(1)) == ops.FINE_STATS_MAX_BATCH
+    assert _lib.ABI_VERSION == _lib.lib().t2p_abi_version()
+    assert ops.FINE_STATS_MAX_BATCH == _lib.DEFINES["T2P_FINE_STATS_MAX_BATCH"] == 1024
     for cite in ("training/losses.py:33-62", "training/losses.py:81-123", "models/superglue_matcher.py:139-161"):
         assert cite in header, cite
     from text2pos_amd import build

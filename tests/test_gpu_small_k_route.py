@@ -3,8 +3,6 @@ T2P_SIM_TOPK_TILE_MIN_PAIRS runs k_sim_scores + k_topk_select with the caller's 
 At the smallest routed shape the result is held to the float64 oracle (indices exact, scores to 1e-12) and, bit for bit, to the
 register-list path on the same pairs: the same call on query blocks of 8, which stay below the threshold."""
 import functools
-import os
-import re
 
 import numpy as np
 import pytest
@@ -14,7 +12,6 @@ import test_gpu_topk_any as TA
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NQ, QBLOCK = 97, 8
 KS = (1, 10, 16)
 LISTS, TILE = {"sim_partial", "topk_merge"}, {"sim_scores", "topk_select"}
@@ -33,8 +30,8 @@ def _ws(nq, nc, k):
 def _threshold():
     """T of the rule nq * nc >= T: the header's constant, confirmed on the library's own size query (one query: below T the
     lists' workspace, from T on one row of the score tile)."""
-    with open(os.path.join(ROOT, "include", "t2p.h")) as f:
-        t = int(re.search(r"#define\s+T2P_SIM_TOPK_TILE_MIN_PAIRS\s+(\d+)", f.read()).group(1))
+    from text2pos_amd import _lib as L
+    t = L.DEFINES["T2P_SIM_TOPK_TILE_MIN_PAIRS"]
     tile_row = lambda nc: 8 * ((nc + 15) // 16 * 16) + 256
     assert _ws(1, t, 10) == tile_row(t) and _ws(1, t - 1, 10) != tile_row(t - 1)
     assert t > 130 * 1000

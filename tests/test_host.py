@@ -14,13 +14,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_library_loads_and_exports_every_declared_symbol():
-    header = open(os.path.join(ROOT, "include", "t2p.h")).read()
-    declared = set(re.findall(r"\b(t2p_[a-z0-9_]+)\s*\(", header))
-    assert len(declared) >= 14
+    assert len(_lib.SYMBOLS) >= 14              # (read from include/t2p.h; signatures and layouts: tests/test_abi_host.py)
     handle = _lib.lib()
-    for name in declared:
+    for name in _lib.SYMBOLS:
         assert hasattr(handle, name), f"{name} declared in include/t2p.h but not exported"
-    assert declared == set(_lib.SYMBOLS), "ctypes binding and header disagree"
     assert handle.t2p_abi_version() == _lib.ABI_VERSION
 
 

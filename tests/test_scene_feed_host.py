@@ -2,8 +2,6 @@
 device), data.flip_cell, the mirror tables of a DeviceScene, and the determinism and draw sanity of training.SceneCoarseFeed.  The GPU
 side is tests/test_gpu_scene_feed.py."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
@@ -12,7 +10,6 @@ import torch
 from text2pos_amd import _lib, data as D, io as IO, synthetic as S, training as T
 from text2pos_amd.scene import DeviceScene
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAME = "t2p_pack_scene_objects_aug"
 DIRS = ["north", "south", "east", "west", "on-top"]
 
@@ -39,14 +36,10 @@ def _toy_scene(n_cells=16, n_poses=40, seed=5, max_pts=60):
 
 # ---- header, binding, exports, refusals -------------------------------------------------------------------------------------------
 def test_aug_entry_point_is_declared_bound_and_exported():
-    header = open(os.path.join(ROOT, "include", "t2p.h")).read()
-    m = re.search(r"int\s+" + NAME + r"\s*\(([^;]*)\)\s*;", header)
-    assert m, f"{NAME} is not declared in include/t2p.h"
-    params = [p for p in m.group(1).split(",") if p.strip()]
-    assert NAME in _lib.SYMBOLS
-    assert len(params) == 19 == len(_lib.SYMBOLS[NAME][1])
+    header = open(_lib.HEADER).read()
+    assert NAME in _lib.SYMBOLS and len(_lib.SYMBOLS[NAME][1]) == 19       # (types and layouts: tests/test_abi_host.py)
     assert hasattr(_lib.lib(), NAME)
-    assert int(re.search(r"#define T2P_ABI_VERSION (\d+)", header).group(1)) == 32 == _lib.ABI_VERSION == _lib.lib().t2p_abi_version()
+    assert _lib.ABI_VERSION == _lib.lib().t2p_abi_version()
     for cite in ("cells.py:79-91", "utils.py:13-86", "training/coarse.py:192-198"):
         assert cite in header, cite
 

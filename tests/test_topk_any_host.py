@@ -1,26 +1,21 @@
 """Host side of "top-k for any k up to 1,024": the workspace arithmetic of t2p_sim_topk (no GPU needed: the size query only
 computes) against the formula include/t2p.h documents, and the pipeline's early refusal of a top_k beyond the limit."""
-import os
-import re
-
 import numpy as np
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MIB = 1 << 20
 SHAPES = [(1000, 12000), (1250, 100000), (10000, 1000000)]
 
 
-def _header():
-    with open(os.path.join(ROOT, "include", "t2p.h")) as f:
-        return f.read()
-
-
 def _macro(name):
-    m = re.search(r"#define\s+%s\s+\(?\(?(?:size_t\))?\s*(\d+)\s*(?:<<\s*(\d+))?" % name, _header())
-    assert m, name
-    return int(m.group(1)) << int(m.group(2) or 0)
+    """An integer limit as the binding read it from include/t2p.h; the tile size is a cast expression there, so it is matched as text."""
+    from text2pos_amd import _lib
+    if name == "T2P_SIM_TOPK_TILE_BYTES":
+        with open(_lib.HEADER) as f:
+            assert "#define T2P_SIM_TOPK_TILE_BYTES ((size_t)256 << 20)" in f.read()
+        return 256 << 20
+    return _lib.DEFINES[name]
 
 
 def _documented_bytes(nq, nc):

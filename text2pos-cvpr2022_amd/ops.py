@@ -39,7 +39,7 @@ def _need(t: torch.Tensor, name: str, dtype, ndim=None, device=None):
     return t
 
 
-DEFAULT_CHUNK_OBJECTS = 65000   # include/t2p.h: T2P_DEFAULT_CHUNK_OBJECTS
+DEFAULT_CHUNK_OBJECTS = L.DEFINES["T2P_DEFAULT_CHUNK_OBJECTS"]
 
 
 def workspace(device, nbytes: int, tag: str) -> torch.Tensor:
@@ -570,16 +570,18 @@ def make_cell_config(n_pts=256, embed_dim=256, pointnet_features=2, use_features
 def make_cell_weights(packed: Dict[str, object]) -> L.CellWeights:
     """packed: name -> tensor (or list of 3 tensors for the sa_* members), fp32 contiguous on the GPU."""
     w = L.CellWeights()
-    for name in L.CellWeights._names[0]:
-        ts = packed[name]
-        for t in ts:
-            _need(t, name, torch.float32)
-        setattr(w, name, (C.c_void_p * 3)(*[t.data_ptr() for t in ts]))
-    for name in L.CellWeights._names[1]:
-        t = packed.get(name)
-        if t is not None:
-            _need(t, name, torch.float32)
-        setattr(w, name, 0 if t is None else t.data_ptr())
+    fields = L.CellWeights._fields_   # the fp32 matrices lead the struct, up to the first split-precision image
+    for name, ctype in fields[:[n for n, _ in fields].index("sa_w2_x3")]:
+        if issubclass(ctype, C.Array):          # const float* name[3]: one per SA level
+            ts = packed[name]
+            for t in ts:
+                _need(t, name, torch.float32)
+            setattr(w, name, ctype(*[t.data_ptr() for t in ts]))
+        else:                                   # const float* name
+            t = packed.get(name)
+            if t is not None:
+                _need(t, name, torch.float32)
+            setattr(w, name, 0 if t is None else t.data_ptr())
     for name in ("sa_w2_x3", "sa_w1_x3"):
         x3 = packed.get(name)
         if x3 is not None:
@@ -1191,7 +1193,7 @@ def colsum(x: torch.Tensor) -> torch.Tensor:
     return out
 
 
-FINE_STATS_MAX_BATCH = 1024   # T2P_FINE_STATS_MAX_BATCH (include/t2p.h)
+FINE_STATS_MAX_BATCH = L.DEFINES["T2P_FINE_STATS_MAX_BATCH"]
 
 
 def fine_step_row(step_row: torch.Tensor) -> np.ndarray:
@@ -1248,7 +1250,7 @@ def fine_step_stats(matches0: torch.Tensor, matches1: torch.Tensor, offsets: tor
     return sample_stats, step_row
 
 
-LOCALIZE_MAX_TOP_K = 1024    # T2P_LOCALIZE_MAX_TOP_K (include/t2p.h)
+LOCALIZE_MAX_TOP_K = L.DEFINES["T2P_LOCALIZE_MAX_TOP_K"]
 
 
 def match_indexed(obj_table: torch.Tensor, hint_table: torch.Tensor, obj_row: torch.Tensor, hint_row: torch.Tensor,

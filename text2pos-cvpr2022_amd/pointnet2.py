@@ -15,10 +15,10 @@ from types import SimpleNamespace
 import torch
 import torch.nn as nn
 
-from . import ops, packing
+from . import _lib, ops, packing
 from .modules import Fp16RangeGuard, PicklableModule, get_mlp
 
-MAX_BATCH_OBJECTS = 65535    # include/t2p.h: T2P_MAX_CHUNK_OBJECTS - the batch is one cell
+MAX_BATCH_OBJECTS = _lib.DEFINES["T2P_MAX_CHUNK_OBJECTS"]   # the batch is one cell
 
 
 class PointConv(nn.Module):

@@ -8,9 +8,9 @@ per-lane lists in registers, above it selects exactly from a float64 score tile 
 import numpy as np
 import torch
 
-from . import ops
+from . import _lib, ops
 
-MAX_TOP_K = 1024   # include/t2p.h: the largest k t2p_sim_topk accepts
+MAX_TOP_K = _lib.DEFINES["T2P_SIM_TOPK_MAX_K"]   # the largest k t2p_sim_topk accepts
 
 
 def check_top_k(top_k) -> int:

@@ -112,8 +112,11 @@ typedef struct t2p_cell_weights {
     const void* ga_w2_x3;
     /* The SA layer-2 images (sa_w2_x3) use the scaled single-accumulator form instead: w' = s w with s = sa_w2_scale[l]
      * a power of two (so that |w'| uses fp16's range), hi = fp16(w'), lo = fp16(w' - hi) (no 2048 factor: MFMA honours
-     * fp16 denormals), the three products hi.hi + hi.lo + lo.hi share ONE fp32 accumulator that starts at
-     * sa_b2_x3[l] = s b2; the kernel divides by s when it drains an object (packing.py::pack_f16x3_scaled). */
+     * fp16 denormals), the three products hi.hi + hi.lo + lo.hi share ONE fp32 accumulator.  The kernels of the 256-point
+     * level shapes (k_sa_points, k_sa_rows, k_sa3) start it at 0, take the maximum over a centroid's rows and add
+     * sa_b2_x3[l] = s b2 once, at the drain: relu(max + s b2) / s; k_sa_stream (every other size) starts it at s b2 and
+     * drains relu(max) / s.  Both divide by s (a power of two: exact) when they drain an object
+     * (packing.py::pack_f16x3_scaled; tests/trunk_ref.py derives one bound for both). */
     const float* sa_b2_x3[3];
     float sa_w2_scale[3];
     /* Scaled split images of the dense layers behind the trunk, for the LDS-tiled f16x3 GEMM

@@ -14,6 +14,8 @@
  * void, char, double, uint8_t, uint16_t, uint64_t and to the structs; members `T name`, `T name[n]`, `T a, b` and `T *a, *b`; no
  * function pointers, bit-fields, nested structs or array parameters.  Anything else fails the import, naming the declaration.
  * Change a signature or a struct: bump T2P_ABI_VERSION and regenerate tests/golden/abi.json.
+ * Additions live in extension headers with a version and a record of their own: include/t2p_serve.h (the serving path's
+ * prior-restricted retrieval).
  *
  * Conventions
  *   - Every pointer is a DEVICE pointer (HBM) unless its name ends in _host.  Buffers are owned by the caller;

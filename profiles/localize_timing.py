@@ -6,10 +6,16 @@
   (c) pipeline.evaluate (--pairs N)       timings["coarse_s"] + timings["fine_s"] of the evaluation with the on-device input side, which
                                           encodes the 2,048 cells and 163,840 objects again; run in interleaved pairs with (b)
 
+  (d) localize with a prior (--prior_pairs N)  (b) beside the same call restricted to the cells within 60 m of each pose's own position
+                                          (t2p_sim_topk_prior: the mask is an epilogue of the same product loop), in interleaved pairs;
+                                          written to its own file
+
 hipEvent and wall-clock times after a warm-up pass, the median of --repeats (>= 5) passes, the per-kernel breakdown of one localize
 pass (t2p_profile_report), written as JSON.
 
-    python profiles/localize_timing.py [--repeats 7] [--pairs 3] [--out profiles/localize_timing.json]"""
+    python profiles/localize_timing.py [--repeats 7] [--pairs 3] [--out profiles/localize_timing.json]
+    python profiles/localize_timing.py --prior_pairs 15 [--prior_radius 60] [--prior_out profiles/localize_prior_timing.json]
+                                          # (d) alone: one build, no evaluation"""
 import argparse
 import json
 import os
@@ -91,11 +97,59 @@ def summary(xs):
     return dict(series=[round(x, 5) for x in xs], median=round(statistics.median(xs), 5), min=round(min(xs), 5), max=round(max(xs), 5))
 
 
+def kernels_ms(run):
+    """Per-kernel split of one pass of run() (t2p_profile_report), largest first."""
+    ops.profile_enable(True)
+    ops.profile_report()
+    run()
+    rep = ops.profile_report()
+    ops.profile_enable(False)
+    return {k: dict(launches=v[0], total_ms=round(v[1], 4)) for k, v in sorted(rep.items(), key=lambda kv: -kv[1][1])}
+
+
+def prior_pairs(loc, scenes, hints, n_pairs, radius, base):
+    """(d): interleaved (unrestricted, restricted) pairs of Localizer.localize; the prior of a query is its pose's own position."""
+    xy = np.array([np.asarray(p.pose_w, dtype=np.float64)[0:2] for p in scenes.all_poses])
+    plain = lambda: loc.localize(hints, top_k=TOP_K)
+    prior = lambda: loc.localize(hints, top_k=TOP_K, prior_xy=xy, prior_radius=radius)
+    free, held = timed(plain)[0], timed(prior)[0]                        # warm-up of both: the prior's tables, its kernels' code objects
+    walls = dict(plain=[], prior=[])
+    events = dict(plain=[], prior=[])
+    for i in range(n_pairs):
+        for name, fn in ((("plain", plain), ("prior", prior)) if i % 2 == 0 else (("prior", prior), ("plain", plain))):
+            _, w, e = timed(fn)
+            walls[name].append(w)
+            events[name].append(e)
+    diff = [b - a for a, b in zip(walls["plain"], walls["prior"])]
+    # what the restriction did to the answers: candidates that qualified, and how often the true cell is among them
+    truth = [p.cell_id for p in scenes.all_poses]
+    hit = lambda r: float(np.mean([t in ids for t, ids in zip(truth, r.cell_ids)]))
+    return dict(base, prior_radius_m=radius, pairs=n_pairs,
+                localize_wall_s=summary(walls["plain"]), localize_prior_wall_s=summary(walls["prior"]),
+                localize_event_s=summary(events["plain"]), localize_prior_event_s=summary(events["prior"]),
+                prior_minus_plain_wall_s=summary(diff), plain_spread_s=round(max(walls["plain"]) - min(walls["plain"]), 5),
+                prior_spread_s=round(max(walls["prior"]) - min(walls["prior"]), 5),
+                n_valid_mean=float(held.n_valid.mean()), n_valid_min=int(held.n_valid.min()),
+                true_cell_in_top_k=dict(plain=hit(free), prior=hit(held)),
+                localize_kernels_ms=kernels_ms(plain), localize_prior_kernels_ms=kernels_ms(prior))
+
+
+def write(out, path):
+    text = json.dumps(out, indent=1)
+    print(text)
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w") as f:
+        f.write(text + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--pairs", type=int, default=3, help="interleaved (evaluate, localize) pairs; 0 = skip the evaluation")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "localize_timing.json"))
+    ap.add_argument("--prior_pairs", type=int, default=0, help="(d) alone: interleaved (localize, localize with a prior) pairs")
+    ap.add_argument("--prior_radius", type=float, default=60.0, help="radius of (d)'s prior around each pose's own position, metres")
+    ap.add_argument("--prior_out", default=os.path.join(ROOT, "profiles", "localize_prior_timing.json"))
     a = ap.parse_args()
     repeats = max(5, a.repeats)
     dev = torch.device("cuda:0")
@@ -109,6 +163,9 @@ def main():
 
     build = lambda: LZ.CellDatabase.build(coarse, fine, scenes.all_cells, tf, PAD)
     db, _, _ = timed(build)                                             # warm-up: the allocator's first workspaces
+    if a.prior_pairs > 0:
+        write(prior_pairs(LZ.Localizer(coarse, fine, db), scenes, hints, max(5, a.prior_pairs), a.prior_radius, out), a.prior_out)
+        return
     walls, events = [], []
     for _ in range(repeats):
         db, w, e = timed(build)
@@ -127,12 +184,7 @@ def main():
     out["localize"] = dict(wall_s=summary(walls), event_s=summary(events), queries_per_s=round(N_POSES / statistics.median(walls), 1),
                            matched_mean=float(res.matched.mean()))
 
-    ops.profile_enable(True)
-    ops.profile_report()
-    run()
-    rep = ops.profile_report()
-    ops.profile_enable(False)
-    out["localize_kernels_ms"] = {k: dict(launches=v[0], total_ms=round(v[1], 4)) for k, v in sorted(rep.items(), key=lambda kv: -kv[1][1])}
+    out["localize_kernels_ms"] = kernels_ms(run)
 
     if a.pairs > 0:
         pairs = max(3, a.pairs)
@@ -149,11 +201,7 @@ def main():
         out["pairs"] = dict(evaluate_coarse_plus_fine_s=summary(ev_s), evaluate_parts=parts, localize_wall_s=summary(loc_s),
                             evaluate_spread_s=round(max(ev_s) - min(ev_s), 5),
                             ratio_of_medians=round(statistics.median(ev_s) / statistics.median(loc_s), 3))
-    text = json.dumps(out, indent=1)
-    print(text)
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        f.write(text + "\n")
+    write(out, a.out)
 
 
 if __name__ == "__main__":

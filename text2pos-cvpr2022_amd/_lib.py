@@ -1,4 +1,4 @@
-"""ctypes binding of libt2p_hip.so (C ABI: include/t2p.h).
+"""ctypes binding of libt2p_hip.so (C ABI: include/t2p.h and its extension include/t2p_serve.h).
 
 The product path has no CPU fallback: if the HIP library is missing or fails a call, this raises.
 torch is imported first so that the library binds to the HIP runtime (libamdhip64.so.7) torch already loaded --
@@ -13,6 +13,7 @@ import torch  # noqa: F401  (must precede CDLL: shares torch's libamdhip64)
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("T2P_LIB") or os.path.join(_HERE, "libt2p_hip.so")  # T2P_LIB: A/B builds of the same ABI
 HEADER = os.path.join(_HERE, "..", "include", "t2p.h")   # the one statement of every signature, struct and limit
+SERVE_HEADER = os.path.join(_HERE, "..", "include", "t2p_serve.h")   # the serving extension: its own version and record
 
 
 class T2PError(RuntimeError):
@@ -90,6 +91,12 @@ ABI_VERSION = DEFINES["T2P_ABI_VERSION"]
 CellWeights, CellConfig, CellTrace, MatchWeights, TextWeights = (
     STRUCTS["t2p_" + n] for n in ("cell_weights", "cell_config", "cell_trace", "match_weights", "text_weights"))
 
+with open(SERVE_HEADER) as _f:    # same dialect, same parser; t2p.h's structs are not repeated there
+    SERVE_DEFINES, _serve_structs, SERVE_SYMBOLS = parse_header(_f.read())
+if _serve_structs or set(SERVE_SYMBOLS) & set(SYMBOLS):
+    raise T2PError("include/t2p_serve.h: declares a struct or repeats a symbol of include/t2p.h")
+SERVE_ABI_VERSION = SERVE_DEFINES["T2P_SERVE_ABI_VERSION"]
+
 _lib = None
 
 
@@ -102,11 +109,13 @@ def lib() -> C.CDLL:
                 f"{LIB_PATH} is missing: build the HIP extension first "
                 "(python __graft_entry__.py build, or python text2pos-cvpr2022_amd/build.py)")
         handle = C.CDLL(LIB_PATH)
-        for name, (res, args) in SYMBOLS.items():
+        for name, (res, args) in list(SYMBOLS.items()) + list(SERVE_SYMBOLS.items()):
             fn = getattr(handle, name)  # AttributeError if the export is missing
             fn.restype, fn.argtypes = res, args
         if handle.t2p_abi_version() != ABI_VERSION:
             raise T2PError(f"libt2p_hip.so ABI {handle.t2p_abi_version()} != binding ABI {ABI_VERSION}")
+        if handle.t2p_serve_abi_version() != SERVE_ABI_VERSION:
+            raise T2PError(f"libt2p_hip.so serve ABI {handle.t2p_serve_abi_version()} != binding serve ABI {SERVE_ABI_VERSION}")
         _lib = handle
     return _lib
 

@@ -10,6 +10,7 @@
 #include <utility>
 
 #include "../../include/t2p.h"
+#include "../../include/t2p_serve.h"
 #include "t2p_common.h"
 
 namespace t2p {
@@ -115,6 +116,7 @@ using namespace t2p;
 extern "C" {
 
 int t2p_abi_version(void) { return T2P_ABI_VERSION; }
+int t2p_serve_abi_version(void) { return T2P_SERVE_ABI_VERSION; }
 
 void t2p_profile_enable(int on) {
     std::lock_guard<std::mutex> lock(g_prof_mu);
@@ -421,6 +423,18 @@ int t2p_sim_topk_grouped(const float* queries, const float* cells, const int32_t
                   "sim_topk_grouped: NULL argument");
     return launch_sim_topk_grouped(queries, cells, query_group, cell_group, nq, nc, dim, k, index_offset, out_idx, out_score,
                                    workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int t2p_sim_topk_prior(const float* queries, const float* cells, const double* query_xy, const double* query_radius,
+                       const double* cell_box, const int32_t* query_group, const int32_t* cell_group, int64_t nq, int64_t nc,
+                       int32_t dim, int32_t k, int64_t index_offset, int64_t* out_idx, double* out_score, void* workspace,
+                       size_t workspace_bytes, t2p_stream_t stream) {
+    T2P_CHECK_ARG(nq >= 0 && nc >= 0, "sim_topk_prior: negative size");
+    T2P_CHECK_ARG((queries != nullptr || nq == 0) && (cells != nullptr || nc == 0) &&
+                      ((out_idx != nullptr && out_score != nullptr) || nq == 0 || k < 1),
+                  "sim_topk_prior: NULL argument");
+    return launch_sim_topk_prior(queries, cells, query_xy, query_radius, cell_box, query_group, cell_group, nq, nc, dim, k,
+                                 index_offset, out_idx, out_score, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 int t2p_sa_balance(const uint16_t* n_rows, int32_t n, int32_t tile_rows, int32_t n_wg, int32_t* prefix, int32_t* bounds,

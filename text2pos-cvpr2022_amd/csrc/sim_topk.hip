@@ -33,6 +33,12 @@
 // t2p_sim_topk_grouped (the street oracle, evaluation/pipeline.py:93-108: `scores[cell_street != pose_street] = -inf` before the
 // argsort) is the same two paths with GROUPED product kernels: the epilogue selects -inf for a pair whose group ids differ.  Merge and
 // select already order -inf entries (after every finite score, lowest cell index first), so they are shared as they are.
+//
+// t2p_sim_topk_prior (include/t2p_serve.h: the serving path's prior) is a third family of the two product kernels, MASK_PRIOR: a pair is
+// allowed when the query's prior point lies within its radius of the cell's closed square (float64, from comparisons so that a
+// NaN anywhere masks the pair) and when the query's group is negative or equals the cell's.  Either half may be absent (a NULL
+// pointer set, uniform over the launch).  The template parameter that was `bool GROUPED` is the mask kind; every line of the
+// prior sits behind `if constexpr (MASK == MASK_PRIOR)`, so the other two families compile to what they were.
 #include "t2p_common.h"
 
 namespace t2p {
@@ -49,6 +55,51 @@ constexpr int QB = 128;      // queries per workgroup (4 waves x 2 tiles x 16)
 constexpr int CB = 32;       // cells staged per iteration
 typedef double f64x2 __attribute__((ext_vector_type(2)));
 typedef int i32x4 __attribute__((ext_vector_type(4)));
+constexpr int MASK_NONE = 0, MASK_GROUP = 1, MASK_PRIOR = 2;   // the families of the product kernels
+
+// What a MASK_PRIOR kernel reads besides the embeddings: xy [nq][2], radius [nq], box [nc][4] = x0 y0 x1 y1 (all three or none; box
+// 16-byte aligned).  The group arrays travel as in MASK_GROUP (both or none).
+struct PriorArgs {
+    const double* xy;
+    const double* radius;
+    const double* box;
+};
+
+// A query's side of the geometric test in registers: px, py and r * r (-1 for a negative or NaN radius: no distance passes).
+struct PriorQuery {
+    double px, py, r2;
+};
+__device__ __forceinline__ PriorQuery prior_query(const PriorArgs& pr, int64_t q, bool in_range) {
+    PriorQuery o = {0.0, 0.0, -1.0};
+    if (pr.box != nullptr && in_range) {
+        const double r = pr.radius[q];
+        o.px = pr.xy[2 * q];
+        o.py = pr.xy[2 * q + 1];
+        o.r2 = r >= 0.0 ? r * r : -1.0;
+    }
+    return o;
+}
+// max(lo - p, p - hi, 0) built from comparisons: a NaN in any of the three operands comes out as NaN (fmax would drop it)
+__device__ __forceinline__ double prior_gap(double lo, double hi, double p) {
+    const double a = lo - p, b = p - hi;
+    double m = a > b ? a : b;   // a NaN in b stays; one in a alone is put back below
+    m = a != a ? a : m;
+    return m < 0.0 ? 0.0 : m;
+}
+// distance^2 from the prior point to the closed box [x0, x1] x [y0, y1] <= r^2; false on any NaN.  Two products and one sum, not
+// contracted: the boundary pairs of integer-valued geometry are exact equalities.
+__device__ __forceinline__ bool prior_reaches(const PriorQuery& pq, const f64x2& lo, const f64x2& hi) {
+#pragma clang fp contract(off)
+    const double dx = prior_gap(lo[0], hi[0], pq.px), dy = prior_gap(lo[1], hi[1], pq.py);
+    const double xx = dx * dx, yy = dy * dy;
+    return (xx + yy) <= pq.r2;
+}
+// geo && grp of one pair; box: the cell's four doubles in LDS (read only with has_geo)
+__device__ __forceinline__ bool prior_allowed(bool has_geo, bool has_grp, const PriorQuery& pq, int qgrp, int cgrp, const double* box) {
+    bool ok = !has_grp || qgrp < 0 || cgrp == qgrp;
+    if (has_geo) ok = ok && prior_reaches(pq, *(const f64x2*)box, *(const f64x2*)(box + 2));
+    return ok;
+}
 
 struct Cand {
     double s;
@@ -72,10 +123,15 @@ __device__ __forceinline__ int tile_pos(int c) { return (c & ~15) | ((c & 3) << 
 // prefetched under the same cell < c_end guard (nothing is read past cell_group[c_end - 1]), stored to g_lds at tile_pos so
 // that a lane's four cells sit side by side - and epi receives them as cg[r] (ids of cells >= c_end are 0 and unused).
 // Without GROUPED cell_group / g_lds are not touched and cg is a constant the epilogues ignore.
-template <int DIM, bool GROUPED, class Epi>
+// MASK_PRIOR: GROUPED when cell_group is given (uniform), and the block's CB boxes travel the same way - one 16-byte half box in
+// a register pair of the first 2 CB threads, prefetched under the same guard (nothing is read past cell_box[c_end - 1]), stored to
+// b_lds as [cell of the block][x0 y0 x1 y1]; the epilogue reads its four cells' boxes from b_lds + 4 * (cell0 - cb + d_row).
+template <int DIM, int MASK, class Epi>
 __device__ __forceinline__ void sim_product_loop(const float* __restrict__ Q, const float* __restrict__ Cm, int64_t nq,
                                                  int64_t q0_wg, int64_t c_begin, int64_t c_end, float* c_lds,
-                                                 const int32_t* __restrict__ cell_group, int* g_lds, Epi&& epi) {
+                                                 const int32_t* __restrict__ cell_group, int* g_lds, Epi&& epi,
+                                                 const double* __restrict__ cell_box = nullptr, double* b_lds = nullptr) {
+    constexpr bool GROUPED = MASK == MASK_GROUP;
     constexpr int LDC = DIM + 4;
     constexpr int KQ = DIM / 4;   // k per lane group (lane>>4 owns k in [g*KQ, (g+1)*KQ))
     constexpr int F4 = CB * DIM / 4 / 256;
@@ -98,9 +154,15 @@ __device__ __forceinline__ void sim_product_loop(const float* __restrict__ Q, co
 
     f32x4 stage[F4];
     int gstage = 0;
+    f64x2 bstage = {0.0, 0.0};
     auto load_block = [&](int64_t cb) {
         if constexpr (GROUPED) {
             if (tid < CB) gstage = (cb + tid) < c_end ? cell_group[cb + tid] : 0;
+        }
+        if constexpr (MASK == MASK_PRIOR) {
+            if (cell_group != nullptr && tid < CB) gstage = (cb + tid) < c_end ? cell_group[cb + tid] : 0;
+            if (cell_box != nullptr && tid < 2 * CB)
+                bstage = (cb + (tid >> 1)) < c_end ? *(const f64x2*)(cell_box + (cb + (tid >> 1)) * 4 + (tid & 1) * 2) : f64x2{0.0, 0.0};
         }
 #pragma unroll
         for (int it = 0; it < F4; it++) {
@@ -113,6 +175,10 @@ __device__ __forceinline__ void sim_product_loop(const float* __restrict__ Q, co
     auto store_block = [&]() {
         if constexpr (GROUPED) {
             if (tid < CB) g_lds[tile_pos(tid)] = gstage;
+        }
+        if constexpr (MASK == MASK_PRIOR) {
+            if (cell_group != nullptr && tid < CB) g_lds[tile_pos(tid)] = gstage;
+            if (cell_box != nullptr && tid < 2 * CB) *(f64x2*)(b_lds + 2 * tid) = bstage;
         }
 #pragma unroll
         for (int it = 0; it < F4; it++) {
@@ -132,6 +198,16 @@ __device__ __forceinline__ void sim_product_loop(const float* __restrict__ Q, co
             f64x4 acc[2];
 #pragma unroll
             for (int t = 0; t < 2; t++) acc[t] = f64x4{0.0, 0.0, 0.0, 0.0};
+            if constexpr (MASK == MASK_PRIOR && DIM >= 256) {
+                // The compiler widens the loop-invariant queries once, ahead of the loop: 2 * DIM / 4 more registers, which beside
+                // the prior's no longer fit (the lists at 256, both kernels at 384) and would go to scratch.  An empty asm that
+                // "rewrites" each fp32 query per tile, in an accumulation register, keeps them in the AGPR half of the file and
+                // the widening (one read, one convert) at its use, in the shadow of the MFMA it feeds.
+#pragma unroll
+                for (int t = 0; t < 2; t++)
+#pragma unroll
+                    for (int j = 0; j < KQ; j++) asm volatile("" : "+a"(qreg[t][j]));
+            }
             const float* arow = c_lds + (ct * 16 + l15) * LDC + g4 * KQ;
 #pragma unroll
             for (int s4 = 0; s4 < KQ / 4; s4++) {
@@ -146,6 +222,9 @@ __device__ __forceinline__ void sim_product_loop(const float* __restrict__ Q, co
             }
             i32x4 cg = {0, 0, 0, 0};
             if constexpr (GROUPED) cg = *(const i32x4*)(g_lds + ct * 16 + g4 * 4);   // == tile_pos(ct * 16 + d_row(lane, r)), r = 0..3
+            if constexpr (MASK == MASK_PRIOR) {
+                if (cell_group != nullptr) cg = *(const i32x4*)(g_lds + ct * 16 + g4 * 4);
+            }
 #pragma unroll
             for (int t = 0; t < 2; t++) epi(t, cb + ct * 16, acc[t], cg);
         }
@@ -155,17 +234,24 @@ __device__ __forceinline__ void sim_product_loop(const float* __restrict__ Q, co
 
 // GROUPED: a pair whose groups differ enters the lists as (-inf, cell) - a select on the finished score, so the allowed pairs'
 // bits are those of the ungrouped kernel; the lists start at (-inf, 0x7fffffff), so masked cells fill what the group leaves.
-template <int DIM, bool GROUPED>
+// MASK_PRIOR: the same select, on geo && grp (prior_allowed).
+template <int DIM, int MASK>
 __global__ __launch_bounds__(256, 1) void k_sim_partial(const float* __restrict__ Q, const float* __restrict__ Cm,
                                                          const int32_t* __restrict__ query_group,
                                                          const int32_t* __restrict__ cell_group,
                                                          int64_t nq, int64_t nc, int cells_per_split,
-                                                         double* __restrict__ ps, int* __restrict__ pi, int n_split) {
+                                                         double* __restrict__ ps, int* __restrict__ pi, int n_split, PriorArgs prior) {
+    constexpr bool GROUPED = MASK == MASK_GROUP;
     __shared__ __attribute__((aligned(16))) float c_lds[CB * (DIM + 4)];
     int* g_lds = nullptr;
-    if constexpr (GROUPED) {
+    double* b_lds = nullptr;
+    if constexpr (MASK != MASK_NONE) {
         __shared__ __attribute__((aligned(16))) int g_buf[CB];
         g_lds = g_buf;
+    }
+    if constexpr (MASK == MASK_PRIOR) {
+        __shared__ __attribute__((aligned(16))) double b_buf[CB * 4];
+        b_lds = b_buf;
     }
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g4 = lane >> 4, l15 = lane & 15;
     const int64_t q0 = (int64_t)blockIdx.x * QB + wave * 32;
@@ -188,12 +274,25 @@ __global__ __launch_bounds__(256, 1) void k_sim_partial(const float* __restrict_
         }
     }
 
-    sim_product_loop<DIM, GROUPED>(Q, Cm, nq, (int64_t)blockIdx.x * QB, c_begin, c_end, c_lds, cell_group, g_lds,
+    PriorQuery pq[2] = {};
+    if constexpr (MASK == MASK_PRIOR) {
+#pragma unroll
+        for (int t = 0; t < 2; t++) {
+            const int64_t q = q0 + t * 16 + l15;
+            if (query_group != nullptr && q < nq) qgrp[t] = query_group[q];
+            pq[t] = prior_query(prior, q, q < nq);
+        }
+    }
+
+    sim_product_loop<DIM, MASK>(Q, Cm, nq, (int64_t)blockIdx.x * QB, c_begin, c_end, c_lds, cell_group, g_lds,
                                    [&](int t, int64_t cell0, const f64x4& acc, const i32x4& cg) {
 #pragma unroll
         for (int r = 0; r < 4; r++) {
             const int64_t cell = cell0 + d_row(lane, r);
-            const double s = (!GROUPED || cg[r] == qgrp[t]) ? acc[r] : -INFINITY;
+            double s = (!GROUPED || cg[r] == qgrp[t]) ? acc[r] : -INFINITY;
+            if constexpr (MASK == MASK_PRIOR)
+                s = prior_allowed(prior.box != nullptr, cell_group != nullptr, pq[t], qgrp[t], cg[r],
+                                  b_lds + 4 * (((int)(cell0 - c_begin) & (CB - 1)) + d_row(lane, r))) ? acc[r] : -INFINITY;
             const int ci = (int)cell;
             if (cell < c_end && better(s, ci, ls[t][KCAP - 1], li[t][KCAP - 1])) {
                 ls[t][KCAP - 1] = s;
@@ -210,7 +309,7 @@ __global__ __launch_bounds__(256, 1) void k_sim_partial(const float* __restrict_
                 }
             }
         }
-    });
+    }, prior.box, b_lds);
     // partial lists: [q][split][g4][KCAP]
 #pragma unroll
     for (int t = 0; t < 2; t++) {
@@ -266,17 +365,24 @@ __global__ __launch_bounds__(256) void k_topk_merge(const double* __restrict__ p
 
 // GROUPED: a pair whose groups differ is written as -inf (score_key(-inf) > 0: k_topk_select retrieves it after every
 // finite score, lowest index first).
-template <int DIM, bool GROUPED>
+// MASK_PRIOR: likewise, on geo && grp.
+template <int DIM, int MASK>
 __global__ __launch_bounds__(256, 1) void k_sim_scores(const float* __restrict__ Q, const float* __restrict__ Cm,
                                                         const int32_t* __restrict__ query_group,
                                                         const int32_t* __restrict__ cell_group,
                                                         int64_t nq, int64_t nc, int cells_per_split,
-                                                        double* __restrict__ S, int64_t ld_s) {
+                                                        double* __restrict__ S, int64_t ld_s, PriorArgs prior) {
+    constexpr bool GROUPED = MASK == MASK_GROUP;
     __shared__ __attribute__((aligned(16))) float c_lds[CB * (DIM + 4)];
     int* g_lds = nullptr;
-    if constexpr (GROUPED) {
+    double* b_lds = nullptr;
+    if constexpr (MASK != MASK_NONE) {
         __shared__ __attribute__((aligned(16))) int g_buf[CB];
         g_lds = g_buf;
+    }
+    if constexpr (MASK == MASK_PRIOR) {
+        __shared__ __attribute__((aligned(16))) double b_buf[CB * 4];
+        b_lds = b_buf;
     }
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g4 = lane >> 4, l15 = lane & 15;
     const int64_t q0 = (int64_t)blockIdx.x * QB + wave * 32;
@@ -290,7 +396,16 @@ __global__ __launch_bounds__(256, 1) void k_sim_scores(const float* __restrict__
             if (q < nq) qgrp[t] = query_group[q];
         }
     }
-    sim_product_loop<DIM, GROUPED>(Q, Cm, nq, (int64_t)blockIdx.x * QB, c_begin, c_end, c_lds, cell_group, g_lds,
+    PriorQuery pq[2] = {};
+    if constexpr (MASK == MASK_PRIOR) {
+#pragma unroll
+        for (int t = 0; t < 2; t++) {
+            const int64_t q = q0 + t * 16 + l15;
+            if (query_group != nullptr && q < nq) qgrp[t] = query_group[q];
+            pq[t] = prior_query(prior, q, q < nq);
+        }
+    }
+    sim_product_loop<DIM, MASK>(Q, Cm, nq, (int64_t)blockIdx.x * QB, c_begin, c_end, c_lds, cell_group, g_lds,
                                    [&](int t, int64_t cell0, const f64x4& acc, const i32x4& cg) {
         const int64_t q = q0 + t * 16 + l15;
         // whole 16-cell tiles: cell0 < c_end <= nc keeps cell0 + 15 < ld_s; the cells past nc in the last one are never read
@@ -298,11 +413,17 @@ __global__ __launch_bounds__(256, 1) void k_sim_scores(const float* __restrict__
             double s[4];
 #pragma unroll
             for (int r = 0; r < 4; r++) s[r] = (!GROUPED || cg[r] == qgrp[t]) ? acc[r] : -INFINITY;
+            if constexpr (MASK == MASK_PRIOR) {
+#pragma unroll
+                for (int r = 0; r < 4; r++)
+                    s[r] = prior_allowed(prior.box != nullptr, cell_group != nullptr, pq[t], qgrp[t], cg[r],
+                                         b_lds + 4 * (((int)(cell0 - c_begin) & (CB - 1)) + d_row(lane, r))) ? acc[r] : -INFINITY;
+            }
             double* dst = S + q * ld_s + cell0 + g4 * 4;   // == tile_pos(cell0 + d_row(lane, r)) for r = 0..3
             *(f64x2*)dst = f64x2{s[0], s[1]};
             *(f64x2*)(dst + 2) = f64x2{s[2], s[3]};
         }
-    });
+    }, prior.box, b_lds);
 }
 
 // Order-preserving key of a score: a > b as doubles <=> key(a) > key(b); -0.0 and +0.0 share a key; every NaN maps to 0,
@@ -531,18 +652,23 @@ int64_t score_chunk(int64_t nq, int64_t nc) {
     return nq < cap ? nq : cap;
 }
 
-// qg == nullptr: the ungrouped kernels (the instantiations t2p_sim_topk has always run)
+// pr != nullptr: the prior kernels (qg / cg and pr's geometry are each given or absent); else qg == nullptr: the ungrouped kernels
+// (the instantiations t2p_sim_topk has always run)
 template <int DIM>
-void launch_scores(dim3 grid, hipStream_t st, const float* Q, const float* Cm, const int32_t* qg, const int32_t* cg, int64_t nq,
-                   int64_t nc, int cps, double* S, int64_t ld_s) {
-    if (qg) hipLaunchKernelGGL((k_sim_scores<DIM, true>), grid, dim3(256), 0, st, Q, Cm, qg, cg, nq, nc, cps, S, ld_s);
-    else hipLaunchKernelGGL((k_sim_scores<DIM, false>), grid, dim3(256), 0, st, Q, Cm, qg, cg, nq, nc, cps, S, ld_s);
+void launch_scores(dim3 grid, hipStream_t st, const float* Q, const float* Cm, const int32_t* qg, const int32_t* cg,
+                   const PriorArgs* pr, int64_t nq, int64_t nc, int cps, double* S, int64_t ld_s) {
+    const PriorArgs none = {nullptr, nullptr, nullptr};
+    if (pr) hipLaunchKernelGGL((k_sim_scores<DIM, MASK_PRIOR>), grid, dim3(256), 0, st, Q, Cm, qg, cg, nq, nc, cps, S, ld_s, *pr);
+    else if (qg) hipLaunchKernelGGL((k_sim_scores<DIM, MASK_GROUP>), grid, dim3(256), 0, st, Q, Cm, qg, cg, nq, nc, cps, S, ld_s, none);
+    else hipLaunchKernelGGL((k_sim_scores<DIM, MASK_NONE>), grid, dim3(256), 0, st, Q, Cm, qg, cg, nq, nc, cps, S, ld_s, none);
 }
 template <int DIM>
-void launch_partial(dim3 grid, hipStream_t st, const float* Q, const float* Cm, const int32_t* qg, const int32_t* cg, int64_t nq,
-                    int64_t nc, int cps, double* ps, int* pi, int sp) {
-    if (qg) hipLaunchKernelGGL((k_sim_partial<DIM, true>), grid, dim3(256), 0, st, Q, Cm, qg, cg, nq, nc, cps, ps, pi, sp);
-    else hipLaunchKernelGGL((k_sim_partial<DIM, false>), grid, dim3(256), 0, st, Q, Cm, qg, cg, nq, nc, cps, ps, pi, sp);
+void launch_partial(dim3 grid, hipStream_t st, const float* Q, const float* Cm, const int32_t* qg, const int32_t* cg,
+                    const PriorArgs* pr, int64_t nq, int64_t nc, int cps, double* ps, int* pi, int sp) {
+    const PriorArgs none = {nullptr, nullptr, nullptr};
+    if (pr) hipLaunchKernelGGL((k_sim_partial<DIM, MASK_PRIOR>), grid, dim3(256), 0, st, Q, Cm, qg, cg, nq, nc, cps, ps, pi, sp, *pr);
+    else if (qg) hipLaunchKernelGGL((k_sim_partial<DIM, MASK_GROUP>), grid, dim3(256), 0, st, Q, Cm, qg, cg, nq, nc, cps, ps, pi, sp, none);
+    else hipLaunchKernelGGL((k_sim_partial<DIM, MASK_NONE>), grid, dim3(256), 0, st, Q, Cm, qg, cg, nq, nc, cps, ps, pi, sp, none);
 }
 
 // The route (the rule at the top of the file): a function of (nq, nc) alone for every k <= KREG
@@ -552,9 +678,9 @@ bool use_score_tile(int64_t nq, int64_t nc, int k) {
     return large && score_chunk(1, nc) > 0;
 }
 
-// both entry points: qg / cg are nullptr for the unrestricted call
-int sim_topk_impl(const float* Q, const float* Cm, const int32_t* qg, const int32_t* cg, int64_t nq, int64_t nc, int dim, int k,
-                  int64_t c_index_offset, int64_t* out_idx, double* out_score, void* ws, size_t ws_bytes, hipStream_t st);
+// every entry point: qg / cg are nullptr for the unrestricted call, pr for all but the prior call
+int sim_topk_impl(const float* Q, const float* Cm, const int32_t* qg, const int32_t* cg, const PriorArgs* pr, int64_t nq, int64_t nc,
+                  int dim, int k, int64_t c_index_offset, int64_t* out_idx, double* out_score, void* ws, size_t ws_bytes, hipStream_t st);
 
 }  // namespace
 
@@ -566,7 +692,7 @@ size_t sim_topk_workspace_bytes(int64_t nq, int64_t nc, int k) {
 
 int launch_sim_topk(const float* Q, const float* Cm, int64_t nq, int64_t nc, int dim, int k, int64_t c_index_offset,
                     int64_t* out_idx, double* out_score, void* ws, size_t ws_bytes, hipStream_t st) {
-    return sim_topk_impl(Q, Cm, nullptr, nullptr, nq, nc, dim, k, c_index_offset, out_idx, out_score, ws, ws_bytes, st);
+    return sim_topk_impl(Q, Cm, nullptr, nullptr, nullptr, nq, nc, dim, k, c_index_offset, out_idx, out_score, ws, ws_bytes, st);
 }
 
 int launch_sim_topk_grouped(const float* Q, const float* Cm, const int32_t* query_group, const int32_t* cell_group, int64_t nq,
@@ -574,12 +700,25 @@ int launch_sim_topk_grouped(const float* Q, const float* Cm, const int32_t* quer
                             size_t ws_bytes, hipStream_t st) {
     T2P_CHECK_ARG((query_group != nullptr || nq == 0) && (cell_group != nullptr || nc == 0), "sim_topk_grouped: NULL group array");
     // (query_group is NULL only with nq == 0, which launches nothing; with nc == 0 no kernel reads cell_group)
-    return sim_topk_impl(Q, Cm, query_group, cell_group, nq, nc, dim, k, c_index_offset, out_idx, out_score, ws, ws_bytes, st);
+    return sim_topk_impl(Q, Cm, query_group, cell_group, nullptr, nq, nc, dim, k, c_index_offset, out_idx, out_score, ws, ws_bytes, st);
+}
+
+int launch_sim_topk_prior(const float* Q, const float* Cm, const double* query_xy, const double* query_radius, const double* cell_box,
+                          const int32_t* query_group, const int32_t* cell_group, int64_t nq, int64_t nc, int dim, int k,
+                          int64_t c_index_offset, int64_t* out_idx, double* out_score, void* ws, size_t ws_bytes, hipStream_t st) {
+    const int n_geo = (query_xy != nullptr) + (query_radius != nullptr) + (cell_box != nullptr);
+    const int n_grp = (query_group != nullptr) + (cell_group != nullptr);
+    T2P_CHECK_ARG(n_geo == 0 || n_geo == 3, "sim_topk_prior: query_xy, query_radius and cell_box go together (%d of 3 given)", n_geo);
+    T2P_CHECK_ARG(n_grp == 0 || n_grp == 2, "sim_topk_prior: query_group and cell_group go together (1 of 2 given)");
+    T2P_CHECK_ARG(n_geo + n_grp > 0, "sim_topk_prior: neither geometry nor groups given: call t2p_sim_topk");
+    T2P_CHECK_ARG((((uintptr_t)cell_box) & 15) == 0, "sim_topk_prior: cell_box must be 16-byte aligned");
+    const PriorArgs pr = {query_xy, query_radius, cell_box};
+    return sim_topk_impl(Q, Cm, query_group, cell_group, &pr, nq, nc, dim, k, c_index_offset, out_idx, out_score, ws, ws_bytes, st);
 }
 
 namespace {
-int sim_topk_impl(const float* Q, const float* Cm, const int32_t* qg, const int32_t* cg, int64_t nq, int64_t nc, int dim, int k,
-                  int64_t c_index_offset, int64_t* out_idx, double* out_score, void* ws, size_t ws_bytes, hipStream_t st) {
+int sim_topk_impl(const float* Q, const float* Cm, const int32_t* qg, const int32_t* cg, const PriorArgs* pr, int64_t nq, int64_t nc,
+                  int dim, int k, int64_t c_index_offset, int64_t* out_idx, double* out_score, void* ws, size_t ws_bytes, hipStream_t st) {
     T2P_CHECK_ARG(k >= 1 && k <= KMAX, "sim_topk: k=%d outside [1,%d]", k, KMAX);
     T2P_CHECK_ARG(dim == 256 || dim == 128 || dim == 384, "sim_topk: dim=%d not instantiated (128, 256, 384)", dim);
     T2P_CHECK_ARG(nc < 0x7fffffff, "sim_topk: nc too large");
@@ -606,9 +745,12 @@ int sim_topk_impl(const float* Q, const float* Cm, const int32_t* qg, const int3
                 const dim3 grid((unsigned)((n + QB - 1) / QB), (unsigned)sp);
                 ProfScope ps_("sim_scores", st);
                 const int32_t* qga = qg ? qg + qa : nullptr;
-                if (dim == 256) launch_scores<256>(grid, st, Q + qa * dim, Cm, qga, cg, n, nc, cps, S, ld_s);
-                else if (dim == 384) launch_scores<384>(grid, st, Q + qa * dim, Cm, qga, cg, n, nc, cps, S, ld_s);
-                else launch_scores<128>(grid, st, Q + qa * dim, Cm, qga, cg, n, nc, cps, S, ld_s);
+                PriorArgs pra = {nullptr, nullptr, nullptr};   // the chunk's queries: the per-query arrays move with qa
+                if (pr && pr->box) pra = PriorArgs{pr->xy + 2 * qa, pr->radius + qa, pr->box};
+                const PriorArgs* prp = pr ? &pra : nullptr;
+                if (dim == 256) launch_scores<256>(grid, st, Q + qa * dim, Cm, qga, cg, prp, n, nc, cps, S, ld_s);
+                else if (dim == 384) launch_scores<384>(grid, st, Q + qa * dim, Cm, qga, cg, prp, n, nc, cps, S, ld_s);
+                else launch_scores<128>(grid, st, Q + qa * dim, Cm, qga, cg, prp, n, nc, cps, S, ld_s);
             }
             T2P_CHECK_LAUNCH("sim_scores");
             ProfScope ps2_("topk_select", st);
@@ -627,9 +769,9 @@ int sim_topk_impl(const float* Q, const float* Cm, const int32_t* qg, const int3
     dim3 grid((unsigned)((nq + QB - 1) / QB), (unsigned)sp);
     {
     ProfScope ps_("sim_partial", st);
-    if (dim == 256) launch_partial<256>(grid, st, Q, Cm, qg, cg, nq, nc, cps, ps, pi, sp);
-    else if (dim == 384) launch_partial<384>(grid, st, Q, Cm, qg, cg, nq, nc, cps, ps, pi, sp);
-    else launch_partial<128>(grid, st, Q, Cm, qg, cg, nq, nc, cps, ps, pi, sp);
+    if (dim == 256) launch_partial<256>(grid, st, Q, Cm, qg, cg, pr, nq, nc, cps, ps, pi, sp);
+    else if (dim == 384) launch_partial<384>(grid, st, Q, Cm, qg, cg, pr, nq, nc, cps, ps, pi, sp);
+    else launch_partial<128>(grid, st, Q, Cm, qg, cg, pr, nq, nc, cps, ps, pi, sp);
     }
     T2P_CHECK_LAUNCH("sim_partial");
     ProfScope ps2_("topk_merge", st);

@@ -475,5 +475,10 @@ int launch_sim_topk(const float* Q, const float* C, int64_t nq, int64_t nc, int 
 int launch_sim_topk_grouped(const float* Q, const float* C, const int32_t* query_group, const int32_t* cell_group, int64_t nq,
                             int64_t nc, int dim, int k, int64_t c_index_offset, int64_t* out_idx, double* out_score, void* ws,
                             size_t ws_bytes, hipStream_t st);
+// include/t2p_serve.h: pairs outside the query's prior (distance to the cell's box, group) score -inf; the geometry pointers are
+// all given or all NULL, the group pointers likewise, not both sets NULL; same workspace as launch_sim_topk
+int launch_sim_topk_prior(const float* Q, const float* C, const double* query_xy, const double* query_radius, const double* cell_box,
+                          const int32_t* query_group, const int32_t* cell_group, int64_t nq, int64_t nc, int dim, int k,
+                          int64_t c_index_offset, int64_t* out_idx, double* out_score, void* ws, size_t ws_bytes, hipStream_t st);
 
 }  // namespace t2p

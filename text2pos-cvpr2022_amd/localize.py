@@ -4,6 +4,7 @@
         --path_coarse ./checkpoints/coarse.pth --path_fine ./checkpoints/fine.pth --out db.pt
     python -m text2pos_amd.localize query --db db.pt --path_coarse ./checkpoints/coarse.pth --path_fine ./checkpoints/fine.pth \\
         --hints "The pose is north of a gray road." "The pose is east of a green tree."
+    python -m text2pos_amd.localize query ... --hints "..." --prior 1042.5 3310.0 --radius 60 --scene 2013_05_28_drive_0010_sync
 
 The reference has no such path: the only code that chains text encoding, top-k, the fine matcher and the pose estimate is its
 evaluation (evaluation/pipeline.py:60-137, :172-279), which needs ground-truth poses and the raw scene, and re-encodes every
@@ -17,6 +18,10 @@ are fixed, so here they are encoded ONCE:
                  t2p_match_indexed (the matcher on the database's tokens, addressed by row) -> t2p_localize_poses (get_pos_in_cell,
                  models/superglue_matcher.py:139-161, the world coordinates and the most confident candidate, on the device).
                  No raw points, no PointNet++, one device-to-host copy per call.
+                 With a prior (a position and a radius in world metres, a scene name, or both) the ranking itself is restricted
+                 (t2p_sim_topk_prior, include/t2p_serve.h): a cell qualifies when the prior point lies within the radius of the
+                 cell's square and the cell belongs to the named scene.  Applied after an unrestricted top-k the prior would
+                 return nothing whenever the k best cells of the whole database lie elsewhere.
 
 The deliberate difference from the evaluation: a database cell has ONE T.FixedPoints draw, `transform.keys(row, slot)` of its
 database row, where run_fine draws once per (query, candidate) sample as the reference's dataloader does.
@@ -104,6 +109,19 @@ class CellDatabase:
     def device(self):
         return self.coarse.device
 
+    # ---- the tables a prior is checked against ----------------------------------------------------------------------------------
+    def cell_boxes(self) -> torch.Tensor:
+        """float64 [Nc, 4] on the database's device: x0, y0, x0 + cell_size, y0 + cell_size (one rounding each), the closed square
+        a prior position is measured against."""
+        return torch.cat([self.bbox_xy, self.bbox_xy + self.cell_size[:, None]], dim=1).contiguous()
+
+    def scene_index(self):
+        """(sorted unique scene names, int32 [Nc] on the database's device: every cell's index into them)."""
+        names = sorted(set(self.scene_names))
+        at = {n: i for i, n in enumerate(names)}
+        idx = torch.tensor([at[n] for n in self.scene_names], dtype=torch.int32)
+        return names, idx.to(self.device)
+
     # ---- building -----------------------------------------------------------------------------------------------------------
     @staticmethod
     def _encode(model_coarse, model_fine, cells, transform, pad_size: int, cells_per_call: int, cell_offset: int):
@@ -186,11 +204,25 @@ class Localization(SimpleNamespace):
     (Q lists of K ids), scores float64 [Q, K], pos_in_cell_mean / pos_in_cell float64 [Q, K, 2] (cell units: the mean of the matched
     objects' centres / of centre + offset; (0.5, 0.5) without matches), world_xy_mean / world_xy [Q, K, 2] (bbox + pos * cell_size),
     matched int32 [Q, K] (matched objects per candidate), best int32 [Q] (the candidate with the most, first on ties) and
-    best_world_xy float64 [Q, 2] = world_xy[q, best[q]]."""
+    best_world_xy float64 [Q, 2] = world_xy[q, best[q]]; n_valid int32 [Q] and restricted (bool).
+    A call with a prior (restricted) may find fewer than K cells that qualify: n_valid[q] candidates are valid, always the first
+    ones; the columns behind them read cell_rows -1, cell_ids None, scores -inf, NaN positions and matched 0; best is taken over
+    the valid columns only and is -1, with a NaN best_world_xy, where n_valid is 0.  Without a prior n_valid is K."""
 
     def to_json(self, q: int) -> dict:
-        return {k: (getattr(self, k)[q].tolist() if isinstance(getattr(self, k), np.ndarray) else list(getattr(self, k)[q]))
-                for k in _RESULT_FIELDS}
+        """One query as plain values.  Unrestricted: the fields of _RESULT_FIELDS.  Restricted: n_valid besides, every per-candidate
+        list cut to its valid prefix, best and best_world_xy null when nothing qualified - no NaN or Infinity in the line."""
+        out = {k: (getattr(self, k)[q].tolist() if isinstance(getattr(self, k), np.ndarray) else list(getattr(self, k)[q]))
+               for k in _RESULT_FIELDS}
+        if not getattr(self, "restricted", False):
+            return out
+        n = int(self.n_valid[q])
+        for k in _RESULT_FIELDS[:-2]:
+            out[k] = out[k][:n]
+        if n == 0:
+            out["best"] = out["best_world_xy"] = None
+        out["n_valid"] = n
+        return out
 
 
 def check_hints(hints) -> List[List[str]]:
@@ -205,6 +237,81 @@ def check_hints(hints) -> List[List[str]]:
             raise ValueError(f"localize: query {q} has {len(h)} hints; a query needs 1 to {MAX_HINTS} (the matcher's token limit)")
         out.append(list(h))
     return out
+
+
+def check_prior(n_queries: int, prior_xy, prior_radius, scenes, known_scenes: Sequence[str]):
+    """The prior of Localizer.localize, checked on the host before anything is launched -> (xy float64 [Q, 2], radius float64 [Q],
+    group int32 [Q]) with each half None where it was not given; (None, None, None) without a prior.
+    prior_xy: one (x, y) or [Q, 2], finite; prior_radius: one number or [Q], >= 0, inf = no geometric restriction; the two go
+    together.  scenes: None, one name, or Q entries each a name or None (None = any scene, group -1); names index known_scenes."""
+    nq = int(n_queries)
+    if (prior_xy is None) != (prior_radius is None):
+        raise ValueError("localize: prior_xy and prior_radius go together (got only "
+                         f"{'prior_xy' if prior_radius is None else 'prior_radius'})")
+    xy = rad = grp = None
+    if prior_xy is not None:
+        try:
+            xy, rad = np.asarray(prior_xy, dtype=np.float64), np.asarray(prior_radius, dtype=np.float64)
+        except (TypeError, ValueError) as e:
+            raise ValueError(f"localize: prior_xy and prior_radius must be numbers ({e})") from None
+        if xy.shape == (2,):
+            xy = np.broadcast_to(xy, (nq, 2))
+        if rad.shape == ():
+            rad = np.broadcast_to(rad, (nq,))
+        if xy.shape != (nq, 2) or rad.shape != (nq,):
+            raise ValueError(f"localize: prior_xy has shape {tuple(np.shape(prior_xy))} and prior_radius {tuple(np.shape(prior_radius))} for "
+                             f"{nq} queries: give one (x, y) or [{nq}, 2], and one radius or [{nq}]")
+        xy, rad = np.ascontiguousarray(xy), np.ascontiguousarray(rad)
+        bad = np.flatnonzero(~np.isfinite(xy).all(axis=1))
+        if len(bad):
+            raise ValueError(f"localize: prior_xy of query {bad[0]} is {xy[bad[0]].tolist()}: a prior position must be finite")
+        bad = np.flatnonzero(~(rad >= 0))
+        if len(bad):
+            raise ValueError(f"localize: prior_radius of query {bad[0]} is {float(rad[bad[0]])}: a radius is >= 0 (inf = no restriction)")
+    if scenes is not None:
+        names = [scenes] * nq if isinstance(scenes, str) else list(scenes) if isinstance(scenes, (list, tuple)) else None
+        if names is None or len(names) != nq or not all(n is None or isinstance(n, str) for n in names):
+            raise ValueError(f"localize: scenes must be one name or {nq} entries, each a name or None (any scene)")
+        at = {n: i for i, n in enumerate(known_scenes)}
+        for n in names:
+            if n is not None and n not in at:
+                raise ValueError(f"localize: unknown scene {n!r}; the database holds {list(known_scenes)}")
+        grp = np.array([-1 if n is None else at[n] for n in names], dtype=np.int32).reshape(nq)
+    return xy, rad, grp
+
+
+def unpack_result(res: np.ndarray, k: int, cell_ids: Sequence[str], restricted: bool, what: str = "Localizer.localize") -> Localization:
+    """The packed float64 [Q, 11 K + 1] rows of Localizer._run_chunk (in the caller's order, on the host) -> Localization.
+    restricted: candidate j of a query is valid iff its score is above -inf (the masked pairs of t2p_sim_topk_prior are exactly
+    -inf and come last); the invalid columns, whose rows are real cells the matcher ran on, are overwritten as Localization
+    states, and best is recomputed over the valid columns (most matched objects, the first on ties, -1 without any)."""
+    nq = res.shape[0]
+    cut = lambda i, n=1: res[:, i * k: (i + n) * k]
+    matched = cut(10).astype(np.int32)
+    ops.localize_check(matched, what)
+    rows = cut(0).astype(np.int64)
+    best = res[:, 11 * k].astype(np.int32)
+    scores = cut(1).copy()
+    pos = [cut(i, 2).reshape(nq, k, 2).copy() for i in (2, 4, 6, 8)]
+    n_valid = np.full(nq, k, dtype=np.int32)
+    if restricted:
+        valid = scores > -np.inf
+        n_valid = valid.sum(axis=1).astype(np.int32)
+        rows[~valid] = -1
+        scores[~valid] = -np.inf
+        matched[~valid] = 0
+        for p in pos:
+            p[~valid] = np.nan
+        ids = [[cell_ids[j] if j >= 0 else None for j in r] for r in rows.tolist()]
+        best = np.where(n_valid > 0, np.argmax(np.where(valid, matched, -1), axis=1), -1).astype(np.int32) if nq else best
+    else:
+        ids = [[cell_ids[j] for j in r] for r in rows]
+    world = pos[3]
+    best_xy = world[np.arange(nq), best] if nq else np.zeros((0, 2))
+    if restricted and nq:
+        best_xy[best < 0] = np.nan           # (a copy: fancy indexing)
+    return Localization(cell_rows=rows, cell_ids=ids, scores=scores, pos_in_cell_mean=pos[0], pos_in_cell=pos[1], world_xy_mean=pos[2],
+                        world_xy=world, matched=matched, best=best, best_world_xy=best_xy, n_valid=n_valid, restricted=bool(restricted))
 
 
 def group_by_hint_count(hints: List[List[str]]) -> Dict[int, List[int]]:
@@ -223,6 +330,13 @@ class Localizer:
                                           "call .eval()")
         check_models(database.meta, model_coarse, model_fine, "Localizer")
         self.model_coarse, self.model_fine, self.database = model_coarse, model_fine, database
+        self._tables = None      # (len(database), cell boxes, scene names, scene index): what a prior is checked against
+
+    def prior_tables(self):
+        """(cell_boxes, scene names, scene index) of the database, computed once and again after the database grew (extend)."""
+        if self._tables is None or self._tables[0] != len(self.database):
+            self._tables = (len(self.database), self.database.cell_boxes(), *self.database.scene_index())
+        return self._tables[1:]
 
     def _require_device(self):
         db = self.database
@@ -232,9 +346,13 @@ class Localizer:
         if not (torch.device(db.device) == torch.device(self.model_coarse.device) == torch.device(self.model_fine.device)):
             raise RuntimeError("Localizer.localize: database and models are on different devices")
 
-    def _run_chunk(self, hints: List[List[str]], top_k: int) -> torch.Tensor:
+    def _run_chunk(self, hints: List[List[str]], top_k: int, prior=None) -> torch.Tensor:
         """Queries with the same number of hints -> float64 [Q, 11 K + 1] on the device: cell rows | scores | pos_mean | pos_offset |
-        world_mean | world_offset (K x 2 each) | matched | best.  (Rows and counts are small integers: exact in float64.)"""
+        world_mean | world_offset (K x 2 each) | matched | best.  (Rows and counts are small integers: exact in float64.)
+        prior: None, or (xy [Q, 2], radius [Q], group [Q] or None) of these queries, already on the device (localize uploads the
+        whole call's prior once, before the first launch: an upload between the chunks would wait for the work in flight) - the
+        ranking then runs on t2p_sim_topk_prior; a masked candidate's row is still a real cell, so the matcher and the pose
+        estimate run on it as on any other."""
         db, mc, mf = self.database, self.model_coarse, self.model_fine
         nq, k = len(hints), int(top_k)
         for m in (mc, mf):
@@ -242,7 +360,13 @@ class Localizer:
                 raise NotImplementedError("Localizer.localize: a model was put into train() mode; call .eval()")
         with torch.no_grad():
             text = mc.encode_text([" ".join(h) for h in hints])                      # io.Scenes.texts (cells.py:82)
-            rows, scores = retrieve_topk(db.coarse, text, k)
+            if prior is None:
+                rows, scores = retrieve_topk(db.coarse, text, k)
+            else:
+                xy, rad, grp = prior
+                boxes, _, scene_idx = self.prior_tables()
+                groups = {} if grp is None else dict(cell_groups=scene_idx, query_groups=grp)
+                rows, scores = retrieve_topk(db.coarse, text, k, cell_boxes=boxes, query_xy=xy, query_radius=rad, validate=False, **groups)
             hint_enc = mf.encode_hints(hints).contiguous()                           # once per query, not per candidate
             obj_row = rows.reshape(-1).to(torch.int32)
             hint_row = torch.arange(nq, dtype=torch.int32, device=rows.device).repeat_interleave(k)
@@ -253,11 +377,16 @@ class Localizer:
         return torch.cat([flat(rows), flat(scores), flat(pose["pos_mean"]), flat(pose["pos_offset"]), flat(pose["world_mean"]),
                           flat(pose["world_offset"]), flat(pose["matched"]), flat(pose["best"])], dim=1)
 
-    def localize(self, hints: List[List[str]], top_k: int = 10, queries_per_call: Optional[int] = None) -> Localization:
+    def localize(self, hints: List[List[str]], top_k: int = 10, queries_per_call: Optional[int] = None, *, prior_xy=None,
+                 prior_radius=None, scenes=None) -> Localization:
         """hints: one list of hint sentences per query (1 to 63 each; the coarse text of a query is " ".join(hints)).  Queries are
         grouped by their number of hints, run in calls of queries_per_call (None = min(256, 4096 // top_k), evaluation.run_fine's
         device default) and returned in the caller's order.  One device-to-host copy at the end; a sample either kernel refused to
-        read through (a row outside the database, a NaN offset) raises IndexError naming query and candidate there."""
+        read through (a row outside the database, a NaN offset) raises IndexError naming query and candidate there.
+        prior_xy (one (x, y) or [Q, 2], world metres) with prior_radius (one number or [Q], >= 0; inf = no geometric restriction)
+        and / or scenes (one name, or Q entries each a name or None = any scene) restrict the ranking to the cells within the
+        radius of the position (distance to the cell's closed square: 0 keeps the cells that contain the point) and of the named
+        scene; see Localization for a query with fewer than top_k such cells.  Without them: the unrestricted call, bit for bit."""
         hints = check_hints(hints)
         k = check_top_k(top_k)
         if np.ndim(top_k) != 0:
@@ -266,33 +395,37 @@ class Localizer:
             raise ValueError(f"localize: top_k={k} exceeds the {len(self.database)} cells of the database")
         per_call = min(256, 4096 // k) if queries_per_call is None else int(queries_per_call)
         per_call = max(1, per_call)
-        self._require_device()
         nq = len(hints)
-        order, parts = [], []
-        for _, qs in group_by_hint_count(hints).items():
-            for a in range(0, len(qs), per_call):
-                chunk = qs[a: a + per_call]
+        restricted = not (prior_xy is None and prior_radius is None and scenes is None)
+        prior = check_prior(nq, prior_xy, prior_radius, scenes, sorted(set(self.database.scene_names))) if restricted else None
+        self._require_device()
+        chunks = [qs[a: a + per_call] for _, qs in group_by_hint_count(hints).items() for a in range(0, len(qs), per_call)]
+        order = [q for chunk in chunks for q in chunk]
+        if restricted:      # the prior in the order the chunks run, on the device before the first launch; a chunk takes a slice
+            xy, rad, grp = prior
+            if xy is None:  # a scene alone: no geometric restriction
+                xy, rad = np.zeros((nq, 2)), np.full(nq, np.inf)
+            sel, dev = np.asarray(order, dtype=np.int64), self.database.device
+            prior = tuple(None if t is None else torch.from_numpy(np.ascontiguousarray(t[sel])).to(dev) for t in (xy, rad, grp))
+        parts, at = [], 0
+        for chunk in chunks:
+            if restricted:
+                parts.append(self._run_chunk([hints[q] for q in chunk], k, tuple(None if t is None else t[at: at + len(chunk)] for t in prior)))
+            else:
                 parts.append(self._run_chunk([hints[q] for q in chunk], k))
-                order += chunk
+            at += len(chunk)
         width = 11 * k + 1
         packed = torch.cat(parts).cpu().numpy() if parts else np.zeros((0, width))       # the call's one device-to-host copy
         res = np.empty((nq, width), dtype=np.float64)
         res[np.asarray(order, dtype=np.int64)] = packed
-        cut = lambda i, n=1: res[:, i * k: (i + n) * k]
-        matched = cut(10).astype(np.int32)
-        ops.localize_check(matched, "Localizer.localize")
-        rows = cut(0).astype(np.int64)
-        best = res[:, 11 * k].astype(np.int32)
-        world = cut(8, 2).reshape(nq, k, 2).copy()
-        return Localization(cell_rows=rows, cell_ids=[[self.database.cell_ids[j] for j in r] for r in rows], scores=cut(1).copy(),
-                            pos_in_cell_mean=cut(2, 2).reshape(nq, k, 2).copy(), pos_in_cell=cut(4, 2).reshape(nq, k, 2).copy(),
-                            world_xy_mean=cut(6, 2).reshape(nq, k, 2).copy(), world_xy=world, matched=matched, best=best,
-                            best_world_xy=world[np.arange(nq), best] if nq else np.zeros((0, 2)))
+        return unpack_result(res, k, self.database.cell_ids, restricted)
 
-    def localize_poses(self, poses, top_k: int = 10, queries_per_call: Optional[int] = None) -> Localization:
+    def localize_poses(self, poses, top_k: int = 10, queries_per_call: Optional[int] = None, *, prior_xy=None, prior_radius=None,
+                       scenes=None) -> Localization:
         """localize() on the hint sentences of data.Pose objects (evaluation.create_hint_description)."""
         from .evaluation import create_hint_description
-        return self.localize([create_hint_description(p) for p in poses], top_k, queries_per_call)
+        return self.localize([create_hint_description(p) for p in poses], top_k, queries_per_call, prior_xy=prior_xy,
+                             prior_radius=prior_radius, scenes=scenes)
 
 
 # ---- command line ---------------------------------------------------------------------------------------------------------------
@@ -327,9 +460,9 @@ def read_queries(hints: Optional[List[str]], queries_file: Optional[str]) -> Lis
     return queries
 
 
-def main(argv: Optional[List[str]] = None):
-    from . import data as D, io as IO
-    from .pipeline import SCENE_NAMES_VAL, PerCellTransform
+def parse_args(argv: Optional[List[str]] = None):
+    """The command line of `build` and `query`, parsed and checked for flags that go together; nothing is read or loaded."""
+    from .pipeline import SCENE_NAMES_VAL
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     sub = ap.add_subparsers(dest="command", required=True)
     for name in ("build", "query"):
@@ -353,9 +486,22 @@ def main(argv: Optional[List[str]] = None):
             p.add_argument("--hints", nargs="+", default=None, help="the hint sentences of one query")
             p.add_argument("--queries_file", default=None, help="one query per line, its hints separated by '|'")
             p.add_argument("--top_k", type=int, default=10)
+            p.add_argument("--prior", type=float, nargs=2, default=None, metavar=("X", "Y"),
+                           help="prior position in world metres (with --radius); applies to every query of the invocation")
+            p.add_argument("--radius", type=float, default=None, help="radius of --prior in metres (0: the cells that contain it)")
+            p.add_argument("--scene", default=None, help="rank only the cells of this scene; applies to every query")
             p.add_argument("--vocab_base_path", default=None, help="dataset the models' vocabulary comes from (with --vocab_scenes)")
             p.add_argument("--vocab_scenes", nargs="*", default=SCENE_NAMES_VAL)
     a = ap.parse_args(argv)
+    if a.command == "query" and (a.prior is None) != (a.radius is None):
+        ap.error("--prior X Y and --radius R go together")
+    return a
+
+
+def main(argv: Optional[List[str]] = None):
+    from . import data as D, io as IO
+    from .pipeline import PerCellTransform
+    a = parse_args(argv)
     if a.command == "build":
         scenes = IO.load_scenes(a.base_path, a.scenes)
         coarse, fine, n_pts = _load_models(a, words=scenes.get_known_words(), classes=scenes.get_known_classes())
@@ -367,6 +513,7 @@ def main(argv: Optional[List[str]] = None):
     check_top_k(a.top_k)                                                          # before the checkpoints are read
     queries = check_hints(read_queries(a.hints, a.queries_file))
     db = CellDatabase.load(a.db)
+    check_prior(len(queries), a.prior, a.radius, a.scene, sorted(set(db.scene_names)))   # before the checkpoints are read
     if a.vocab_base_path:
         words = IO.load_scenes(a.vocab_base_path, a.vocab_scenes).get_known_words()
     elif "known_words" in db.meta:
@@ -374,7 +521,7 @@ def main(argv: Optional[List[str]] = None):
     else:
         raise ValueError("query: the database carries no vocabulary; give --vocab_base_path")
     coarse, fine, _ = _load_models(a, words=words, classes=list(D.KNOWN_CLASSES))
-    res = Localizer(coarse, fine, db.to(coarse.device)).localize(queries, a.top_k)
+    res = Localizer(coarse, fine, db.to(coarse.device)).localize(queries, a.top_k, prior_xy=a.prior, prior_radius=a.radius, scenes=a.scene)
     for q in range(len(queries)):
         print(json.dumps(res.to_json(q)))
     return res

@@ -61,13 +61,52 @@ def _as_device_groups(g, n: int, name: str, device):
     return t.to(device=device).contiguous()
 
 
+def _as_device_f64(x, shape, name: str, device):
+    """Float64 geometry (torch or numpy, anything array-like) of the given shape on the device; other shapes are refused."""
+    t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(x, dtype=np.float64)))
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError(f"retrieve_topk: {name} has shape {tuple(t.shape)}, expected {tuple(shape)}")
+    return t.to(device=device, dtype=torch.float64).contiguous()
+
+
+def _first_offender(bad: torch.Tensor):
+    """Row of the first True of a [n] or [n, m] mask (one host read), or None."""
+    rows = bad.reshape(bad.shape[0], -1).any(dim=1) if bad.numel() else bad.reshape(-1)
+    hit = torch.nonzero(rows)
+    return int(hit[0]) if hit.numel() else None
+
+
+def check_prior(query_xy: torch.Tensor, query_radius: torch.Tensor, cell_boxes: torch.Tensor):
+    """ValueError naming the first query whose prior is not a finite point with a radius >= 0 (inf allowed), or the first cell whose
+    box holds a NaN.  The kernel would mask such pairs silently; a caller who passes one has a bug upstream."""
+    q = _first_offender(~torch.isfinite(query_xy))
+    if q is not None:
+        raise ValueError(f"retrieve_topk: query_xy[{q}] = {query_xy[q].tolist()} is not finite")
+    q = _first_offender(~(query_radius >= 0))
+    if q is not None:
+        raise ValueError(f"retrieve_topk: query_radius[{q}] = {float(query_radius[q])} is NaN or negative (inf = no geometric restriction)")
+    c = _first_offender(torch.isnan(cell_boxes))
+    if c is not None:
+        raise ValueError(f"retrieve_topk: cell_boxes[{c}] = {cell_boxes[c].tolist()} holds a NaN")
+
+
 def retrieve_topk(cell_encodings, text_encodings, k: int, device=None, index_offset: int = 0, cell_groups=None,
-                  query_groups=None):
+                  query_groups=None, cell_boxes=None, query_xy=None, query_radius=None, validate: bool = True):
     """cell_encodings [Nc, D], text_encodings [Nq, D] (torch or numpy) -> (indices int64 [Nq, k], scores f64 [Nq, k])
     as torch tensors on the GPU.
     cell_groups [Nc] / query_groups [Nq] (integer arrays, torch or numpy, both or neither): the group-restricted ranking
     of the street oracle (evaluation/pipeline.py:93-108) - a pair whose groups differ scores -inf, so a query retrieves
-    its own group's cells first and, when those run out, masked cells at -inf by ascending index."""
+    its own group's cells first and, when those run out, masked cells at -inf by ascending index.
+    cell_boxes [Nc, 4] = x0 y0 x1 y1, query_xy [Nq, 2], query_radius [Nq] (float64, all three or none): the prior of the serving
+    path (t2p_sim_topk_prior) - a pair is allowed when the query's point lies within its radius of the cell's closed square
+    (radius 0: the cells that contain the point; inf: every cell).  With them the groups are optional companions, and a negative
+    query group means any group.  Non-finite points, NaN or negative radii and NaN boxes are refused here, by name (one host
+    read of three flags; validate=False skips it for a caller that has checked its values on the host, as Localizer does)."""
+    geo = (cell_boxes, query_xy, query_radius)
+    if any(g is None for g in geo) != all(g is None for g in geo):
+        names = ("cell_boxes", "query_xy", "query_radius")
+        raise ValueError("retrieve_topk: cell_boxes, query_xy and query_radius go together (missing: "
+                         f"{', '.join(n for n, g in zip(names, geo) if g is None)})")
     if (cell_groups is None) != (query_groups is None):
         raise ValueError("retrieve_topk: cell_groups and query_groups go together (got only "
                          f"{'cell_groups' if query_groups is None else 'query_groups'})")
@@ -81,9 +120,19 @@ def retrieve_topk(cell_encodings, text_encodings, k: int, device=None, index_off
         from .packing import kernel_embed_dim
         pad = kernel_embed_dim(d) - d
         c, q = torch.nn.functional.pad(c, (0, pad)).contiguous(), torch.nn.functional.pad(q, (0, pad)).contiguous()
+    cg = qg = None
     if cell_groups is not None:
         cg = _as_device_groups(cell_groups, c.shape[0], "cell_groups", device)
         qg = _as_device_groups(query_groups, q.shape[0], "query_groups", device)
+    if cell_boxes is not None:
+        box = _as_device_f64(cell_boxes, (c.shape[0], 4), "cell_boxes", device)
+        xy = _as_device_f64(query_xy, (q.shape[0], 2), "query_xy", device)
+        rad = _as_device_f64(query_radius, (q.shape[0],), "query_radius", device)
+        if validate:
+            check_prior(xy, rad, box)
+        return ops.sim_topk_prior(q, c, int(k), index_offset, query_xy=xy, query_radius=rad, cell_box=box, query_group=qg,
+                                  cell_group=cg)
+    if cg is not None:
         return ops.sim_topk_grouped(q, c, qg, cg, int(k), index_offset)
     return ops.sim_topk(q, c, int(k), index_offset)
 

@@ -1,75 +1,20 @@
-"""t2p_sim_topk_grouped (csrc/sim_topk.hip, GROUPED instantiations) against a NumPy restatement of the reference's street oracle
-(evaluation/pipeline.py:93-108): per query float64 `C @ q` on one BLAS thread, every cell of another group set to -inf, stable
+"""t2p_sim_topk_grouped (csrc/sim_topk.hip, MASK_GROUP instantiations) against tests/topk_ref.py's NumPy restatement of the
+reference's street oracle (evaluation/pipeline.py:93-108): per query float64 `C @ q` on one BLAS thread, every cell of another group set to -inf, stable
 descending argsort.  Indices must match exactly, finite scores within 1e-12 (the project's bar for float64 scores), masked entries
 are exactly -inf in ascending index.  Every case first asserts that the yardstick's finite gaps inside the top k + 1 are 0 or above
 1e-10, so a last-bit difference between the kernel's fma chain and BLAS cannot reorder anything but exact duplicates."""
-import functools
-
 import numpy as np
 import pytest
 import torch
 
+import topk_ref as R
+from topk_ref import dev as _dev, inputs as _inputs, strict_groups as _groups
+
 pytestmark = pytest.mark.gpu
 
 
-def _dev():
-    return torch.device("cuda:0")
-
-
-@functools.lru_cache(maxsize=None)
-def _inputs(nq, nc, dim=256):
-    """The generator of tests/test_gpu_topk_any.py::_inputs: unit rows in fp32, two planted copies of row 3."""
-    rng = np.random.default_rng(nq * 31 + nc)
-    c = rng.standard_normal((nc, dim)).astype(np.float32)
-    q = rng.standard_normal((nq, dim)).astype(np.float32)
-    c /= np.linalg.norm(c, axis=1, keepdims=True)
-    q /= np.linalg.norm(q, axis=1, keepdims=True)
-    if nc > 40:
-        c[7] = c[3]; c[39] = c[3]              # exact duplicates -> ties -> ascending index
-    c.setflags(write=False)
-    q.setflags(write=False)
-    return c, q
-
-
-@functools.lru_cache(maxsize=None)
-def _groups(nq, nc, n_groups):
-    """Cell groups uniform over the ids 0 .. G-3, then exactly 5 cells moved to id G-2; id G-1 has no cell.  Query 0 is given the
-    empty group, query 1 the 5-cell group, the others are uniform over 0 .. G-3."""
-    rng = np.random.default_rng(1000 * n_groups + nq + nc)
-    cg = rng.integers(0, n_groups - 2, nc).astype(np.int32)
-    cg[rng.choice(nc, 5, replace=False)] = n_groups - 2
-    qg = rng.integers(0, n_groups - 2, nq).astype(np.int32)
-    qg[0], qg[1] = n_groups - 1, n_groups - 2
-    assert (cg == n_groups - 2).sum() == 5 and not (cg == n_groups - 1).any()
-    cg.setflags(write=False)
-    qg.setflags(write=False)
-    return cg, qg
-
-
-@functools.lru_cache(maxsize=None)
-def _masked_scores(nq, nc, dim, n_groups):
-    """[nq, nc] float64: the yardstick's masked score rows for _inputs / _groups, computed once per shape."""
-    c, q = _inputs(nq, nc, dim)
-    cg, qg = _groups(nq, nc, n_groups)
-    s = _restate_scores(c, q, cg, qg)
-    s.setflags(write=False)
-    return s
-
-
 def _restate_scores(c, q, cg, qg):
-    from threadpoolctl import threadpool_limits
-    c64, q64 = np.asarray(c, dtype=np.float64), np.asarray(q, dtype=np.float64)
-    s = np.empty((q64.shape[0], c64.shape[0]), dtype=np.float64)
-    with threadpool_limits(limits=1, user_api="blas"):
-        for i in range(q64.shape[0]):
-            s[i] = c64 @ q64[i]
-    s[np.asarray(qg)[:, None] != np.asarray(cg)[None, :]] = -np.inf      # a select: whatever the product was, NaN included
-    return s
-
-
-def _restate_topk(s, k):
-    order = np.argsort(-1.0 * s, axis=1, kind="stable")[:, :k]
-    return order, np.take_along_axis(s, order, 1)
+    return R.masked(R.scores(c, q), R.same_group(qg, cg))
 
 
 def _topk(c, q, k, cg, qg, **kw):
@@ -77,33 +22,6 @@ def _topk(c, q, k, cg, qg, **kw):
     c, q = (torch.tensor(a, device=_dev()) if isinstance(a, np.ndarray) else a for a in (c, q))   # (the cached inputs are read-only)
     idx, score = t2p.retrieve_topk(c, q, k, cell_groups=np.array(cg), query_groups=np.array(qg), **kw)
     return idx.cpu().numpy(), score.cpu().numpy()
-
-
-def _check(s, k, idx, score, index_offset=0):
-    nq, nc = s.shape
-    kk = min(k, nc)
-    widx, wscore = _restate_topk(s, min(k + 1, nc))
-    fin = np.isfinite(wscore[:, :-1]) & np.isfinite(wscore[:, 1:])
-    with np.errstate(invalid="ignore"):                                 # (-inf) - (-inf) between two masked entries
-        gaps = (wscore[:, :-1] - wscore[:, 1:])[fin]
-    assert (gaps >= 0).all()
-    nz = gaps[gaps != 0]
-    assert nz.size == 0 or nz.min() > 1e-10, "the generator produced a near-tie inside the top k + 1"
-    widx, wscore = widx[:, :kk], wscore[:, :kk]
-    finite = np.isfinite(wscore)
-    err = np.abs(score[:, :kk][finite] - wscore[finite]).max() if finite.any() else 0.0
-    print(f"nq={nq} nc={nc} k={k}: min non-zero finite gap {nz.min() if nz.size else float('nan'):.2e}, max|score - yardstick| {err:.2e}, "
-          f"{int((~finite).sum())} masked entries")
-    assert idx.shape == (nq, k) and score.shape == (nq, k)
-    assert np.array_equal(idx[:, :kk], widx + index_offset)
-    assert err < 1e-12
-    assert np.array_equal(np.isneginf(score[:, :kk]), ~finite)         # masked entries: exactly -inf, nothing else is
-    for r in np.flatnonzero((~finite).any(axis=1)):
-        m = idx[r, :kk][~finite[r]]
-        assert (np.diff(m) > 0).all()                                   # ... in ascending index, after every finite score
-        assert finite[r, : kk - len(m)].all()
-    if nc < k:
-        assert (idx[:, nc:] == -1).all() and np.isneginf(score[:, nc:]).all()
 
 
 # ---- 1. against the restatement -----------------------------------------------------------------------------------------
@@ -116,7 +34,7 @@ def test_grouped_vs_restatement(nq, nc, dim, n_groups, k):
     c, q = _inputs(nq, nc, dim)
     cg, qg = _groups(nq, nc, n_groups)
     idx, score = _topk(c, q, k, cg, qg)
-    _check(_masked_scores(nq, nc, dim, n_groups), k, idx, score)
+    R.check(R.grouped_scores(nq, nc, dim, n_groups), k, idx, score)
     # query 0's group is empty: masked cells only, 0 .. k-1; query 1's group has 5 cells: they come first
     assert idx[0].tolist() == list(range(k)) and np.isneginf(score[0]).all()
     five = set(np.flatnonzero(cg == n_groups - 2).tolist())
@@ -158,7 +76,7 @@ def test_ties_across_the_mask(k):
     qg = np.ones(33, np.int32)
     idx, score = _topk(c, q, k, cg, qg)
     s = _restate_scores(c, q, cg, qg)
-    _check(s, k, idx, score)
+    R.check(s, k, idx, score)
     assert idx[0, :min(k, 30)].tolist() == list(range(100, 100 + min(k, 30)))
     assert (score[0, :min(k, 30)] == score[0, 0]).all()
     masked_copies = {3} | set(range(130, 160))
@@ -185,7 +103,7 @@ def test_nan_allowed_never_masked_as_minus_inf(k):
         assert idx[r, 9:].tolist() == list(range(10, 10 + k - 9)) and np.isneginf(score[r, 9:]).all()
     assert 12 in idx[0].tolist() and not (idx == 4).any()
     s = _restate_scores(c, q, cg, qg)
-    widx, wscore = _restate_topk(s, k)                                   # (NumPy sorts the allowed NaN last: beyond k)
+    widx, wscore = R.topk(s, k)                                   # (NumPy sorts the allowed NaN last: beyond k)
     assert np.array_equal(idx, widx) and np.abs(score[:, :9] - wscore[:, :9]).max() < 1e-12
 
 
@@ -208,7 +126,7 @@ def test_cell_groups_are_not_read_past_the_end(k):
     ei, es = t2p.retrieve_topk(c, q, k, cell_groups=view.clone(), query_groups=qg)
     assert int(vi.max()) < nc and int(vi.min()) >= 0
     assert torch.equal(vi, ei) and torch.equal(vs.view(torch.int64), es.view(torch.int64))
-    _check(_restate_scores(c.cpu().numpy(), q.cpu().numpy(), view.cpu().numpy(), qg.cpu().numpy()), k, vi.cpu().numpy(), vs.cpu().numpy())
+    R.check(_restate_scores(c.cpu().numpy(), q.cpu().numpy(), view.cpu().numpy(), qg.cpu().numpy()), k, vi.cpu().numpy(), vs.cpu().numpy())
 
 
 # ---- 6. which kernels run, what is refused ------------------------------------------------------------------------------
@@ -254,4 +172,4 @@ def test_embed_dim_300_is_padded():
     q /= np.linalg.norm(q, axis=1, keepdims=True)
     cg, qg = rng.integers(0, 3, 500).astype(np.int64), rng.integers(0, 3, 9).astype(np.int64)   # int64 input is converted
     idx, score = _topk(c, q, 20, cg, qg)
-    _check(_restate_scores(c, q, cg, qg), 20, idx, score)
+    R.check(_restate_scores(c, q, cg, qg), 20, idx, score)

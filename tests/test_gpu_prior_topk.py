@@ -1,24 +1,17 @@
 """t2p_sim_topk_prior (csrc/sim_topk.hip, MASK_PRIOR instantiations; include/t2p_serve.h) against the NumPy float64 yardstick
-tests/prior_ref.py (proved on hand cases by tests/test_prior_ref_host.py): indices equal, finite scores within 1e-12 (the project's
+tests/topk_ref.py (proved on hand cases by tests/test_topk_ref_host.py): indices equal, finite scores within 1e-12 (the project's
 bar for float64 scores), masked entries exactly -inf in ascending index behind every finite score.  Every case first asserts that
 the yardstick's finite gaps inside the top k + 1 are 0 or above 1e-10, so a last-bit difference between the kernel's fma chain and
 BLAS can reorder only exact duplicates.  Then: bit identity with the unrestricted and the grouped call where the prior allows
 everything, the route, NaN on both routes, reads past the end, embed_dim 300 and the wrappers' refusals."""
-import os
-import sys
-
 import numpy as np
 import pytest
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import prior_ref as P  # noqa: E402
+import topk_ref as P
+from topk_ref import LISTS, TILE, dev as _dev, profiled as _profiled
 
 pytestmark = pytest.mark.gpu
-
-
-def _dev():
-    return torch.device("cuda:0")
 
 
 def _up(a):
@@ -31,21 +24,6 @@ def _topk(c, q, k, xy, radius, box, cg=None, qg=None, **kw):
     groups = {} if cg is None else dict(cell_groups=np.array(cg), query_groups=np.array(qg))
     idx, score = t2p.retrieve_topk(c, q, k, cell_boxes=np.array(box), query_xy=np.array(xy), query_radius=np.array(radius), **groups, **kw)
     return idx.cpu().numpy(), score.cpu().numpy()
-
-
-def _profiled(fn):
-    from text2pos_amd import ops
-    torch.cuda.synchronize()
-    ops.profile_report()
-    ops.profile_enable(True)
-    try:
-        out = fn()
-    finally:
-        ops.profile_enable(False)
-    return out, ops.profile_report()
-
-
-LISTS, TILE = {"sim_partial", "topk_merge"}, {"sim_scores", "topk_select"}
 
 
 # ---- 1. against the yardstick -------------------------------------------------------------------------------------------

@@ -9,16 +9,12 @@ import pytest
 import torch
 
 import test_gpu_topk_any as TA
+from topk_ref import LISTS, TILE, dev as _dev, profiled as _profiled
 
 pytestmark = pytest.mark.gpu
 
 NQ, QBLOCK = 97, 8
 KS = (1, 10, 16)
-LISTS, TILE = {"sim_partial", "topk_merge"}, {"sim_scores", "topk_select"}
-
-
-def _dev():
-    return torch.device("cuda:0")
 
 
 def _ws(nq, nc, k):
@@ -61,18 +57,6 @@ def _inputs(nq, nc, dim):
     c.setflags(write=False)
     q.setflags(write=False)
     return c, q, torch.tensor(c, device=_dev()), torch.tensor(q, device=_dev())
-
-
-def _profiled(fn):
-    from text2pos_amd import ops
-    torch.cuda.synchronize()
-    ops.profile_report()
-    ops.profile_enable(True)
-    try:
-        out = fn()
-    finally:
-        ops.profile_enable(False)
-    return out, ops.profile_report()
 
 
 def _np(pair):

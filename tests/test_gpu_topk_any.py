@@ -8,28 +8,11 @@ import numpy as np
 import pytest
 import torch
 
+from topk_ref import dev as _dev, inputs as _inputs, profiled as _profiled
+
 pytestmark = pytest.mark.gpu
 
 KMAX = 1024
-
-
-def _dev():
-    return torch.device("cuda:0")
-
-
-@functools.lru_cache(maxsize=None)
-def _inputs(nq, nc, dim=256):
-    """Unit rows in fp32, generated as tests/test_gpu_parity.py::test_retrieval_vs_oracle does (two planted copies of row 3)."""
-    rng = np.random.default_rng(nq * 31 + nc)
-    c = rng.standard_normal((nc, dim)).astype(np.float32)
-    q = rng.standard_normal((nq, dim)).astype(np.float32)
-    c /= np.linalg.norm(c, axis=1, keepdims=True)
-    q /= np.linalg.norm(q, axis=1, keepdims=True)
-    if nc > 40:
-        c[7] = c[3]; c[39] = c[3]              # exact duplicates -> ties -> ascending index
-    c.setflags(write=False)
-    q.setflags(write=False)
-    return c, q
 
 
 @functools.lru_cache(maxsize=None)
@@ -185,16 +168,8 @@ def test_two_calls_give_identical_bytes():
 
 # ---- 6. k <= 16 untouched -----------------------------------------------------------------------------------------------
 def _kernel_names(dc, dq, k):
-    from text2pos_amd import ops
     import text2pos_amd as t2p
-    torch.cuda.synchronize()
-    ops.profile_report()
-    ops.profile_enable(True)
-    try:
-        t2p.retrieve_topk(dc, dq, k)
-    finally:
-        ops.profile_enable(False)
-    return ops.profile_report()
+    return _profiled(lambda: t2p.retrieve_topk(dc, dq, k))[1]
 
 
 def test_small_k_runs_the_register_list_kernels():

@@ -1,7 +1,7 @@
 """Host side of the prior-restricted retrieval and of Localizer.localize's prior (no GPU needed): the refusals of
 t2p_sim_topk_prior (nothing is launched: the pointers are never dereferenced), the argument checks of retrieve_topk and localize, the
 host post-processing of a restricted result on a hand-made packed array, and the command line.  The GPU side is
-tests/test_gpu_prior_topk.py and tests/test_gpu_localize_prior.py; the yardstick's own proof tests/test_prior_ref_host.py."""
+tests/test_gpu_prior_topk.py and tests/test_gpu_localize_prior.py; the yardstick's own proof tests/test_topk_ref_host.py."""
 import ctypes as C
 import json
 import re

@@ -1,13 +1,10 @@
-"""The yardstick of the prior-restricted retrieval (tests/prior_ref.py) on hand cases: no GPU, no package.  The GPU cases of
-tests/test_gpu_prior_topk.py compare the kernel with it, so its mask is proved here on pairs whose answer is known by hand."""
-import os
-import sys
-
+"""The yardstick of the restricted retrieval (tests/topk_ref.py) on hand cases: no GPU, no package.  The GPU cases of
+tests/test_gpu_prior_topk.py and tests/test_gpu_grouped_topk.py compare the kernels with it, so its masks are proved here on pairs
+whose answer is known by hand."""
 import numpy as np
 import pytest
 
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import prior_ref as P  # noqa: E402
+import topk_ref as P
 
 BOX = np.array([[10.0, 20.0, 40.0, 50.0]])          # one cell: [10, 40] x [20, 50]
 
@@ -55,6 +52,14 @@ def test_groups_and_their_combination_with_the_geometry():
     assert P.allowed(None, None, None, qg, cg).tolist() == [[True, True, True], [True, False, True], [True, True, True]]
     assert P.allowed(xy, r, box, qg, cg).tolist() == [[True, True, False], [True, False, False], [False, False, False]]
     assert P.allowed(xy, r, box).tolist() == [[True, True, False], [True, True, False], [False, False, False]]
+
+
+def test_the_grouped_mask_is_strict_where_the_prior_reads_a_negative_id_as_any_group():
+    qg, cg = np.array([-1, 4, -7], np.int32), np.array([4, -1, -7, 5], np.int32)
+    assert P.same_group(qg, cg).tolist() == [[False, True, False, False], [True, False, False, False], [False, False, True, False]]
+    assert P.allowed(None, None, None, qg, cg).tolist() == [[True] * 4, [True, False, False, False], [True] * 4]
+    cg7, qg7 = P.strict_groups(130, 1000, 7)
+    assert (qg7 >= 0).all() and np.array_equal(P.groups(130, 1000, 7)[0], cg7) and (P.groups(130, 1000, 7)[1][1::5] == qg7[1::5]).all()
 
 
 def test_masked_pairs_are_minus_inf_whatever_the_product_and_sort_last_in_index_order():

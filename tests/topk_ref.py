@@ -1,18 +1,21 @@
-"""The yardstick of the prior-restricted retrieval (t2p_sim_topk_prior, include/t2p_serve.h) in NumPy float64; no GPU, no package.
+"""The NumPy float64 yardstick of the restricted retrieval tests (t2p_sim_topk_grouped, include/t2p.h; t2p_sim_topk_prior,
+include/t2p_serve.h), their shared input generators and the helpers of the GPU cases; no GPU at import, no package.
 
     geo(q, c) = dx = max(x0[c] - px[q], px[q] - x1[c], 0), dy likewise: dx * dx + dy * dy <= r[q] * r[q]
-    grp(q, c) = query_group[q] < 0 or cell_group[c] == query_group[q]
-    s'(q, c)  = geo && grp ? C64[c] @ q64[q] : -inf,  then a stable descending argsort
+    grp(q, c) = query_group[q] < 0 or cell_group[c] == query_group[q]          (the prior call: a negative id is "any group")
+    same(q, c) = cell_group[c] == query_group[q]                               (the grouped call: strict, whatever the sign)
+    s'(q, c)  = allowed ? C64[c] @ q64[q] : -inf,  then a stable descending argsort
 
 np.maximum keeps NaN, and a comparison with NaN is False: a NaN in px, py, r or a box member masks the pair; so does r < 0.
-The embeddings are the generator of tests/test_gpu_topk_any.py / test_gpu_grouped_topk.py; the geometry is integer-valued, so every
-distance and every r * r is exact and the pairs on the boundary are exact equalities (tests/test_prior_ref_host.py proves the mask
-on hand cases and counts them).  The scores are computed per query on one BLAS thread, once per shape, and left unchanged."""
+The geometry is integer-valued, so every distance and every r * r is exact and the pairs on the boundary are exact equalities
+(tests/test_topk_ref_host.py proves the masks on hand cases and counts them).  The scores are computed per query on one BLAS thread,
+once per shape, and left unchanged."""
 import functools
 from math import isqrt
 
 import numpy as np
 
+LISTS, TILE = {"sim_partial", "topk_merge"}, {"sim_scores", "topk_select"}      # the kernels of the two routes (ops.profile_report)
 RADII = (0.0, 5.0, 25.0, 60.0, np.inf)
 # (nq, nc, dim, k): the shapes the GPU cases run
 SHAPES = [(130, 1000, 256, 100), (260, 1000, 256, 16), (257, 4099, 128, 100), (37, 2500, 384, 16), (17, 12000, 256, 1024),
@@ -36,6 +39,11 @@ def allowed(xy, radius, box, query_group=None, cell_group=None):
         ok = grp if ok is None else ok & grp
     assert ok is not None, "neither geometry nor groups"
     return ok
+
+
+def same_group(query_group, cell_group):
+    """bool [nq, nc]: the grouped call's mask - the ids are equal, negative ones included."""
+    return np.asarray(query_group)[:, None] == np.asarray(cell_group)[None, :]
 
 
 @functools.lru_cache(maxsize=None)
@@ -75,15 +83,26 @@ def geometry(nq, nc):
 
 
 @functools.lru_cache(maxsize=None)
-def groups(nq, nc, n_groups):
-    """tests/test_gpu_grouped_topk.py::_groups, then every fifth query's group set to -1 (any group)."""
+def strict_groups(nq, nc, n_groups):
+    """(cell groups, query groups) int32, read-only.  Cell groups uniform over the ids 0 .. G-3, then exactly 5 cells moved to id
+    G-2; id G-1 has no cell.  Query 0 is given the empty group, query 1 the 5-cell group, the others are uniform over 0 .. G-3."""
     rng = np.random.default_rng(1000 * n_groups + nq + nc)
     cg = rng.integers(0, n_groups - 2, nc).astype(np.int32)
     cg[rng.choice(nc, 5, replace=False)] = n_groups - 2
     qg = rng.integers(0, n_groups - 2, nq).astype(np.int32)
     qg[0], qg[1] = n_groups - 1, n_groups - 2
-    qg[::5] = -1
+    assert (cg == n_groups - 2).sum() == 5 and not (cg == n_groups - 1).any()
     cg.setflags(write=False)
+    qg.setflags(write=False)
+    return cg, qg
+
+
+@functools.lru_cache(maxsize=None)
+def groups(nq, nc, n_groups):
+    """strict_groups, then every fifth query's group set to -1 (any group)."""
+    cg, qg = strict_groups(nq, nc, n_groups)
+    qg = qg.copy()
+    qg[::5] = -1
     qg.setflags(write=False)
     return cg, qg
 
@@ -116,6 +135,14 @@ def masked_scores(nq, nc, dim, n_groups=0):
     return s
 
 
+@functools.lru_cache(maxsize=None)
+def grouped_scores(nq, nc, dim, n_groups):
+    """The grouped call's yardstick: the score rows of inputs, masked by same_group of strict_groups, once per shape (read-only)."""
+    s = masked(scores(*inputs(nq, nc, dim)), same_group(*strict_groups(nq, nc, n_groups)[::-1]))
+    s.setflags(write=False)
+    return s
+
+
 def topk(s, k):
     order = np.argsort(-1.0 * s, axis=1, kind="stable")[:, :k]
     return order, np.take_along_axis(s, order, 1)
@@ -133,8 +160,8 @@ def min_gap(s, k):
 
 
 def check(s, k, idx, score, index_offset=0, rows=None):
-    """tests/test_gpu_grouped_topk.py::_check: the yardstick's finite gaps inside the top k + 1 are 0 or above 1e-10; indices
-    equal; finite scores within 1e-12; masked entries exactly -inf, in ascending index, behind every finite score.
+    """The yardstick's finite gaps inside the top k + 1 are 0 or above 1e-10; indices equal; finite scores within 1e-12; masked
+    entries exactly -inf, in ascending index, behind every finite score; beyond nc cells -1 / -inf.
     rows: compare only these queries (idx / score hold all of them)."""
     if rows is not None:
         s, idx, score = s[rows], idx[rows], score[rows]
@@ -156,3 +183,23 @@ def check(s, k, idx, score, index_offset=0, rows=None):
         assert finite[r, : kk - len(m)].all()
     if nc < k:
         assert (idx[:, nc:] == -1).all() and np.isneginf(score[:, nc:]).all()
+
+
+# ---- helpers of the GPU cases (torch and the package are imported where they are used) ----------------------------------
+def dev():
+    import torch
+    return torch.device("cuda:0")
+
+
+def profiled(fn):
+    """(fn(), the kernels it launched: name -> (launches, ms))"""
+    import torch
+    from text2pos_amd import ops
+    torch.cuda.synchronize()
+    ops.profile_report()
+    ops.profile_enable(True)
+    try:
+        out = fn()
+    finally:
+        ops.profile_enable(False)
+    return out, ops.profile_report()

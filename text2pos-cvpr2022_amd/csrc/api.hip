@@ -402,14 +402,11 @@ int t2p_hardest_ranking(const float* scores, int32_t batch, float margin, float*
 
 size_t t2p_sim_topk_workspace_bytes(int64_t nq, int64_t nc, int32_t k) { return sim_topk_workspace_bytes(nq, nc, k); }
 
+// (the three calls' sizes and pointers are checked in sim_topk.hip, once, under each call's name)
+
 int t2p_sim_topk(const float* queries, const float* cells, int64_t nq, int64_t nc, int32_t dim, int32_t k,
                  int64_t index_offset, int64_t* out_idx, double* out_score, void* workspace, size_t workspace_bytes,
                  t2p_stream_t stream) {
-    T2P_CHECK_ARG(nq >= 0 && nc >= 0, "sim_topk: negative size");
-    // an empty side has no storage to point to (nq == 0 launches nothing; k < 1 is refused below, by its range)
-    T2P_CHECK_ARG((queries != nullptr || nq == 0) && (cells != nullptr || nc == 0) &&
-                      ((out_idx != nullptr && out_score != nullptr) || nq == 0 || k < 1),
-                  "sim_topk: NULL argument");
     return launch_sim_topk(queries, cells, nq, nc, dim, k, index_offset, out_idx, out_score, workspace, workspace_bytes,
                            (hipStream_t)stream);
 }
@@ -417,10 +414,6 @@ int t2p_sim_topk(const float* queries, const float* cells, int64_t nq, int64_t n
 int t2p_sim_topk_grouped(const float* queries, const float* cells, const int32_t* query_group, const int32_t* cell_group,
                          int64_t nq, int64_t nc, int32_t dim, int32_t k, int64_t index_offset, int64_t* out_idx,
                          double* out_score, void* workspace, size_t workspace_bytes, t2p_stream_t stream) {
-    T2P_CHECK_ARG(nq >= 0 && nc >= 0, "sim_topk_grouped: negative size");
-    T2P_CHECK_ARG((queries != nullptr || nq == 0) && (cells != nullptr || nc == 0) &&
-                      ((out_idx != nullptr && out_score != nullptr) || nq == 0 || k < 1),
-                  "sim_topk_grouped: NULL argument");
     return launch_sim_topk_grouped(queries, cells, query_group, cell_group, nq, nc, dim, k, index_offset, out_idx, out_score,
                                    workspace, workspace_bytes, (hipStream_t)stream);
 }
@@ -429,10 +422,6 @@ int t2p_sim_topk_prior(const float* queries, const float* cells, const double* q
                        const double* cell_box, const int32_t* query_group, const int32_t* cell_group, int64_t nq, int64_t nc,
                        int32_t dim, int32_t k, int64_t index_offset, int64_t* out_idx, double* out_score, void* workspace,
                        size_t workspace_bytes, t2p_stream_t stream) {
-    T2P_CHECK_ARG(nq >= 0 && nc >= 0, "sim_topk_prior: negative size");
-    T2P_CHECK_ARG((queries != nullptr || nq == 0) && (cells != nullptr || nc == 0) &&
-                      ((out_idx != nullptr && out_score != nullptr) || nq == 0 || k < 1),
-                  "sim_topk_prior: NULL argument");
     return launch_sim_topk_prior(queries, cells, query_xy, query_radius, cell_box, query_group, cell_group, nq, nc, dim, k,
                                  index_offset, out_idx, out_score, workspace, workspace_bytes, (hipStream_t)stream);
 }

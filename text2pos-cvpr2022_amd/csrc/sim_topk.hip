@@ -30,15 +30,20 @@
 // and a bitonic sort in LDS puts the k candidates into better() order.  Queries go through in chunks whose score tile
 // stays within 256 MiB (the Infinity Cache: the select passes re-read what the score kernel just wrote).
 //
-// t2p_sim_topk_grouped (the street oracle, evaluation/pipeline.py:93-108: `scores[cell_street != pose_street] = -inf` before the
-// argsort) is the same two paths with GROUPED product kernels: the epilogue selects -inf for a pair whose group ids differ.  Merge and
-// select already order -inf entries (after every finite score, lowest cell index first), so they are shared as they are.
-//
-// t2p_sim_topk_prior (include/t2p_serve.h: the serving path's prior) is a third family of the two product kernels, MASK_PRIOR: a pair is
-// allowed when the query's prior point lies within its radius of the cell's closed square (float64, from comparisons so that a
-// NaN anywhere masks the pair) and when the query's group is negative or equals the cell's.  Either half may be absent (a NULL
-// pointer set, uniform over the launch).  The template parameter that was `bool GROUPED` is the mask kind; every line of the
-// prior sits behind `if constexpr (MASK == MASK_PRIOR)`, so the other two families compile to what they were.
+// Restricted rankings.  The two product kernels (k_sim_partial, k_sim_scores) come in three compile-time families, MASK; a family's
+// epilogue selects -inf for a pair its mask does not allow - a select on the finished score, so an allowed pair has the bits of
+// the unrestricted call.  Merge and select order -inf entries after every finite score, lowest cell index first, and are shared.
+//     MASK_NONE   t2p_sim_topk: every pair is allowed; reads the embeddings only.
+//     MASK_GROUP  t2p_sim_topk_grouped (the street oracle, evaluation/pipeline.py:93-108: `scores[cell_street != pose_street] = -inf`
+//                 before the argsort): allowed when the group ids are equal, whatever their sign; reads query_group [nq], cell_group [nc].
+//     MASK_PRIOR  t2p_sim_topk_prior (include/t2p_serve.h: the serving path's prior): allowed when the query's prior point lies within
+//                 its radius of the cell's closed square (float64, from comparisons so that a NaN anywhere masks the pair) and when the
+//                 query's group is negative or equals the cell's.  Reads PriorArgs and the two group arrays; either half may be
+//                 absent (a NULL pointer set, uniform over the launch).
+// One type, QueryMask<MASK>, holds a lane's query side of the test and answers allowed(); sim_product_loop stages the cell side (group
+// ids, boxes) next to the block's rows.  What a family does not read sits behind `if constexpr` and is not compiled into it.
+#include <type_traits>
+
 #include "t2p_common.h"
 
 namespace t2p {
@@ -94,12 +99,40 @@ __device__ __forceinline__ bool prior_reaches(const PriorQuery& pq, const f64x2&
     const double xx = dx * dx, yy = dy * dy;
     return (xx + yy) <= pq.r2;
 }
-// geo && grp of one pair; box: the cell's four doubles in LDS (read only with has_geo)
-__device__ __forceinline__ bool prior_allowed(bool has_geo, bool has_grp, const PriorQuery& pq, int qgrp, int cgrp, const double* box) {
-    bool ok = !has_grp || qgrp < 0 || cgrp == qgrp;
-    if (has_geo) ok = ok && prior_reaches(pq, *(const f64x2*)box, *(const f64x2*)(box + 2));
-    return ok;
-}
+
+// A lane's query side of the mask: the group ids and prior points of its two queries q0 + 16 t + (lane & 15), t = 0, 1, and which
+// halves of the test the launch has (uniform).  What is not read - a query >= nq, an absent half, another family's members - keeps
+// its initial value; a prior call without groups thus asks for "any group" (-1), and allowed() needs no has_grp.
+template <int MASK>
+struct QueryMask {
+    int qgrp[2] = {MASK == MASK_PRIOR ? -1 : 0, MASK == MASK_PRIOR ? -1 : 0};
+    PriorQuery pq[2] = {};
+    bool has_grp, has_geo;
+
+    __device__ __forceinline__ QueryMask(const int32_t* __restrict__ query_group, const int32_t* __restrict__ cell_group,
+                                         const PriorArgs& prior, int64_t q0, int64_t nq)
+        : has_grp(MASK == MASK_GROUP || (MASK == MASK_PRIOR && cell_group != nullptr)),
+          has_geo(MASK == MASK_PRIOR && prior.box != nullptr) {
+        if constexpr (MASK != MASK_NONE) {
+#pragma unroll
+            for (int t = 0; t < 2; t++) {
+                const int64_t q = q0 + t * 16 + (threadIdx.x & 15);
+                if (has_grp && q < nq) qgrp[t] = query_group[q];
+                if constexpr (MASK == MASK_PRIOR) pq[t] = prior_query(prior, q, q < nq);
+            }
+        }
+    }
+    // the pair (query t of this lane, a cell of group cgrp); box: the cell's four doubles in LDS (read only with has_geo)
+    __device__ __forceinline__ bool allowed(int t, int cgrp, const double* box) const {
+        if constexpr (MASK == MASK_GROUP) return cgrp == qgrp[t];
+        if constexpr (MASK == MASK_PRIOR) {
+            bool ok = qgrp[t] < 0 || cgrp == qgrp[t];
+            if (has_geo) ok = ok && prior_reaches(pq[t], *(const f64x2*)box, *(const f64x2*)(box + 2));
+            return ok;
+        }
+        return true;
+    }
+};
 
 struct Cand {
     double s;
@@ -114,24 +147,50 @@ __device__ __forceinline__ int d_row(int lane, int reg) { return (lane >> 4) + 4
 // side, cell c sits at tile_pos(c) = (c & ~15) | (c & 3) << 2 | (c >> 2) & 3 (the two 2-bit fields swapped; its own inverse).
 __device__ __forceinline__ int tile_pos(int c) { return (c & ~15) | ((c & 3) << 2) | ((c >> 2) & 3); }
 
+// The LDS of a product kernel: c = the block's CB cell rows (pitch DIM + 4), g = its group ids at tile_pos (MASK != MASK_NONE),
+// b = its boxes, 4 doubles per cell (MASK_PRIOR).
+struct ProductLds {
+    float* c;
+    int* g;
+    double* b;
+    // the box of the cell in row d_row(lane, r) of the tile that starts at cell0 (blocks start at c_begin + a multiple of CB)
+    __device__ __forceinline__ const double* box(int64_t cell0, int64_t c_begin, int lane, int r) const {
+        return b + 4 * (((int)(cell0 - c_begin) & (CB - 1)) + d_row(lane, r));
+    }
+};
+template <int DIM, int MASK>
+__device__ __forceinline__ ProductLds product_lds() {
+    __shared__ __attribute__((aligned(16))) float c_buf[CB * (DIM + 4)];
+    ProductLds lds = {c_buf, nullptr, nullptr};
+    if constexpr (MASK != MASK_NONE) {
+        __shared__ __attribute__((aligned(16))) int g_buf[CB];
+        lds.g = g_buf;
+    }
+    if constexpr (MASK == MASK_PRIOR) {
+        __shared__ __attribute__((aligned(16))) double b_buf[CB * 4];
+        lds.b = b_buf;
+    }
+    return lds;
+}
+
 // The product loop of both paths: a workgroup of 4 waves keeps queries [q0_wg, q0_wg + QB) as MFMA B operands in registers
 // (wave w: two 16-query tiles from q0_wg + 32 w), streams cells [c_begin, c_end) through c_lds in CB-row blocks
 // (register-prefetched) and hands every finished 16 x 16 tile to epi(t, cell0, acc): lane `lane` holds, for query
 // q0_wg + 32 w + 16 t + (lane & 15), the scores of cells cell0 + d_row(lane, r) in acc[r], r = 0..3 (cells >= c_end are
 // products with zero rows; the epilogue drops them).  One fp64 fma chain over dim per pair, the same whatever the epilogue.
-// GROUPED (t2p_sim_topk_grouped): the block's CB group ids travel with its rows - one register of the first CB threads,
-// prefetched under the same cell < c_end guard (nothing is read past cell_group[c_end - 1]), stored to g_lds at tile_pos so
-// that a lane's four cells sit side by side - and epi receives them as cg[r] (ids of cells >= c_end are 0 and unused).
-// Without GROUPED cell_group / g_lds are not touched and cg is a constant the epilogues ignore.
-// MASK_PRIOR: GROUPED when cell_group is given (uniform), and the block's CB boxes travel the same way - one 16-byte half box in
-// a register pair of the first 2 CB threads, prefetched under the same guard (nothing is read past cell_box[c_end - 1]), stored to
-// b_lds as [cell of the block][x0 y0 x1 y1]; the epilogue reads its four cells' boxes from b_lds + 4 * (cell0 - cb + d_row).
+// With groups (mask.has_grp: MASK_GROUP, or MASK_PRIOR with the group arrays) the block's CB group ids travel with its rows - one
+// register of the first CB threads, prefetched under the same cell < c_end guard (nothing is read past cell_group[c_end - 1]),
+// stored to lds.g at tile_pos so that a lane's four cells sit side by side - and epi receives them as cg[r] (ids of cells >= c_end
+// are 0 and unused).  Without groups cell_group / lds.g are not touched and cg is a constant the epilogues ignore.
+// With geometry (mask.has_geo: MASK_PRIOR with the boxes) the block's CB boxes travel the same way - one 16-byte half box in a
+// register pair of the first 2 CB threads, prefetched under the same guard (nothing is read past cell_box[c_end - 1]), stored to
+// lds.b as [cell of the block][x0 y0 x1 y1]; the epilogue reads its four cells' boxes at lds.box().
 template <int DIM, int MASK, class Epi>
 __device__ __forceinline__ void sim_product_loop(const float* __restrict__ Q, const float* __restrict__ Cm, int64_t nq,
-                                                 int64_t q0_wg, int64_t c_begin, int64_t c_end, float* c_lds,
-                                                 const int32_t* __restrict__ cell_group, int* g_lds, Epi&& epi,
-                                                 const double* __restrict__ cell_box = nullptr, double* b_lds = nullptr) {
-    constexpr bool GROUPED = MASK == MASK_GROUP;
+                                                 int64_t q0_wg, int64_t c_begin, int64_t c_end, const ProductLds& lds,
+                                                 const QueryMask<MASK>& mask, const int32_t* __restrict__ cell_group,
+                                                 const double* __restrict__ cell_box, Epi&& epi) {
+    float* const c_lds = lds.c;
     constexpr int LDC = DIM + 4;
     constexpr int KQ = DIM / 4;   // k per lane group (lane>>4 owns k in [g*KQ, (g+1)*KQ))
     constexpr int F4 = CB * DIM / 4 / 256;
@@ -156,12 +215,11 @@ __device__ __forceinline__ void sim_product_loop(const float* __restrict__ Q, co
     int gstage = 0;
     f64x2 bstage = {0.0, 0.0};
     auto load_block = [&](int64_t cb) {
-        if constexpr (GROUPED) {
-            if (tid < CB) gstage = (cb + tid) < c_end ? cell_group[cb + tid] : 0;
+        if constexpr (MASK != MASK_NONE) {
+            if (mask.has_grp && tid < CB) gstage = (cb + tid) < c_end ? cell_group[cb + tid] : 0;
         }
         if constexpr (MASK == MASK_PRIOR) {
-            if (cell_group != nullptr && tid < CB) gstage = (cb + tid) < c_end ? cell_group[cb + tid] : 0;
-            if (cell_box != nullptr && tid < 2 * CB)
+            if (mask.has_geo && tid < 2 * CB)
                 bstage = (cb + (tid >> 1)) < c_end ? *(const f64x2*)(cell_box + (cb + (tid >> 1)) * 4 + (tid & 1) * 2) : f64x2{0.0, 0.0};
         }
 #pragma unroll
@@ -173,12 +231,11 @@ __device__ __forceinline__ void sim_product_loop(const float* __restrict__ Q, co
         }
     };
     auto store_block = [&]() {
-        if constexpr (GROUPED) {
-            if (tid < CB) g_lds[tile_pos(tid)] = gstage;
+        if constexpr (MASK != MASK_NONE) {
+            if (mask.has_grp && tid < CB) lds.g[tile_pos(tid)] = gstage;
         }
         if constexpr (MASK == MASK_PRIOR) {
-            if (cell_group != nullptr && tid < CB) g_lds[tile_pos(tid)] = gstage;
-            if (cell_box != nullptr && tid < 2 * CB) *(f64x2*)(b_lds + 2 * tid) = bstage;
+            if (mask.has_geo && tid < 2 * CB) *(f64x2*)(lds.b + 2 * tid) = bstage;
         }
 #pragma unroll
         for (int it = 0; it < F4; it++) {
@@ -221,9 +278,8 @@ __device__ __forceinline__ void sim_product_loop(const float* __restrict__ Q, co
                 }
             }
             i32x4 cg = {0, 0, 0, 0};
-            if constexpr (GROUPED) cg = *(const i32x4*)(g_lds + ct * 16 + g4 * 4);   // == tile_pos(ct * 16 + d_row(lane, r)), r = 0..3
-            if constexpr (MASK == MASK_PRIOR) {
-                if (cell_group != nullptr) cg = *(const i32x4*)(g_lds + ct * 16 + g4 * 4);
+            if constexpr (MASK != MASK_NONE) {
+                if (mask.has_grp) cg = *(const i32x4*)(lds.g + ct * 16 + g4 * 4);   // == tile_pos(ct * 16 + d_row(lane, r)), r = 0..3
             }
 #pragma unroll
             for (int t = 0; t < 2; t++) epi(t, cb + ct * 16, acc[t], cg);
@@ -232,27 +288,15 @@ __device__ __forceinline__ void sim_product_loop(const float* __restrict__ Q, co
     }
 }
 
-// GROUPED: a pair whose groups differ enters the lists as (-inf, cell) - a select on the finished score, so the allowed pairs'
-// bits are those of the ungrouped kernel; the lists start at (-inf, 0x7fffffff), so masked cells fill what the group leaves.
-// MASK_PRIOR: the same select, on geo && grp (prior_allowed).
+// A pair the mask does not allow enters the lists as (-inf, cell) - a select on the finished score, so the allowed pairs' bits
+// are those of the MASK_NONE kernel; the lists start at (-inf, 0x7fffffff), so masked cells fill what the mask leaves.
 template <int DIM, int MASK>
 __global__ __launch_bounds__(256, 1) void k_sim_partial(const float* __restrict__ Q, const float* __restrict__ Cm,
                                                          const int32_t* __restrict__ query_group,
                                                          const int32_t* __restrict__ cell_group,
                                                          int64_t nq, int64_t nc, int cells_per_split,
                                                          double* __restrict__ ps, int* __restrict__ pi, int n_split, PriorArgs prior) {
-    constexpr bool GROUPED = MASK == MASK_GROUP;
-    __shared__ __attribute__((aligned(16))) float c_lds[CB * (DIM + 4)];
-    int* g_lds = nullptr;
-    double* b_lds = nullptr;
-    if constexpr (MASK != MASK_NONE) {
-        __shared__ __attribute__((aligned(16))) int g_buf[CB];
-        g_lds = g_buf;
-    }
-    if constexpr (MASK == MASK_PRIOR) {
-        __shared__ __attribute__((aligned(16))) double b_buf[CB * 4];
-        b_lds = b_buf;
-    }
+    const ProductLds lds = product_lds<DIM, MASK>();
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g4 = lane >> 4, l15 = lane & 15;
     const int64_t q0 = (int64_t)blockIdx.x * QB + wave * 32;
     const int split = blockIdx.y;
@@ -265,34 +309,14 @@ __global__ __launch_bounds__(256, 1) void k_sim_partial(const float* __restrict_
     for (int t = 0; t < 2; t++)
 #pragma unroll
         for (int j = 0; j < KCAP; j++) { ls[t][j] = -INFINITY; li[t][j] = 0x7fffffff; }
-    int qgrp[2] = {0, 0};
-    if constexpr (GROUPED) {
-#pragma unroll
-        for (int t = 0; t < 2; t++) {
-            const int64_t q = q0 + t * 16 + l15;
-            if (q < nq) qgrp[t] = query_group[q];
-        }
-    }
+    const QueryMask<MASK> mask(query_group, cell_group, prior, q0, nq);
 
-    PriorQuery pq[2] = {};
-    if constexpr (MASK == MASK_PRIOR) {
-#pragma unroll
-        for (int t = 0; t < 2; t++) {
-            const int64_t q = q0 + t * 16 + l15;
-            if (query_group != nullptr && q < nq) qgrp[t] = query_group[q];
-            pq[t] = prior_query(prior, q, q < nq);
-        }
-    }
-
-    sim_product_loop<DIM, MASK>(Q, Cm, nq, (int64_t)blockIdx.x * QB, c_begin, c_end, c_lds, cell_group, g_lds,
-                                   [&](int t, int64_t cell0, const f64x4& acc, const i32x4& cg) {
+    sim_product_loop<DIM, MASK>(Q, Cm, nq, (int64_t)blockIdx.x * QB, c_begin, c_end, lds, mask, cell_group, prior.box,
+                                [&](int t, int64_t cell0, const f64x4& acc, const i32x4& cg) {
 #pragma unroll
         for (int r = 0; r < 4; r++) {
             const int64_t cell = cell0 + d_row(lane, r);
-            double s = (!GROUPED || cg[r] == qgrp[t]) ? acc[r] : -INFINITY;
-            if constexpr (MASK == MASK_PRIOR)
-                s = prior_allowed(prior.box != nullptr, cell_group != nullptr, pq[t], qgrp[t], cg[r],
-                                  b_lds + 4 * (((int)(cell0 - c_begin) & (CB - 1)) + d_row(lane, r))) ? acc[r] : -INFINITY;
+            const double s = mask.allowed(t, cg[r], lds.box(cell0, c_begin, lane, r)) ? acc[r] : -INFINITY;
             const int ci = (int)cell;
             if (cell < c_end && better(s, ci, ls[t][KCAP - 1], li[t][KCAP - 1])) {
                 ls[t][KCAP - 1] = s;
@@ -309,7 +333,7 @@ __global__ __launch_bounds__(256, 1) void k_sim_partial(const float* __restrict_
                 }
             }
         }
-    }, prior.box, b_lds);
+    });
     // partial lists: [q][split][g4][KCAP]
 #pragma unroll
     for (int t = 0; t < 2; t++) {
@@ -363,67 +387,33 @@ __global__ __launch_bounds__(256) void k_topk_merge(const double* __restrict__ p
 // Score tile of a query chunk: row q holds ld_s (a multiple of 16) doubles.  A lane stores its four scores side by side, so
 // cell c of a row sits at tile_pos(c) and the four lane groups of a query fill one 128-byte line.
 
-// GROUPED: a pair whose groups differ is written as -inf (score_key(-inf) > 0: k_topk_select retrieves it after every
-// finite score, lowest index first).
-// MASK_PRIOR: likewise, on geo && grp.
+// A pair the mask does not allow is written as -inf (score_key(-inf) > 0: k_topk_select retrieves it after every finite score,
+// lowest index first).
 template <int DIM, int MASK>
 __global__ __launch_bounds__(256, 1) void k_sim_scores(const float* __restrict__ Q, const float* __restrict__ Cm,
                                                         const int32_t* __restrict__ query_group,
                                                         const int32_t* __restrict__ cell_group,
                                                         int64_t nq, int64_t nc, int cells_per_split,
                                                         double* __restrict__ S, int64_t ld_s, PriorArgs prior) {
-    constexpr bool GROUPED = MASK == MASK_GROUP;
-    __shared__ __attribute__((aligned(16))) float c_lds[CB * (DIM + 4)];
-    int* g_lds = nullptr;
-    double* b_lds = nullptr;
-    if constexpr (MASK != MASK_NONE) {
-        __shared__ __attribute__((aligned(16))) int g_buf[CB];
-        g_lds = g_buf;
-    }
-    if constexpr (MASK == MASK_PRIOR) {
-        __shared__ __attribute__((aligned(16))) double b_buf[CB * 4];
-        b_lds = b_buf;
-    }
+    const ProductLds lds = product_lds<DIM, MASK>();
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g4 = lane >> 4, l15 = lane & 15;
     const int64_t q0 = (int64_t)blockIdx.x * QB + wave * 32;
     const int64_t c_begin = (int64_t)blockIdx.y * cells_per_split;
     const int64_t c_end = (c_begin + cells_per_split) < nc ? (c_begin + cells_per_split) : nc;
-    int qgrp[2] = {0, 0};
-    if constexpr (GROUPED) {
-#pragma unroll
-        for (int t = 0; t < 2; t++) {
-            const int64_t q = q0 + t * 16 + l15;
-            if (q < nq) qgrp[t] = query_group[q];
-        }
-    }
-    PriorQuery pq[2] = {};
-    if constexpr (MASK == MASK_PRIOR) {
-#pragma unroll
-        for (int t = 0; t < 2; t++) {
-            const int64_t q = q0 + t * 16 + l15;
-            if (query_group != nullptr && q < nq) qgrp[t] = query_group[q];
-            pq[t] = prior_query(prior, q, q < nq);
-        }
-    }
-    sim_product_loop<DIM, MASK>(Q, Cm, nq, (int64_t)blockIdx.x * QB, c_begin, c_end, c_lds, cell_group, g_lds,
-                                   [&](int t, int64_t cell0, const f64x4& acc, const i32x4& cg) {
+    const QueryMask<MASK> mask(query_group, cell_group, prior, q0, nq);
+    sim_product_loop<DIM, MASK>(Q, Cm, nq, (int64_t)blockIdx.x * QB, c_begin, c_end, lds, mask, cell_group, prior.box,
+                                [&](int t, int64_t cell0, const f64x4& acc, const i32x4& cg) {
         const int64_t q = q0 + t * 16 + l15;
         // whole 16-cell tiles: cell0 < c_end <= nc keeps cell0 + 15 < ld_s; the cells past nc in the last one are never read
         if (q < nq && cell0 < c_end) {
             double s[4];
 #pragma unroll
-            for (int r = 0; r < 4; r++) s[r] = (!GROUPED || cg[r] == qgrp[t]) ? acc[r] : -INFINITY;
-            if constexpr (MASK == MASK_PRIOR) {
-#pragma unroll
-                for (int r = 0; r < 4; r++)
-                    s[r] = prior_allowed(prior.box != nullptr, cell_group != nullptr, pq[t], qgrp[t], cg[r],
-                                         b_lds + 4 * (((int)(cell0 - c_begin) & (CB - 1)) + d_row(lane, r))) ? acc[r] : -INFINITY;
-            }
+            for (int r = 0; r < 4; r++) s[r] = mask.allowed(t, cg[r], lds.box(cell0, c_begin, lane, r)) ? acc[r] : -INFINITY;
             double* dst = S + q * ld_s + cell0 + g4 * 4;   // == tile_pos(cell0 + d_row(lane, r)) for r = 0..3
             *(f64x2*)dst = f64x2{s[0], s[1]};
             *(f64x2*)(dst + 2) = f64x2{s[2], s[3]};
         }
-    }, prior.box, b_lds);
+    });
 }
 
 // Order-preserving key of a score: a > b as doubles <=> key(a) > key(b); -0.0 and +0.0 share a key; every NaN maps to 0,
@@ -652,23 +642,18 @@ int64_t score_chunk(int64_t nq, int64_t nc) {
     return nq < cap ? nq : cap;
 }
 
-// pr != nullptr: the prior kernels (qg / cg and pr's geometry are each given or absent); else qg == nullptr: the ungrouped kernels
-// (the instantiations t2p_sim_topk has always run)
-template <int DIM>
-void launch_scores(dim3 grid, hipStream_t st, const float* Q, const float* Cm, const int32_t* qg, const int32_t* cg,
-                   const PriorArgs* pr, int64_t nq, int64_t nc, int cps, double* S, int64_t ld_s) {
-    const PriorArgs none = {nullptr, nullptr, nullptr};
-    if (pr) hipLaunchKernelGGL((k_sim_scores<DIM, MASK_PRIOR>), grid, dim3(256), 0, st, Q, Cm, qg, cg, nq, nc, cps, S, ld_s, *pr);
-    else if (qg) hipLaunchKernelGGL((k_sim_scores<DIM, MASK_GROUP>), grid, dim3(256), 0, st, Q, Cm, qg, cg, nq, nc, cps, S, ld_s, none);
-    else hipLaunchKernelGGL((k_sim_scores<DIM, MASK_NONE>), grid, dim3(256), 0, st, Q, Cm, qg, cg, nq, nc, cps, S, ld_s, none);
-}
-template <int DIM>
-void launch_partial(dim3 grid, hipStream_t st, const float* Q, const float* Cm, const int32_t* qg, const int32_t* cg,
-                    const PriorArgs* pr, int64_t nq, int64_t nc, int cps, double* ps, int* pi, int sp) {
-    const PriorArgs none = {nullptr, nullptr, nullptr};
-    if (pr) hipLaunchKernelGGL((k_sim_partial<DIM, MASK_PRIOR>), grid, dim3(256), 0, st, Q, Cm, qg, cg, nq, nc, cps, ps, pi, sp, *pr);
-    else if (qg) hipLaunchKernelGGL((k_sim_partial<DIM, MASK_GROUP>), grid, dim3(256), 0, st, Q, Cm, qg, cg, nq, nc, cps, ps, pi, sp, none);
-    else hipLaunchKernelGGL((k_sim_partial<DIM, MASK_NONE>), grid, dim3(256), 0, st, Q, Cm, qg, cg, nq, nc, cps, ps, pi, sp, none);
+// The run-time (dim, mask) as compile-time constants: f(D, M) with decltype(D)::value = DIM, decltype(M)::value = MASK.
+// dim is one of the three instantiated widths (sim_topk_impl refuses any other).
+template <class F>
+void with_dim_mask(int dim, int mask, F&& f) {
+    auto with_mask = [&](auto d) {
+        if (mask == MASK_PRIOR) f(d, std::integral_constant<int, MASK_PRIOR>{});
+        else if (mask == MASK_GROUP) f(d, std::integral_constant<int, MASK_GROUP>{});
+        else f(d, std::integral_constant<int, MASK_NONE>{});
+    };
+    if (dim == 256) with_mask(std::integral_constant<int, 256>{});
+    else if (dim == 384) with_mask(std::integral_constant<int, 384>{});
+    else with_mask(std::integral_constant<int, 128>{});
 }
 
 // The route (the rule at the top of the file): a function of (nq, nc) alone for every k <= KREG
@@ -678,47 +663,20 @@ bool use_score_tile(int64_t nq, int64_t nc, int k) {
     return large && score_chunk(1, nc) > 0;
 }
 
-// every entry point: qg / cg are nullptr for the unrestricted call, pr for all but the prior call
-int sim_topk_impl(const float* Q, const float* Cm, const int32_t* qg, const int32_t* cg, const PriorArgs* pr, int64_t nq, int64_t nc,
-                  int dim, int k, int64_t c_index_offset, int64_t* out_idx, double* out_score, void* ws, size_t ws_bytes, hipStream_t st);
-
-}  // namespace
-
-size_t sim_topk_workspace_bytes(int64_t nq, int64_t nc, int k) {
-    if (use_score_tile(nq, nc, k)) return (size_t)score_chunk(nq, nc) * score_ld(nc) * sizeof(double) + 256;
-    const int sp = pick_splits(nq, nc);
-    return (size_t)nq * sp * 4 * KCAP * (sizeof(double) + sizeof(int)) + 256;
+// What every entry point refuses first, under its own name.  An empty side has no storage to point to (nq == 0 launches nothing;
+// k < 1 is refused by its range, in sim_topk_impl).
+int check_sizes_and_pointers(const char* name, const float* Q, const float* Cm, int64_t nq, int64_t nc, int k, const int64_t* out_idx,
+                             const double* out_score) {
+    T2P_CHECK_ARG(nq >= 0 && nc >= 0, "%s: negative size", name);
+    T2P_CHECK_ARG((Q != nullptr || nq == 0) && (Cm != nullptr || nc == 0) && ((out_idx != nullptr && out_score != nullptr) || nq == 0 || k < 1),
+                  "%s: NULL argument", name);
+    return 0;
 }
 
-int launch_sim_topk(const float* Q, const float* Cm, int64_t nq, int64_t nc, int dim, int k, int64_t c_index_offset,
-                    int64_t* out_idx, double* out_score, void* ws, size_t ws_bytes, hipStream_t st) {
-    return sim_topk_impl(Q, Cm, nullptr, nullptr, nullptr, nq, nc, dim, k, c_index_offset, out_idx, out_score, ws, ws_bytes, st);
-}
-
-int launch_sim_topk_grouped(const float* Q, const float* Cm, const int32_t* query_group, const int32_t* cell_group, int64_t nq,
-                            int64_t nc, int dim, int k, int64_t c_index_offset, int64_t* out_idx, double* out_score, void* ws,
-                            size_t ws_bytes, hipStream_t st) {
-    T2P_CHECK_ARG((query_group != nullptr || nq == 0) && (cell_group != nullptr || nc == 0), "sim_topk_grouped: NULL group array");
-    // (query_group is NULL only with nq == 0, which launches nothing; with nc == 0 no kernel reads cell_group)
-    return sim_topk_impl(Q, Cm, query_group, cell_group, nullptr, nq, nc, dim, k, c_index_offset, out_idx, out_score, ws, ws_bytes, st);
-}
-
-int launch_sim_topk_prior(const float* Q, const float* Cm, const double* query_xy, const double* query_radius, const double* cell_box,
-                          const int32_t* query_group, const int32_t* cell_group, int64_t nq, int64_t nc, int dim, int k,
-                          int64_t c_index_offset, int64_t* out_idx, double* out_score, void* ws, size_t ws_bytes, hipStream_t st) {
-    const int n_geo = (query_xy != nullptr) + (query_radius != nullptr) + (cell_box != nullptr);
-    const int n_grp = (query_group != nullptr) + (cell_group != nullptr);
-    T2P_CHECK_ARG(n_geo == 0 || n_geo == 3, "sim_topk_prior: query_xy, query_radius and cell_box go together (%d of 3 given)", n_geo);
-    T2P_CHECK_ARG(n_grp == 0 || n_grp == 2, "sim_topk_prior: query_group and cell_group go together (1 of 2 given)");
-    T2P_CHECK_ARG(n_geo + n_grp > 0, "sim_topk_prior: neither geometry nor groups given: call t2p_sim_topk");
-    T2P_CHECK_ARG((((uintptr_t)cell_box) & 15) == 0, "sim_topk_prior: cell_box must be 16-byte aligned");
-    const PriorArgs pr = {query_xy, query_radius, cell_box};
-    return sim_topk_impl(Q, Cm, query_group, cell_group, &pr, nq, nc, dim, k, c_index_offset, out_idx, out_score, ws, ws_bytes, st);
-}
-
-namespace {
-int sim_topk_impl(const float* Q, const float* Cm, const int32_t* qg, const int32_t* cg, const PriorArgs* pr, int64_t nq, int64_t nc,
-                  int dim, int k, int64_t c_index_offset, int64_t* out_idx, double* out_score, void* ws, size_t ws_bytes, hipStream_t st) {
+// every entry point: the family `mask` with what it reads (qg / cg are nullptr for MASK_NONE, pr's members for all but MASK_PRIOR)
+int sim_topk_impl(int mask, const float* Q, const float* Cm, const int32_t* qg, const int32_t* cg, const PriorArgs& pr, int64_t nq,
+                  int64_t nc, int dim, int k, int64_t c_index_offset, int64_t* out_idx, double* out_score, void* ws, size_t ws_bytes,
+                  hipStream_t st) {
     T2P_CHECK_ARG(k >= 1 && k <= KMAX, "sim_topk: k=%d outside [1,%d]", k, KMAX);
     T2P_CHECK_ARG(dim == 256 || dim == 128 || dim == 384, "sim_topk: dim=%d not instantiated (128, 256, 384)", dim);
     T2P_CHECK_ARG(nc < 0x7fffffff, "sim_topk: nc too large");
@@ -744,13 +702,12 @@ int sim_topk_impl(const float* Q, const float* Cm, const int32_t* qg, const int3
                 cps = ((cps + CB - 1) / CB) * CB;
                 const dim3 grid((unsigned)((n + QB - 1) / QB), (unsigned)sp);
                 ProfScope ps_("sim_scores", st);
-                const int32_t* qga = qg ? qg + qa : nullptr;
-                PriorArgs pra = {nullptr, nullptr, nullptr};   // the chunk's queries: the per-query arrays move with qa
-                if (pr && pr->box) pra = PriorArgs{pr->xy + 2 * qa, pr->radius + qa, pr->box};
-                const PriorArgs* prp = pr ? &pra : nullptr;
-                if (dim == 256) launch_scores<256>(grid, st, Q + qa * dim, Cm, qga, cg, prp, n, nc, cps, S, ld_s);
-                else if (dim == 384) launch_scores<384>(grid, st, Q + qa * dim, Cm, qga, cg, prp, n, nc, cps, S, ld_s);
-                else launch_scores<128>(grid, st, Q + qa * dim, Cm, qga, cg, prp, n, nc, cps, S, ld_s);
+                const int32_t* qga = qg ? qg + qa : nullptr;   // the chunk's queries: the per-query arrays move with qa
+                const PriorArgs pra = pr.box ? PriorArgs{pr.xy + 2 * qa, pr.radius + qa, pr.box} : pr;
+                with_dim_mask(dim, mask, [&](auto D, auto M) {
+                    hipLaunchKernelGGL((k_sim_scores<decltype(D)::value, decltype(M)::value>), grid, dim3(256), 0, st, Q + qa * dim, Cm,
+                                       qga, cg, n, nc, cps, S, ld_s, pra);
+                });
             }
             T2P_CHECK_LAUNCH("sim_scores");
             ProfScope ps2_("topk_select", st);
@@ -769,9 +726,10 @@ int sim_topk_impl(const float* Q, const float* Cm, const int32_t* qg, const int3
     dim3 grid((unsigned)((nq + QB - 1) / QB), (unsigned)sp);
     {
     ProfScope ps_("sim_partial", st);
-    if (dim == 256) launch_partial<256>(grid, st, Q, Cm, qg, cg, pr, nq, nc, cps, ps, pi, sp);
-    else if (dim == 384) launch_partial<384>(grid, st, Q, Cm, qg, cg, pr, nq, nc, cps, ps, pi, sp);
-    else launch_partial<128>(grid, st, Q, Cm, qg, cg, pr, nq, nc, cps, ps, pi, sp);
+    with_dim_mask(dim, mask, [&](auto D, auto M) {
+        hipLaunchKernelGGL((k_sim_partial<decltype(D)::value, decltype(M)::value>), grid, dim3(256), 0, st, Q, Cm, qg, cg, nq, nc, cps,
+                           ps, pi, sp, pr);
+    });
     }
     T2P_CHECK_LAUNCH("sim_partial");
     ProfScope ps2_("topk_merge", st);
@@ -780,6 +738,44 @@ int sim_topk_impl(const float* Q, const float* Cm, const int32_t* qg, const int3
     T2P_CHECK_LAUNCH("topk_merge");
     return 0;
 }
+constexpr PriorArgs kNoPrior = {nullptr, nullptr, nullptr};
+
 }  // namespace
+
+size_t sim_topk_workspace_bytes(int64_t nq, int64_t nc, int k) {
+    if (use_score_tile(nq, nc, k)) return (size_t)score_chunk(nq, nc) * score_ld(nc) * sizeof(double) + 256;
+    const int sp = pick_splits(nq, nc);
+    return (size_t)nq * sp * 4 * KCAP * (sizeof(double) + sizeof(int)) + 256;
+}
+
+int launch_sim_topk(const float* Q, const float* Cm, int64_t nq, int64_t nc, int dim, int k, int64_t c_index_offset,
+                    int64_t* out_idx, double* out_score, void* ws, size_t ws_bytes, hipStream_t st) {
+    T2P_TRY(check_sizes_and_pointers("sim_topk", Q, Cm, nq, nc, k, out_idx, out_score));
+    return sim_topk_impl(MASK_NONE, Q, Cm, nullptr, nullptr, kNoPrior, nq, nc, dim, k, c_index_offset, out_idx, out_score, ws, ws_bytes, st);
+}
+
+int launch_sim_topk_grouped(const float* Q, const float* Cm, const int32_t* query_group, const int32_t* cell_group, int64_t nq,
+                            int64_t nc, int dim, int k, int64_t c_index_offset, int64_t* out_idx, double* out_score, void* ws,
+                            size_t ws_bytes, hipStream_t st) {
+    T2P_TRY(check_sizes_and_pointers("sim_topk_grouped", Q, Cm, nq, nc, k, out_idx, out_score));
+    T2P_CHECK_ARG((query_group != nullptr || nq == 0) && (cell_group != nullptr || nc == 0), "sim_topk_grouped: NULL group array");
+    // (query_group is NULL only with nq == 0, which launches nothing; with nc == 0 no kernel reads cell_group)
+    return sim_topk_impl(MASK_GROUP, Q, Cm, query_group, cell_group, kNoPrior, nq, nc, dim, k, c_index_offset, out_idx, out_score, ws,
+                         ws_bytes, st);
+}
+
+int launch_sim_topk_prior(const float* Q, const float* Cm, const double* query_xy, const double* query_radius, const double* cell_box,
+                          const int32_t* query_group, const int32_t* cell_group, int64_t nq, int64_t nc, int dim, int k,
+                          int64_t c_index_offset, int64_t* out_idx, double* out_score, void* ws, size_t ws_bytes, hipStream_t st) {
+    T2P_TRY(check_sizes_and_pointers("sim_topk_prior", Q, Cm, nq, nc, k, out_idx, out_score));
+    const int n_geo = (query_xy != nullptr) + (query_radius != nullptr) + (cell_box != nullptr);
+    const int n_grp = (query_group != nullptr) + (cell_group != nullptr);
+    T2P_CHECK_ARG(n_geo == 0 || n_geo == 3, "sim_topk_prior: query_xy, query_radius and cell_box go together (%d of 3 given)", n_geo);
+    T2P_CHECK_ARG(n_grp == 0 || n_grp == 2, "sim_topk_prior: query_group and cell_group go together (1 of 2 given)");
+    T2P_CHECK_ARG(n_geo + n_grp > 0, "sim_topk_prior: neither geometry nor groups given: call t2p_sim_topk");
+    T2P_CHECK_ARG((((uintptr_t)cell_box) & 15) == 0, "sim_topk_prior: cell_box must be 16-byte aligned");
+    return sim_topk_impl(MASK_PRIOR, Q, Cm, query_group, cell_group, PriorArgs{query_xy, query_radius, cell_box}, nq, nc, dim, k,
+                         c_index_offset, out_idx, out_score, ws, ws_bytes, st);
+}
 
 }  // namespace t2p

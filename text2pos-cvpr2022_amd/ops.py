@@ -491,48 +491,50 @@ def rownorm(x: torch.Tensor) -> torch.Tensor:
     return out
 
 
-def sim_topk(queries: torch.Tensor, cells: torch.Tensor, k: int, index_offset: int = 0):
-    """Float64 cosine scores + ordered top-k (ties -> lower index).  Returns (idx int64 [nq,k], score f64 [nq,k])."""
+def _sim_topk_call(entry: str, queries: torch.Tensor, cells: torch.Tensor, k: int, index_offset: int, extra=None, skip_empty=False):
+    """What sim_topk, sim_topk_grouped and sim_topk_prior share: the checks of queries / cells, the outputs, the workspace and the
+    call of t2p_<entry>.  extra(nq, nc, dev) validates the wrapper's own tensors and returns them in the entry point's order (they
+    follow `cells`); skip_empty: nq == 0 returns the empty outputs without the call."""
     _need(queries, "queries", torch.float32, 2)
     _need(cells, "cells", torch.float32, 2, queries.device)
     nq, dim = queries.shape
     nc = cells.shape[0]
     if cells.shape[1] != dim:
-        raise RuntimeError(f"sim_topk: queries have dim {dim}, cells {cells.shape[1]}")
+        raise RuntimeError(f"{entry}: queries have dim {dim}, cells {cells.shape[1]}")
     dev = queries.device
+    more = extra(nq, nc, dev) if extra else ()
     idx = torch.empty((nq, k), dtype=torch.int64, device=dev)
     score = torch.empty((nq, k), dtype=torch.float64, device=dev)
+    if nq == 0 and skip_empty:
+        return idx, score
     nbytes = L.lib().t2p_sim_topk_workspace_bytes(nq, nc, k)
     ws = workspace(dev, nbytes, "sim_topk")
-    L.check(L.lib().t2p_sim_topk(_ptr(queries), _ptr(cells), nq, nc, dim, k, int(index_offset), _ptr(idx), _ptr(score),
-                                 _ptr(ws), ws.numel(), _stream(dev)), "t2p_sim_topk")
+    L.check(getattr(L.lib(), "t2p_" + entry)(_ptr(queries), _ptr(cells), *[_ptr(t) for t in more], nq, nc, dim, k, int(index_offset),
+                                             _ptr(idx), _ptr(score), _ptr(ws), ws.numel(), _stream(dev)), "t2p_" + entry)
     return idx, score
+
+
+def _need_groups(entry: str, query_group, cell_group, nq: int, nc: int, dev):
+    _need(query_group, "query_group", torch.int32, 1, dev)
+    _need(cell_group, "cell_group", torch.int32, 1, dev)
+    if query_group.shape[0] != nq or cell_group.shape[0] != nc:
+        raise RuntimeError(f"{entry}: {query_group.shape[0]} query groups for {nq} queries, "
+                           f"{cell_group.shape[0]} cell groups for {nc} cells")
+
+
+def sim_topk(queries: torch.Tensor, cells: torch.Tensor, k: int, index_offset: int = 0):
+    """Float64 cosine scores + ordered top-k (ties -> lower index).  Returns (idx int64 [nq,k], score f64 [nq,k])."""
+    return _sim_topk_call("sim_topk", queries, cells, k, index_offset)
 
 
 def sim_topk_grouped(queries: torch.Tensor, cells: torch.Tensor, query_group: torch.Tensor, cell_group: torch.Tensor, k: int,
                      index_offset: int = 0):
     """sim_topk over the effective score `cell_group[c] == query_group[q] ? score : -inf` (int32 group ids, [nq] and [nc]):
     a query's own group first, then masked cells at -inf by ascending index.  Returns (idx int64 [nq,k], score f64 [nq,k])."""
-    _need(queries, "queries", torch.float32, 2)
-    _need(cells, "cells", torch.float32, 2, queries.device)
-    _need(query_group, "query_group", torch.int32, 1, queries.device)
-    _need(cell_group, "cell_group", torch.int32, 1, queries.device)
-    nq, dim = queries.shape
-    nc = cells.shape[0]
-    if cells.shape[1] != dim:
-        raise RuntimeError(f"sim_topk_grouped: queries have dim {dim}, cells {cells.shape[1]}")
-    if query_group.shape[0] != nq or cell_group.shape[0] != nc:
-        raise RuntimeError(f"sim_topk_grouped: {query_group.shape[0]} query groups for {nq} queries, "
-                           f"{cell_group.shape[0]} cell groups for {nc} cells")
-    dev = queries.device
-    idx = torch.empty((nq, k), dtype=torch.int64, device=dev)
-    score = torch.empty((nq, k), dtype=torch.float64, device=dev)
-    nbytes = L.lib().t2p_sim_topk_workspace_bytes(nq, nc, k)
-    ws = workspace(dev, nbytes, "sim_topk")
-    L.check(L.lib().t2p_sim_topk_grouped(_ptr(queries), _ptr(cells), _ptr(query_group), _ptr(cell_group), nq, nc, dim, k,
-                                         int(index_offset), _ptr(idx), _ptr(score), _ptr(ws), ws.numel(), _stream(dev)),
-            "t2p_sim_topk_grouped")
-    return idx, score
+    def groups(nq, nc, dev):
+        _need_groups("sim_topk_grouped", query_group, cell_group, nq, nc, dev)
+        return query_group, cell_group
+    return _sim_topk_call("sim_topk_grouped", queries, cells, k, index_offset, groups)
 
 
 def sim_topk_prior(queries: torch.Tensor, cells: torch.Tensor, k: int, index_offset: int = 0, *, query_xy=None, query_radius=None,
@@ -541,43 +543,26 @@ def sim_topk_prior(queries: torch.Tensor, cells: torch.Tensor, k: int, index_off
     lies within query_radius [nq] of the cell's closed square cell_box [nc, 4] = x0 y0 x1 y1 (float64, all three or none), and
     query_group [nq] is negative or equals cell_group [nc] (int32, both or none).  Every other pair scores -inf: a query's
     allowed cells first, then masked cells at -inf by ascending index.  Returns (idx int64 [nq,k], score f64 [nq,k])."""
-    _need(queries, "queries", torch.float32, 2)
-    _need(cells, "cells", torch.float32, 2, queries.device)
-    nq, dim = queries.shape
-    nc = cells.shape[0]
-    if cells.shape[1] != dim:
-        raise RuntimeError(f"sim_topk_prior: queries have dim {dim}, cells {cells.shape[1]}")
-    geo, grp = (query_xy, query_radius, cell_box), (query_group, cell_group)
-    if any(t is None for t in geo) != all(t is None for t in geo):
-        raise RuntimeError("sim_topk_prior: query_xy, query_radius and cell_box go together")
-    if (query_group is None) != (cell_group is None):
-        raise RuntimeError("sim_topk_prior: query_group and cell_group go together")
-    if cell_box is None and cell_group is None:
-        raise RuntimeError("sim_topk_prior: neither geometry nor groups given: call sim_topk")
-    dev = queries.device
-    if cell_box is not None:
-        _need(query_xy, "query_xy", torch.float64, 2, dev)
-        _need(query_radius, "query_radius", torch.float64, 1, dev)
-        _need(cell_box, "cell_box", torch.float64, 2, dev)
-        if tuple(query_xy.shape) != (nq, 2) or query_radius.shape[0] != nq or tuple(cell_box.shape) != (nc, 4):
-            raise RuntimeError(f"sim_topk_prior: query_xy {tuple(query_xy.shape)}, query_radius {tuple(query_radius.shape)}, cell_box "
-                               f"{tuple(cell_box.shape)} for {nq} queries and {nc} cells: expected ({nq}, 2), ({nq},), ({nc}, 4)")
-    if cell_group is not None:
-        _need(query_group, "query_group", torch.int32, 1, dev)
-        _need(cell_group, "cell_group", torch.int32, 1, dev)
-        if query_group.shape[0] != nq or cell_group.shape[0] != nc:
-            raise RuntimeError(f"sim_topk_prior: {query_group.shape[0]} query groups for {nq} queries, "
-                               f"{cell_group.shape[0]} cell groups for {nc} cells")
-    idx = torch.empty((nq, k), dtype=torch.int64, device=dev)
-    score = torch.empty((nq, k), dtype=torch.float64, device=dev)
-    if nq == 0:      # (an empty tensor has no address: the entry point would read a partial pointer set)
-        return idx, score
-    nbytes = L.lib().t2p_sim_topk_workspace_bytes(nq, nc, k)
-    ws = workspace(dev, nbytes, "sim_topk")
-    L.check(L.lib().t2p_sim_topk_prior(_ptr(queries), _ptr(cells), _ptr(query_xy), _ptr(query_radius), _ptr(cell_box),
-                                       _ptr(query_group), _ptr(cell_group), nq, nc, dim, k, int(index_offset), _ptr(idx),
-                                       _ptr(score), _ptr(ws), ws.numel(), _stream(dev)), "t2p_sim_topk_prior")
-    return idx, score
+    def prior(nq, nc, dev):
+        geo = (query_xy, query_radius, cell_box)
+        if any(t is None for t in geo) != all(t is None for t in geo):
+            raise RuntimeError("sim_topk_prior: query_xy, query_radius and cell_box go together")
+        if (query_group is None) != (cell_group is None):
+            raise RuntimeError("sim_topk_prior: query_group and cell_group go together")
+        if cell_box is None and cell_group is None:
+            raise RuntimeError("sim_topk_prior: neither geometry nor groups given: call sim_topk")
+        if cell_box is not None:
+            _need(query_xy, "query_xy", torch.float64, 2, dev)
+            _need(query_radius, "query_radius", torch.float64, 1, dev)
+            _need(cell_box, "cell_box", torch.float64, 2, dev)
+            if tuple(query_xy.shape) != (nq, 2) or query_radius.shape[0] != nq or tuple(cell_box.shape) != (nc, 4):
+                raise RuntimeError(f"sim_topk_prior: query_xy {tuple(query_xy.shape)}, query_radius {tuple(query_radius.shape)}, cell_box "
+                                   f"{tuple(cell_box.shape)} for {nq} queries and {nc} cells: expected ({nq}, 2), ({nq},), ({nc}, 4)")
+        if cell_group is not None:
+            _need_groups("sim_topk_prior", query_group, cell_group, nq, nc, dev)
+        return query_xy, query_radius, cell_box, query_group, cell_group
+    # (skip_empty: an empty tensor has no address: the entry point would read a partial pointer set)
+    return _sim_topk_call("sim_topk_prior", queries, cells, k, index_offset, prior, skip_empty=True)
 
 
 # ---------------------------------------------------------------------------------------------------------------

@@ -601,7 +601,8 @@ void t2p_profile_repeat(const char* scope, int32_t reps);
  * tiny and the Python loop around them was bound by the host's launch rate).  Layouts as modules._LstmTrainFn keeps them:
  * gates [T][B][4D], cs / hs [T+1][B][D] with slice 0 = the initial state (zeros), w_hh_k [D][4D] = W_hh^T, pre_ws [B][4D] scratch.
  * backward: dh_last [B][D] = the gradient of the final hidden state, w_hh_t [4D][D] = W_hh, d_pre [T][B][4D] (out),
- * ws [5][B][D] scratch.  embed_dim must be a multiple of 4 (else T2P_E_UNSUPPORTED: the host falls back to the per-step calls).
+ * ws [5][B][D] scratch.  embed_dim must be a multiple of 4 (else T2P_E_UNSUPPORTED with nothing written: the host falls back to the
+ * per-step calls, its products zero-padded to t2p_gemm's granules).
  * The recurrent products run on a few-rows kernel (tg_gemm.hip::k_gemm_skinny): fp32 sums in another order than t2p_gemm's. */
 int t2p_lstm_train_forward(const float* gate_table, const float* w_hh_k, const int32_t* tokens, const int32_t* lengths,
                            int64_t batch, int32_t max_len, int32_t embed_dim, int32_t reverse, float* gates, float* cs, float* hs,
@@ -667,13 +668,25 @@ int t2p_rownorm_backward(const float* x, const float* dy, int64_t n_rows, int32_
 
 /* PairwiseRankingLoss (training/losses.py:126-164, margin training/args.py:46) on the score matrix of the L2-normalised
  * anchor / positive embeddings, scores [B][B] = im_n s_n^T:  row_loss [B] (loss = sum(row_loss) / B),
- * d_scores [B][B] = dLoss / dScores, row_count [B] scratch.  Deterministic (fixed-order reductions). */
+ * d_scores [B][B] = dLoss / dScores, row_count [B] scratch.  Deterministic (fixed-order reductions).
+ * Hinge rule: a term max(0, x) counts, and has gradient 1, only where x > 0.  At an exact hinge x == 0 this implementation
+ * yields gradient 0; the reference's element-wise torch.max(zeros, x) yields 1/2 there.  Off the diagonal d_scores is
+ * (number of its two terms that are > 0) * fl(1 / B), on the diagonal -(number of terms > 0 that hold it) / B.
+ * NaN rule: a NaN hinge stays NaN, as in torch.max(zeros, x): row_loss[i] is NaN if S[i][i], any S[i][j] or any S[j][j] is.
+ * Every entry of d_scores is written; its values where a NaN took part are unspecified.  batch in [0, 32768]; 0 writes nothing. */
 int t2p_pairwise_ranking(const float* scores, int32_t batch, float margin, float* row_loss, float* d_scores, float* row_count,
                          t2p_stream_t stream);
 
 /* HardestRankingLoss (training/losses.py:167-201, --ranking_loss hardest) on the same score matrix: best [2B] = the largest
  * hinge of every row (first B) and column (last B), where [2B] = its position (-1 if none is positive),
- * d_scores [B][B] = dLoss / dScores; loss = (sum best[:B] + sum best[B:]) / B. */
+ * d_scores [B][B] = dLoss / dScores; loss = (sum best[:B] + sum best[B:]) / B.
+ * Hinge rule: only a hinge > 0 can win; a row or column whose largest hinge is <= 0 has best = 0, where = -1 and adds nothing
+ * to d_scores (torch's relu has gradient 0 at an exact 0 as well; an element-wise torch.max(zeros, x) would yield 1/2).
+ * Tie rule: among equal maxima the lowest index wins (torch.max on the CPU).  d_scores gets +fl(1 / B) at each winner and
+ * -fl(1 / B) on the diagonal of its row (row maxima) or column (column maxima): every entry is a small integer times fl(1 / B).
+ * NaN rule: a NaN hinge wins over every number, as relu and max keep it in torch: best = NaN, where = the first position that
+ * holds one.  Every entry of d_scores is written; its values in the rows / columns of a NaN winner are unspecified.
+ * batch in [0, 32768]; 0 writes nothing. */
 int t2p_hardest_ranking(const float* scores, int32_t batch, float margin, float* best, int32_t* where, float* d_scores,
                         t2p_stream_t stream);
 

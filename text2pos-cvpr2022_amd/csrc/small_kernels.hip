@@ -600,6 +600,8 @@ __global__ __launch_bounds__(256) void k_pack_scene_aug(const float* __restrict_
 //   loss = (sum cost_s + sum cost_im) / B.
 // One block per row: the row's loss, dLoss/dS off the diagonal, and the row's count of active cost_im terms (which
 // the diagonal entry of the gradient needs); fixed-order reductions, so the result is run-to-run identical.
+// A hinge counts, and has gradient 1, only where it is > 0 (an exact 0 has gradient 0; torch.max(zeros, x) gives 1/2 there).
+// A NaN hinge stays NaN in the row's loss, as in torch.max(zeros, x): the select below keeps it, fmaxf would drop it.
 __global__ __launch_bounds__(256) void k_rank_rows(const float* __restrict__ S, int B, float margin,
                                                    float* __restrict__ row_loss, float* __restrict__ dS,
                                                    float* __restrict__ row_cnt) {
@@ -611,7 +613,7 @@ __global__ __launch_bounds__(256) void k_rank_rows(const float* __restrict__ S, 
         if (j == i) continue;
         const float sij = S[(int64_t)i * B + j];
         const float cs = margin - S[(int64_t)j * B + j] + sij, ci = margin - di + sij;
-        loss += fmaxf(cs, 0.f) + fmaxf(ci, 0.f);
+        loss += (cs <= 0.f ? 0.f : cs) + (ci <= 0.f ? 0.f : ci);
         cnt += ci > 0.f ? 1.f : 0.f;
         dS[(int64_t)i * B + j] = ((cs > 0.f ? 1.f : 0.f) + (ci > 0.f ? 1.f : 0.f)) * inv;
     }
@@ -651,7 +653,9 @@ __global__ __launch_bounds__(256) void k_rank_diag(const float* __restrict__ S, 
 // HardestRankingLoss (training/losses.py:167-201): per row i the largest hinge margin + S[i][j] - S[i][i] over j != i, per
 // column j the largest margin + S[i][j] - S[j][j] over i != j; loss = mean of the row maxima + mean of the column maxima.
 // Block b < B: row b; block b >= B: column b - B.  Writes the maximum (>= 0) and its position (-1: nothing above 0; first
-// position on ties, torch.max's choice on the CPU path the reference was written against).
+// position on ties, torch.max's choice on the CPU path the reference was written against).  A NaN hinge wins over every number
+// and sticks, in the lane's scan and through the LDS reduction (relu and max keep NaN in torch): best = NaN, where = the first
+// position that holds one.
 __global__ __launch_bounds__(256) void k_hardest_scan(const float* __restrict__ S, int B, float margin, float* __restrict__ best,
                                                       int32_t* __restrict__ where) {
     __shared__ float bv[256];
@@ -665,7 +669,7 @@ __global__ __launch_bounds__(256) void k_hardest_scan(const float* __restrict__ 
     for (int k = tid; k < B; k += 256) {
         if (k == a) continue;
         const float h = margin + (is_row ? S[(int64_t)a * B + k] : S[(int64_t)k * B + a]) - d;
-        if (h > v) { v = h; w = k; }
+        if (h > v || (h != h && v == v)) { v = h; w = k; }
     }
     bv[tid] = v;
     bi[tid] = w;
@@ -674,7 +678,10 @@ __global__ __launch_bounds__(256) void k_hardest_scan(const float* __restrict__ 
         if (tid < s) {
             const float ov = bv[tid + s];
             const int ow = bi[tid + s];
-            if (ow >= 0 && (ov > bv[tid] || (ov == bv[tid] && (bi[tid] < 0 || ow < bi[tid])))) {
+            const float mv = bv[tid];
+            const int mw = bi[tid];
+            const bool take = ov != ov ? (mv == mv || ow < mw) : (mv == mv && (ov > mv || (ov == mv && (mw < 0 || ow < mw))));
+            if (ow >= 0 && take) {
                 bv[tid] = ov;
                 bi[tid] = ow;
             }

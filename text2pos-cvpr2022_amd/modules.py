@@ -54,9 +54,10 @@ class _LstmTrainFn(torch.autograd.Function):
     """Training-mode text branch (first part): Embedding -> packed biLSTM -> mean of the two final
     hidden states (models/modules.py:77-90) with a backward pass, for `anchor = model.encode_text(...); loss.backward()`
     (training/coarse.py:44-58).  The recurrence runs on the HIP kernels behind t2p_lstm_cell_forward / _backward and
-    t2p_gemm, the time loop inside the library (t2p_lstm_train_forward / _backward) when the width allows, else step by step from
-    here (the persistent inference kernel keeps no activations); the weight-gradient reductions at the end are plain
-    library GEMMs over the stored activations.  Parameters come in nn.LSTM's own layout (weight_* [4D, D], gates i f g o)."""
+    t2p_gemm, the time loop inside the library (t2p_lstm_train_forward / _backward) when the width allows (a multiple of 4),
+    else step by step from here with the products on ops.matmul, which zero-pads them to t2p_gemm's granules (the persistent
+    inference kernel keeps no activations); the weight-gradient reductions at the end are plain library GEMMs over the stored
+    activations.  Parameters come in nn.LSTM's own layout (weight_* [4D, D], gates i f g o)."""
 
     @staticmethod
     def forward(ctx, tokens, lengths, emb, w_ih, w_hh, b_ih, b_hh, w_ih_r, w_hh_r, b_ih_r, b_hh_r):
@@ -81,9 +82,10 @@ class _LstmTrainFn(torch.autograd.Function):
                     table = ops.gemm(emb_c, wih_k[dr], bias[dr])
                     ops.lstm_train_forward(table, whh_k[dr], tokens, lengths, dr == 1, gates[dr], cs[dr], hs[dr])
                 continue
-            table = ops.gemm(emb_c, wih_k[dr], bias[dr])                                 # [V, 4D] = E W_ih^T + b_ih + b_hh
+            # a width the loops refuse is no multiple of the GEMM's K granule either: matmul pads K to 4 (and N to 8)
+            table = ops.matmul(emb_c, wih_k[dr]) + bias[dr]                              # [V, 4D] = E W_ih^T + b_ih + b_hh
             for s in range(t):
-                pre = ops.gemm(hs[dr, s], whh_k[dr])
+                pre = ops.matmul(hs[dr, s], whh_k[dr])
                 ops.lstm_cell_forward(pre, table, tokens, lengths, s, dr == 1, cs[dr, s], hs[dr, s], gates[dr, s],
                                       cs[dr, s + 1], hs[dr, s + 1])
         if in_library:

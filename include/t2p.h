@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define T2P_ABI_VERSION 32
+#define T2P_ABI_VERSION 33
 #define T2P_DEFAULT_CHUNK_OBJECTS 65000 /* t2p_cell_config.chunk_objects == 0 */
 #define T2P_MAX_CHUNK_OBJECTS 65535     /* 32-bit table offsets / 16-bit local indices: chunk_objects and the largest single
                                            cell may not exceed it (T2P_E_ARG otherwise).  The caller-provided workspace holds
@@ -190,7 +190,10 @@ typedef struct t2p_cell_config {
      * 1-3 edge inputs, judged by max|A_l| + max|B_l|; bit 3: SA output rows split by the dense table kernels; bit 4: GA
      * hidden planes, judged by a norm bound and by their exact maximum; bit 5: rows of the LDS-tiled GEMMs and the kNN edge
      * rows; bit 6: a NaN among the input points / colours - the float-max aggregation of the f16x3 kernels would drop it where
-     * the reference's scatter-max propagates it; bit 7: LOW side - the largest hidden activation or the largest output of an
+     * the reference's scatter-max propagates it - or a NaN / infinity in an object's embedding row as the cell head receives it:
+     * every kNN distance to that object is NaN, so it gets no neighbour and no edge row, and in BOTH precisions the output row
+     * of its cell is NaN (never a finite row computed from the cell's other objects);
+     * bit 7: LOW side - the largest hidden activation or the largest output of an
      * SA level, the largest GA hidden activation, PointNet2 feature (features0 / 1 / 2, each on its own) or kNN edge row is
      * below 2^-7, where the fp16 pieces keep an absolute 2^-25 instead of a relative 2^-22 and a later BatchNorm that rescales
      * would expose the loss).  The tests are conservative: they may
@@ -218,7 +221,12 @@ typedef struct t2p_cell_config {
  *   nbr[l]     uint8 [n_obj][n_cent_l][32]  ball-query neighbours (first cnt valid), cnt[l] uint8 [n_obj][n_cent_l]
  *   sa_out[l]  fp32  [n_obj*n_cent_l][C_l+32] rows = [features C_l | centroid xyz | 0 | 28 columns the call leaves untouched]
  *   features0  fp32  [n_obj][1024]; features1 [n_obj][512]; features2 [n_obj][256]; obj_emb [n_obj][D] (ObjectEncoder output)
- *   knn_idx    int32 [n_obj][knn_k] global object rows (-1 = none) */
+ *   knn_idx    int32 [n_obj][knn_k] global object rows (-1 = none)
+ * The cell head's stages (D = cfg->embed_dim, the padded width the kernels run at; not written by objects_only calls):
+ *   head_in    fp32  [n_obj][D]   F.normalize(obj_emb), the rows the P / Q products and the kNN read
+ *   head_edge  fp32  [n_obj][D]   DynamicEdgeConv's output rows (max or mean over each object's neighbours)
+ *   head_pool  fp32  [n_cells][D] global max / mean pool over each cell's rows
+ *   head_l1    fp32  [n_cells][D] first layer of CellRetrievalNetwork.lin; head_l2: the second, which the final F.normalize reads */
 typedef struct t2p_cell_trace {
     uint8_t* fps_idx[3];
     uint8_t* nbr[3];
@@ -229,6 +237,11 @@ typedef struct t2p_cell_trace {
     float* obj_emb;
     int32_t* knn_idx;
     float* features1;
+    float* head_in;
+    float* head_edge;
+    float* head_pool;
+    float* head_l1;
+    float* head_l2;
 } t2p_cell_trace;
 
 size_t t2p_encode_cells_workspace_bytes(int64_t n_obj, int64_t n_cells, const t2p_cell_config* cfg);

@@ -92,4 +92,4 @@ def test_library_resolves_every_serve_symbol_at_the_headers_version():
         fn = getattr(handle, name)
         assert fn.restype is res and list(fn.argtypes) == args, name
     assert handle.t2p_serve_abi_version() == _lib.SERVE_ABI_VERSION == _lib.SERVE_DEFINES["T2P_SERVE_ABI_VERSION"]
-    assert handle.t2p_abi_version() == _lib.ABI_VERSION == 32
+    assert handle.t2p_abi_version() == _lib.ABI_VERSION == 33

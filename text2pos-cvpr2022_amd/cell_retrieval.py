@@ -123,8 +123,9 @@ class CellRetrievalNetwork(Fp16RangeGuard, PicklableModule):
             return out
         if isinstance(out, tuple):
             emb, tr = out
-            if isinstance(tr, dict) and tr.get("obj_emb") is not None:
-                tr["obj_emb"] = tr["obj_emb"][:, : self.embed_dim].contiguous()
+            for name in ("obj_emb",) + ops.HEAD_TRACE:
+                if isinstance(tr, dict) and tr.get(name) is not None:
+                    tr[name] = tr[name][:, : self.embed_dim].contiguous()
             return emb[:, : self.embed_dim].contiguous(), tr
         return out[:, : self.embed_dim].contiguous()
 

@@ -201,7 +201,7 @@ struct Chunk {
     int trunk_heads() const;
     int object_encoder(const float* center, const float* mean_rgb, int32_t o_lo, const float** emb_out) const;
     int cell_head(const float* emb, int max_cell, float* out) const;
-    int copy_traces(const t2p_cell_trace& tr, int64_t obj0, bool trunk_ran, const float* emb) const;
+    int copy_traces(const t2p_cell_trace& tr, int64_t obj0, int64_t cell0, bool trunk_ran, const float* emb) const;
 };
 
 // FPS + ball query of the three levels, the row lists the SA kernels consume and their balanced object ranges
@@ -447,7 +447,7 @@ int Chunk::cell_head(const float* emb, int max_cell, float* out) const {
     p.n_dst = n;
     p.mean = cfg.variation == 1;  // cell_retrieval.py:50-54: DynamicEdgeConv(aggr="mean") + global_mean_pool
     T2P_TRY(launch_ws(WS_EDGE_KNN, D, D, p, st));
-    T2P_TRY(launch_segmax(ws.x1, D, ws.seg_ptr, (int)nb, ws.pool, cfg.variation == 1, st));
+    T2P_TRY(launch_segmax(ws.x1, D, ws.seg_ptr, (int)nb, ws.pool, cfg.variation == 1, st, ws.knn, cfg.knn_k, gslot(G_INPUT)));
     T2P_TRY(launch_gemm(ws.pool, D, W.lin_w1, W.lin_b1, ws.l1, D, 0, nb, D, D, 1, st));
     T2P_TRY(launch_gemm(ws.l1, D, W.lin_w2, W.lin_b2, ws.l2, D, 0, nb, D, D, 1, st));
     return launch_rownorm(ws.l2, D, nb, D, out, D, 0, st);
@@ -464,9 +464,10 @@ int copy_trace(T* dst, int64_t row0, size_t width, const T* src, int64_t n, hipS
     return 0;
 }
 
-// The stage outputs tr names, into its rows obj0 .. obj0 + n.  trunk_ran: the PointNet++ stages hold this chunk's values;
-// emb: the object encoder's result (nullptr: not run), with which tr->knn_idx goes.
-int Chunk::copy_traces(const t2p_cell_trace& tr, int64_t obj0, bool trunk_ran, const float* emb) const {
+// The stage outputs tr names, into its object rows obj0 .. obj0 + n and its cell rows cell0 .. cell0 + nb.  trunk_ran: the
+// PointNet++ stages hold this chunk's values; emb: the object encoder's result (nullptr: not run), with which tr->knn_idx and
+// the cell head's stages go (not for objects_only calls: the head did not run).
+int Chunk::copy_traces(const t2p_cell_trace& tr, int64_t obj0, int64_t cell0, bool trunk_ran, const float* emb) const {
     for (int l = 0; trunk_ran && l < 3; l++) {
         T2P_TRY(copy_trace(tr.fps_idx[l], obj0, g.nc[l], ws.gt.fps_idx[l], n, st));
         T2P_TRY(copy_trace(tr.nbr[l], obj0, (size_t)g.nc[l] * 32, ws.gt.nbr[l], n, st));
@@ -496,6 +497,14 @@ int Chunk::copy_traces(const t2p_cell_trace& tr, int64_t obj0, bool trunk_ran, c
         T2P_TRY(copy_trace(tr.obj_emb, obj0, cfg.embed_dim, emb, n, st));
         // knn indices are chunk-local object rows; tests use a single chunk or add the chunk offset themselves
         T2P_TRY(copy_trace(tr.knn_idx, obj0, cfg.knn_k, ws.knn, n, st));
+    }
+    if (emb != nullptr && !cfg.objects_only) {
+        const size_t D = cfg.embed_dim;
+        T2P_TRY(copy_trace(tr.head_in, obj0, D, ws.embn, n, st));
+        T2P_TRY(copy_trace(tr.head_edge, obj0, D, ws.x1, n, st));
+        T2P_TRY(copy_trace(tr.head_pool, cell0, D, ws.pool, nb, st));
+        T2P_TRY(copy_trace(tr.head_l1, cell0, D, ws.l1, nb, st));
+        T2P_TRY(copy_trace(tr.head_l2, cell0, D, ws.l2, nb, st));
     }
     return 0;
 }
@@ -638,7 +647,7 @@ int t2p_encode_cells(const float* xyz, const float* rgb, const float* center, co
         T2P_TRY(c.object_encoder(center + (int64_t)o_lo * 3, mean_rgb + (int64_t)o_lo * 3, o_lo, &emb));
         if (!cfg->objects_only) T2P_TRY(c.cell_head(emb, max_cell, out + c0 * cfg->embed_dim));
         T2P_TRY(c.guard_check());
-        T2P_TRY(c.copy_traces(tr, o_lo, run_pointnet, emb));
+        T2P_TRY(c.copy_traces(tr, o_lo, c0, run_pointnet, emb));
         c0 = c1;
     }
     return 0;
@@ -693,7 +702,7 @@ int t2p_pointnet2_forward(const float* xyz, const float* rgb, int64_t n_obj, con
     T2P_TRY(launch_one_cell_index(n_obj, ws.seg_ptr, ws.first, st, c.guard));
     T2P_TRY(c.trunk(xyz, rgb, false));
     T2P_TRY(c.guard_check());
-    T2P_TRY(c.copy_traces(tr, 0, true, nullptr));
+    T2P_TRY(c.copy_traces(tr, 0, 0, true, nullptr));
     if (heads)   // (on the workspace's copy of features2: the caller need not ask for it)
         T2P_TRY(launch_classifier_heads(ws.f2, head_w, head_b, n_obj, n_classes, n_colors, class_pred, color_pred, st));
     return 0;

@@ -45,12 +45,25 @@ __global__ __launch_bounds__(256) void k_gather_rownorm(const float* __restrict_
     for (int i = lane; i < dim; i += 64) y[i] = x[i] / den;
 }
 
+// first_nbr (the cell head; nullptr otherwise): knn_idx [rows][knn_k] of k_knn.  An object whose embedding row holds a NaN or an
+// infinity has a NaN distance to every object, itself included: k_knn lists no neighbour for it and no other object lists it, the
+// edge kernel leaves its row at 0 and the object would drop out of its cell without a trace.  Its first slot is the only -1 a
+// first slot can hold (an ordinary object finds itself at distance 0), so the pool reads it: such a cell's pooled row is NaN -
+// as the reference's scatter would have it - which lin and the final F.normalize carry to the output, and the NaN pattern goes
+// to the guard's input slot (bit 6 of the f16x3 path's word).
 __global__ void k_segpool(const float* __restrict__ in, int dim, const int32_t* __restrict__ seg_ptr, int n_seg,
-                          float* __restrict__ out, int mean) {
+                          float* __restrict__ out, int mean, const int32_t* __restrict__ first_nbr, int knn_k,
+                          uint32_t* guard_input) {
     int s = blockIdx.x;
     int lo = seg_ptr[s], hi = seg_ptr[s + 1];
+    bool lost = false;
+    if (first_nbr != nullptr)
+        for (int r = lo; r < hi; r++) lost |= first_nbr[(int64_t)r * knn_k] < 0;
+    if (lost && guard_input != nullptr && threadIdx.x == 0) atomicMax(guard_input, 0x7fc00000u);
     for (int c = threadIdx.x; c < dim; c += blockDim.x) {
-        if (mean) {
+        if (lost) {
+            out[(int64_t)s * dim + c] = __builtin_nanf("");
+        } else if (mean) {
             float acc = 0.f;
             for (int r = lo; r < hi; r++) acc += in[(int64_t)r * dim + c];
             out[(int64_t)s * dim + c] = hi > lo ? acc / (float)(hi - lo) : 0.f;
@@ -785,10 +798,11 @@ int launch_gather_rownorm(const float* table, const int32_t* idx, int64_t n_rows
     return 0;
 }
 
-int launch_segmax(const float* in, int dim, const int32_t* seg_ptr, int n_seg, float* out, int mean, hipStream_t st) {
+int launch_segmax(const float* in, int dim, const int32_t* seg_ptr, int n_seg, float* out, int mean, hipStream_t st,
+                  const int32_t* first_nbr, int knn_k, uint32_t* guard_input) {
     if (n_seg == 0) return 0;
     ProfScope ps_("segpool", st);
-    hipLaunchKernelGGL(k_segpool, dim3(n_seg), dim3(256), 0, st, in, dim, seg_ptr, n_seg, out, mean);
+    hipLaunchKernelGGL(k_segpool, dim3(n_seg), dim3(256), 0, st, in, dim, seg_ptr, n_seg, out, mean, first_nbr, knn_k, guard_input);
     T2P_CHECK_LAUNCH("segpool");
     return 0;
 }

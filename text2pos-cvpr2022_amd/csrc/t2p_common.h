@@ -273,8 +273,9 @@ int launch_rownorm(const float* in, int ld_in, int64_t n_rows, int dim, float* o
                    hipStream_t st);
 int launch_gather_rownorm(const float* table, const int32_t* idx, int64_t n_rows, int dim, float* out, int ld_out,
                           int col0, hipStream_t st);
+// first_nbr: k_knn's table of the same rows (an object without a first neighbour holds a NaN: its cell's pooled row is NaN)
 int launch_segmax(const float* in, int dim, const int32_t* seg_ptr, int n_seg, float* out, int mean,
-                  hipStream_t st);
+                  hipStream_t st, const int32_t* first_nbr = nullptr, int knn_k = 0, uint32_t* guard_input = nullptr);
 int launch_knn(const float* x, int dim, const int32_t* seg_ptr, int n_seg, int max_seg_rows, int k,
                int32_t* out_idx, hipStream_t st);
 // 3 -> 64 -> D MLP (BN folded, ReLU after both layers) + F.normalize, written into out[row*ld_out + col0 ...]

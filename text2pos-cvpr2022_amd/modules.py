@@ -190,7 +190,7 @@ class Fp16RangeGuard:
         return code
 
     _GUARD_BITS = ("bits 0-2 = SA level 1-3 edge inputs, 3 = SA output rows, 4 = GA hidden planes, 5 = GEMM rows (PointNet2 "
-                   "features, kNN edge rows) past fp16's largest value; 6 = NaN among the input points / colours; 7 = a stage's "
+                   "features, kNN edge rows) past fp16's largest value; 6 = NaN among the input points / colours or in an object's embedding row; 7 = a stage's "
                    "activations too SMALL for the fp16 pieces (SA levels, GA hidden planes, PointNet2 features, kNN edge rows: "
                    "largest magnitude below 2^-7, their low parts would underflow)")
 

@@ -647,6 +647,9 @@ def make_cell_weights(packed: Dict[str, object]) -> L.CellWeights:
     return w
 
 
+HEAD_TRACE = ("head_in", "head_edge", "head_pool", "head_l1", "head_l2")   # t2p_cell_trace: the cell head's stage outputs
+
+
 def encode_cells(xyz, rgb, center, mean_rgb, cell_ptr_host: np.ndarray, cell_ptr_dev, weights: L.CellWeights,
                  cfg: L.CellConfig, want_trace=False, ws_tag: str = "encode_cells"):
     """Cell branch on packed, device-resident inputs.  Returns out [n_cells, D] (and a dict of stage outputs when
@@ -682,9 +685,10 @@ def encode_cells(xyz, rgb, center, mean_rgb, cell_ptr_host: np.ndarray, cell_ptr
         tr.obj_emb = obj_emb.data_ptr()
     elif want_trace:
         # want_trace: True = every stage output, or an iterable of names (the full set is ~130 KB per object)
+        # (True keeps its meaning: the stages up to the kNN graph; the cell head's stages HEAD_TRACE are asked for by name)
         names = set(("fps_idx", "nbr", "cnt", "sa_out", "features0", "features1", "features2", "obj_emb", "knn_idx")
                     if want_trace is True else want_trace)
-        unknown = names - {"fps_idx", "nbr", "cnt", "sa_out", "features0", "features1", "features2", "obj_emb", "knn_idx"}
+        unknown = names - {"fps_idx", "nbr", "cnt", "sa_out", "features0", "features1", "features2", "obj_emb", "knn_idx", *HEAD_TRACE}
         if unknown:
             raise RuntimeError(f"encode_cells: unknown trace outputs {sorted(unknown)}")
         tr = L.CellTrace()
@@ -695,7 +699,10 @@ def encode_cells(xyz, rgb, center, mean_rgb, cell_ptr_host: np.ndarray, cell_ptr
             setattr(tr, name, arr[name])
         flat = {"features0": ((n_obj, 1024), torch.float32), "features1": ((n_obj, 512), torch.float32),
                 "features2": ((n_obj, 256), torch.float32), "obj_emb": ((n_obj, D), torch.float32),
-                "knn_idx": ((n_obj, cfg.knn_k), torch.int32)}
+                "knn_idx": ((n_obj, cfg.knn_k), torch.int32),
+                "head_in": ((n_obj, D), torch.float32), "head_edge": ((n_obj, D), torch.float32),
+                "head_pool": ((n_cells, D), torch.float32), "head_l1": ((n_cells, D), torch.float32),
+                "head_l2": ((n_cells, D), torch.float32)}
         for name, (shape, dt) in flat.items():
             if name in names:
                 trace[name] = torch.empty(shape, dtype=dt, device=dev)

@@ -216,6 +216,23 @@ def head_forward(md, B, M, N, D, alpha, iters, dtype):
     return out
 
 
+def head_scores_fma(md, B, M, N, D, alpha):
+    """Z0 [B, M + 1, N + 1] with the kernels' own bits (transport_scores of csrc/match_common.h): a = fma(x_k, y_k, a) over k in
+    order in float64, times 1 / sqrt(D) once, alpha in the dustbin row and column.  The product of two fp32 values has 48
+    significant bits and is exact in float64, so `a + x_k * y_k` rounds once, as the fma does: no tolerance is needed."""
+    md = np.asarray(md)
+    assert md.dtype == F32
+    z0 = np.full((B, M + 1, N + 1), np.float64(F32(alpha)))
+    for b in range(B):
+        m0 = md[set_row(0, b, B, M, N): set_row(0, b, B, M, N) + M].astype(np.float64)
+        m1 = md[set_row(1, b, B, M, N): set_row(1, b, B, M, N) + N].astype(np.float64)
+        a = np.zeros((M, N))
+        for k in range(D):
+            a = a + m0[:, k, None] * m1[None, :, k]
+        z0[b, :M, :N] = a * (1.0 / np.sqrt(np.float64(D)))
+    return z0
+
+
 def head_couplings(md, B, M, N, D, alpha, iters, dtype=np.float64):
     """P [B, M + 1, N + 1] in `dtype`."""
     p = []

@@ -106,6 +106,36 @@ def test_head_backward_kernel(shape, iters):
     assert torch.equal(d_md, a_md) and torch.equal(d_bin, a_bin)
 
 
+@pytest.mark.parametrize("iters", [1, 50])
+@pytest.mark.parametrize("shape", FB.ATTN_SHAPES)
+def test_head_backward_reruns_the_forward_bit_for_bit(shape, iters):
+    """The backward's forward pass is the forward kernel's (csrc/match_common.h: one statement of both).  Its last iterate u_T | v_T,
+    read from the workspace at (iters - 1) (M + N + 2) doubles into each sample's block, gives the forward's P: fp32(exp(Z0 + u_T +
+    v_T - norm)) with Z0 = FB.head_scores_fma (the kernel's own float64 chain, exact on the host), the additions in the kernel's order
+    and log / exp of float64 taken on the device.  No tolerance.  The workspace starts as NaN and ends with none: every iterate of every
+    sample is stored."""
+    from text2pos_amd import _lib as L, ops
+    B, M, N, D = shape
+    md, _ = _head_case(shape, iters)
+    x = _t(md)
+    P = ops.match_head(x, B, M, N, 1.0, iters)["P"]
+    dP = torch.ones_like(P)
+    d_md, d_bin = _nan_like(md.shape), _nan_like((B,), torch.float64)
+    need = L.lib().t2p_match_head_backward_workspace_bytes(B, M, N, iters)
+    assert need == B * iters * (M + N + 2) * 8
+    ws = _nan_like((need // 8,), torch.float64)
+    L.check(L.lib().t2p_match_head_backward(ops._ptr(x), ops._ptr(dP), B, M, N, D, 1.0, iters, ops._ptr(d_md), ops._ptr(d_bin),
+                                            ops._ptr(ws), need, ops._stream(_dev())), "t2p_match_head_backward")
+    assert not torch.isnan(ws).any()
+    last = ws.reshape(B, iters, M + N + 2)[:, -1]
+    u, v = last[:, :M + 1], last[:, M + 1:]
+    norm = -torch.log(torch.tensor(float(M + N), dtype=torch.float64, device=_dev()))
+    z = _t(FB.head_scores_fma(md, B, M, N, D, 1.0)) + u[:, :, None] + v[:, None, :] - norm
+    again = torch.exp(z).to(torch.float32)
+    print(f"head backward's forward {shape} iters={iters}: {int((again != P).sum())} of {P.numel()} couplings differ from t2p_match_head's")
+    assert torch.equal(again, P)
+
+
 @pytest.mark.parametrize("shape,dup", [((3, 5, 4), True), ((1, 2, 2), False), ((2, 64, 64), False)])
 def test_matching_loss_backward_kernel(shape, dup):
     from text2pos_amd import ops

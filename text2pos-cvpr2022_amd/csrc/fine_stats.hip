@@ -25,18 +25,6 @@ constexpr int kStatCols = 5;             // recall, precision, pose_mid, pose_me
 constexpr int kStatMaxBatch = 1024;      // the LDS rows of the batch reduction: 1024 x 5 doubles = 40 KiB (T2P_FINE_STATS_MAX_BATCH)
 constexpr int kStatMaxTokens = 63;       // t2p_match_attention's limit: a wavefront's lanes cover a set
 
-__device__ __forceinline__ int wave_sum_i(int x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-    return x;
-}
-
-__device__ __forceinline__ double wave_sum_d(double x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-    return x;
-}
-
 __global__ __launch_bounds__(kStatThreads) void k_fine_step_stats(
     const int64_t* __restrict__ matches0, const int64_t* __restrict__ matches1, const float* __restrict__ offsets,
     const int32_t* __restrict__ pose_idx, const int32_t* __restrict__ gt_hint, const double* __restrict__ pose_xy,
@@ -82,14 +70,14 @@ __global__ __launch_bounds__(kStatThreads) void k_fine_step_stats(
                 oy = cy + (double)o[1];
             }
         }
-        pair = wave_sum_i(pair);
-        found = wave_sum_i(found);
-        assigned = wave_sum_i(assigned);
-        right = wave_sum_i(right);
-        cx = wave_sum_d(cx);
-        cy = wave_sum_d(cy);
-        ox = wave_sum_d(ox);
-        oy = wave_sum_d(oy);
+        pair = wave_sum(pair);
+        found = wave_sum(found);
+        assigned = wave_sum(assigned);
+        right = wave_sum(right);
+        cx = wave_sum(cx);
+        cy = wave_sum(cy);
+        ox = wave_sum(ox);
+        oy = wave_sum(oy);
         if (lane == 0) {
             double r[kStatCols];
             if (ok) {

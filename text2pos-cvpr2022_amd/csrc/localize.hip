@@ -52,18 +52,6 @@ __global__ __launch_bounds__(256) void k_gather_tokens(const f32x4* __restrict__
     }
 }
 
-__device__ __forceinline__ int loc_wave_sum_i(int x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-    return x;
-}
-
-__device__ __forceinline__ double loc_wave_sum_d(double x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-    return x;
-}
-
 __global__ __launch_bounds__(kLocThreads) void k_localize_poses(
     const int64_t* __restrict__ matches0, const float* __restrict__ offsets, const int32_t* __restrict__ cell_row, int K, int M, int N,
     const double* __restrict__ center_xy, const double* __restrict__ bbox_xy, const double* __restrict__ cell_size, int64_t n_cells,
@@ -98,11 +86,11 @@ __global__ __launch_bounds__(kLocThreads) void k_localize_poses(
             ox = cx + (double)o[0];
             oy = cy + (double)o[1];
         }
-        assigned = loc_wave_sum_i(assigned);
-        cx = loc_wave_sum_d(cx);
-        cy = loc_wave_sum_d(cy);
-        ox = loc_wave_sum_d(ox);
-        oy = loc_wave_sum_d(oy);
+        assigned = wave_sum(assigned);
+        cx = wave_sum(cx);
+        cy = wave_sum(cy);
+        ox = wave_sum(ox);
+        oy = wave_sum(oy);
         if (lane == 0) {
             double r[8];
             if (ok) {

@@ -12,16 +12,14 @@
 //   CAT[:, D:] = MSG Wm;   H = relu(CAT W1) (BatchNorm folded);   X += H W2 (residual in the GEMM epilogue)
 // X lives in the left half of CAT [T][2D], so the concat of AttentionalPropagation is free.  The optimal-transport
 // part (score matrix, 50 log-Sinkhorn iterations on (M+1) x (N+1), exp, mutual nearest neighbours, threshold) and the
-// offset MLP run in one wavefront per sample with the matrix in LDS (k_match_final).  fp32 throughout, except the optimal-transport
-// part, which is float64 and rounds P once.
-#include "t2p_common.h"
+// offset MLP run in one wavefront per sample with the matrix in LDS (k_match_final).  The optimal-transport part is stated once, in
+// match_common.h, for this kernel and the training path's (match_train.hip): float64, P rounded once.  Everything else is fp32.
+#include "match_common.h"
 
 #include "../../include/t2p.h"
 
 namespace t2p {
 namespace {
-
-constexpr int kHeads = 4;
 
 __global__ void k_concat(const float* __restrict__ d0, const float* __restrict__ d1, int64_t B, int M, int N, int D,
                          float* __restrict__ cat) {
@@ -58,6 +56,7 @@ __global__ __launch_bounds__(256) void k_attn(const float* __restrict__ qkv, int
         const bool side0 = t < M;                       // token of set 0 (objects)
         const bool from0 = cross ? !side0 : side0;      // source set
         const int s0 = from0 ? 0 : M, ns = from0 ? M : N;
+        // the statements of attention_row / attention_values (match_common.h), on the strided LDS rows
         const float* q = rows + t * LD + h;
         float* s = sc + item * S;
         float mx = -INFINITY;
@@ -91,11 +90,7 @@ __global__ __launch_bounds__(256) void k_attn(const float* __restrict__ qkv, int
     }
 }
 
-// One wavefront per sample: score matrix, log-space Sinkhorn with dustbins, exp, mutual NN + threshold, offsets.
-// The scores, u, v and the log couplings are float64, as in k_head_sets (match_train.hip), and P is rounded to fp32 once: |u| and
-// |v| reach 5 to 8, where one fp32 rounding is 5e-7 to 1e-6 of log P, and a fp32 recurrence left the dustbin couplings (P of 4 to 6)
-// 2.5e-6 from the float64 matcher - four times the fp32 oracle's own distance (docs/notebook.md, "The fine matcher's forward kernels
-// against float64").  The offset MLP stays fp32.
+// One wavefront per sample: the transport head of match_common.h on the sample-major rows, then the offset MLP (fp32).
 __global__ __launch_bounds__(64) void k_match_final(const float* __restrict__ md /*[B T][D] final_proj outputs*/,
                                                     const float* __restrict__ d1 /*[B N][D] hint encodings*/,
                                                     int M, int N, int D, float alpha_f, int iters, float thresh,
@@ -106,95 +101,13 @@ __global__ __launch_bounds__(64) void k_match_final(const float* __restrict__ md
                                                     float* __restrict__ ms1, float* __restrict__ offsets) {
     extern __shared__ double smd[];
     const int lane = threadIdx.x;
-    const int T = M + N, M1 = M + 1, N1 = N + 1;
-    double* Z = smd;                 // [M1][N1]
-    double* u = Z + M1 * N1;         // [M1]
-    double* v = u + M1;              // [N1]
-    double* rmax = v + N1;           // [M] row max (inner), [N] col max
-    int* ridx = (int*)(rmax + M + N);  // [M] + [N]
-    float* hid = (float*)(ridx + M + N);  // [D/2]
+    const HeadLds s(smd, M, N, true);
+    float* hid = (float*)s.end;      // [D/2]
     const int64_t b = blockIdx.x;
-    const float* m0 = md + b * T * (int64_t)D;
-    const float* m1 = m0 + M * (int64_t)D;
-    const double alpha = (double)alpha_f;
-    const double inv = 1.0 / sqrt((double)D);
-    for (int e = lane; e < M1 * N1; e += 64) {
-        const int i = e / N1, j = e % N1;
-        double a = alpha;
-        if (i < M && j < N) {
-            a = 0.0;
-            const float* x = m0 + i * (int64_t)D;
-            const float* y = m1 + j * (int64_t)D;
-            for (int k = 0; k < D; k++) a = fma((double)x[k], (double)y[k], a);
-            a *= inv;
-        }
-        Z[e] = a;
-    }
-    const double norm = -log((double)(M + N));
-    const double lmu_bin = log((double)N) + norm, lnu_bin = log((double)M) + norm;
-    if (lane < M1) u[lane] = 0.0;
-    if (lane < N1) v[lane] = 0.0;
-    __syncthreads();
-    for (int it = 0; it < iters; it++) {
-        if (lane < M1) {  // u = log_mu - logsumexp_j(Z + v)
-            double mx = -INFINITY;
-            for (int j = 0; j < N1; j++) mx = fmax(mx, Z[lane * N1 + j] + v[j]);
-            double s = 0.0;
-            for (int j = 0; j < N1; j++) s += exp(Z[lane * N1 + j] + v[j] - mx);
-            u[lane] = (lane < M ? norm : lmu_bin) - (mx + log(s));
-        }
-        __syncthreads();
-        if (lane < N1) {  // v = log_nu - logsumexp_i(Z + u)
-            double mx = -INFINITY;
-            for (int i = 0; i < M1; i++) mx = fmax(mx, Z[i * N1 + lane] + u[i]);
-            double s = 0.0;
-            for (int i = 0; i < M1; i++) s += exp(Z[i * N1 + lane] + u[i] - mx);
-            v[lane] = (lane < N ? norm : lnu_bin) - (mx + log(s));
-        }
-        __syncthreads();
-    }
-    for (int e = lane; e < M1 * N1; e += 64) {
-        const int i = e / N1, j = e % N1;
-        const double z = Z[e] + u[i] + v[j] - norm;
-        Z[e] = z;
-        P[b * M1 * N1 + e] = (float)exp(z);
-    }
-    __syncthreads();
-    // maxima over the inner (non-dustbin) block; ties -> first index
-    if (lane < M) {
-        double mx = -INFINITY;
-        int bi = 0;
-        for (int j = 0; j < N; j++)
-            if (Z[lane * N1 + j] > mx) { mx = Z[lane * N1 + j]; bi = j; }
-        rmax[lane] = mx;
-        ridx[lane] = bi;
-    }
-    if (lane < N) {
-        double mx = -INFINITY;
-        int bi = 0;
-        for (int i = 0; i < M; i++)
-            if (Z[i * N1 + lane] > mx) { mx = Z[i * N1 + lane]; bi = i; }
-        rmax[M + lane] = mx;
-        ridx[M + lane] = bi;
-    }
-    __syncthreads();
-    if (lane < M) {
-        const int j = ridx[lane];
-        const bool mutual = ridx[M + j] == lane;
-        const float s = mutual ? (float)exp(rmax[lane]) : 0.f;
-        ms0[b * M + lane] = s;
-        matches0[b * M + lane] = (mutual && s > thresh) ? j : -1;
-    }
-    if (lane < N) {
-        const int i = ridx[M + lane];
-        const bool mutual1 = ridx[i] == lane;
-        const bool mutual0 = ridx[M + ridx[i]] == i;                       // mutual0[i]
-        const float s0 = mutual0 ? (float)exp(rmax[i]) : 0.f;             // mscores0[i]
-        const float s = mutual1 ? s0 : 0.f;
-        ms1[b * N + lane] = s;
-        const bool valid0 = mutual0 && s0 > thresh;
-        matches1[b * N + lane] = (mutual1 && valid0) ? i : -1;
-    }
+    const float* m0 = md + b * (M + N) * (int64_t)D;
+    transport_scores(m0, m0 + M * (int64_t)D, M, N, D, (double)alpha_f, s.Z);
+    const LogMarginals lm = sinkhorn_iterate(s.Z, s.u, s.v, M, N, iters, [](int, int, bool, double) {});
+    transport_decide(s, M, N, lm.norm, thresh, P + b * (M + 1) * (N + 1), matches0 + b * M, matches1 + b * N, ms0 + b * M, ms1 + b * N);
     // offsets = Linear(D/2 -> 2)(relu(Linear(D -> D/2)(hint)))
     const int H = D / 2;
     for (int j = 0; j < N; j++) {
@@ -256,11 +169,7 @@ int t2p_match(const float* desc0, const float* desc1, int64_t batch, int32_t n_o
     hipStream_t st = (hipStream_t)stream;
     const int M = n_obj, N = n_hints, D = embed_dim;
     T2P_CHECK_ARG(desc0 && desc1 && w && P && matches0 && matches1 && mscores0 && mscores1 && offsets, "match: NULL argument");
-    T2P_CHECK_ARG(batch >= 0 && M >= 1 && N >= 1 && M < 64 && N < 64, "match: need 1 <= n_obj, n_hints <= 63 (got %d, %d)", M, N);
-    if (D != 64 && D != 128 && D != 256) {
-        set_error("match: embed_dim=%d not built (64, 128, 256)", D);
-        return T2P_E_UNSUPPORTED;
-    }
+    T2P_TRY(check_sizes("match", batch, M, N, D, false));
     T2P_CHECK_ARG(w->n_layers >= 0 && w->n_layers <= 64 && (w->n_layers == 0 || w->cross != nullptr), "match: bad layer list");
     T2P_CHECK_ARG(sinkhorn_iters >= 0, "match: sinkhorn_iters < 0");
     if (batch == 0) return 0;
@@ -312,9 +221,7 @@ int t2p_match(const float* desc0, const float* desc1, int64_t batch, int32_t n_o
     }
     T2P_TRY(launch_dense(ws.cat, 2 * D, DenseW{w->wf, w->wf_x3, w->scale_f}, w->bf, ws.md, D, 0, rows, D, D, 0, st));
     {
-        // float64: Z, u, v, the maxima; then the winners' indices and the offset MLP's hidden row (35 KiB at 63 + 63 tokens)
-        const size_t lds = ((size_t)(M + 1) * (N + 1) + (M + 1) + (N + 1) + (M + N)) * sizeof(double) +
-                           ((size_t)(M + N) + D / 2 + 8) * sizeof(float);
+        const size_t lds = head_lds_bytes(M, N, true) + ((size_t)D / 2 + 8) * sizeof(float);   // the head, then the offset MLP's hidden row
         ProfScope ps_("match_final", st);
         hipLaunchKernelGGL(k_match_final, dim3((unsigned)batch), dim3(64), lds, st, ws.md, desc1, M, N, D, w->bin_score,
                            sinkhorn_iters, match_threshold, w->wo1, w->bo1, w->wo2, w->bo2, P, matches0, matches1,

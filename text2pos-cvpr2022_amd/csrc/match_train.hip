@@ -11,7 +11,9 @@
 //   [0, B M)            object tokens, sample-major (row b M + i)
 //   [B M, B (M + N))    hint tokens, sample-major   (row B M + b N + j)
 // and a BatchNorm call is one contiguous row segment (train_ops.bn_relu_train).  match.hip's k_attn / k_match_final address
-// sample-major rows [B (M + N)] and fold BatchNorm; the kernels here address the two sets.
+// sample-major rows [B (M + N)] and fold BatchNorm; the kernels here address the two sets.  What the two files compute alike - the
+// attention's softmax row, the transport head - is one statement in match_common.h; the kernels here and there differ in where
+// their rows lie, in what they keep (the backward's iterates) and in what follows.
 //
 // Everything is small and latency-bound (a sample is at most 63 + 63 tokens): the kernels aim at being exact, deterministic (no
 // atomics, fixed reduction orders) and in bounds at every 1 <= M, N <= 63, D in {64, 128, 256}.
@@ -35,19 +37,12 @@
 //     caller's workspace (T (M + N + 2) doubles per sample; a lane reads back only what it wrote itself), then walks the unrolled
 //     iterations backwards with Z0 and its gradient both in LDS (2 x 32 KiB + vectors at 63 + 63 tokens: the kernel's dynamic-LDS
 //     limit is raised, gfx950 has 160 KiB per CU).
-#include "t2p_common.h"
+#include "match_common.h"
 
 #include "../../include/t2p.h"
 
 namespace t2p {
 namespace {
-
-constexpr int kHeads = 4;
-constexpr int kMaxTokens = 63;   // per set: a wavefront's lanes cover a set plus its dustbin
-
-__device__ __forceinline__ int64_t set_row(int set, int64_t b, int64_t B, int M, int N) {
-    return set == 0 ? b * M : B * M + b * N;   // first row of sample b's tokens of that set
-}
 
 // grid = B * 2 * heads, 64 threads.  qkv rows [B (M + N)][3D] (q | k | v), channel c of a projection = d * heads + h.
 template <int DH>
@@ -80,33 +75,11 @@ __global__ __launch_bounds__(64) void k_attn_sets(const float* __restrict__ qkv,
 #pragma unroll
         for (int d = 0; d < DH; d++) q[d] = r[d * kHeads];
     }
-    const float scale = 1.0f / sqrtf((float)DH);
     float* s = sc + t * LS;
-    float mx = -INFINITY;
-    for (int m = 0; m < ns; m++) {
-        const float* k = K + m * DH;                         // (every lane reads the same address: a broadcast)
-        float a = 0.f;
-#pragma unroll
-        for (int d = 0; d < DH; d++) a = fmaf(q[d], k[d], a);
-        a *= scale;
-        s[m] = a;
-        mx = fmaxf(mx, a);
-    }
-    float den = 0.f;
-    for (int m = 0; m < ns; m++) {
-        const float e = expf(s[m] - mx);
-        s[m] = e;
-        den += e;
-    }
+    float den;
+    attention_row<DH>(q, K, DH, ns, 1.0f / sqrtf((float)DH), s, den);   // (every lane reads the same key address: a broadcast)
     float acc[DH];
-#pragma unroll
-    for (int d = 0; d < DH; d++) acc[d] = 0.f;
-    for (int m = 0; m < ns; m++) {
-        const float p = s[m] / den;
-        const float* v = V + m * DH;
-#pragma unroll
-        for (int d = 0; d < DH; d++) acc[d] = fmaf(p, v[d], acc[d]);
-    }
+    attention_values<DH>(s, den, V, DH, ns, acc);
     float* o = msg + (t0 + t) * (int64_t)D + h;
 #pragma unroll
     for (int d = 0; d < DH; d++) o[d * kHeads] = acc[d];
@@ -117,93 +90,11 @@ __global__ __launch_bounds__(64) void k_head_sets(const float* __restrict__ md, 
                                                   int iters, float thresh, float* __restrict__ P, int64_t* __restrict__ matches0,
                                                   int64_t* __restrict__ matches1, float* __restrict__ ms0, float* __restrict__ ms1) {
     extern __shared__ double smd[];
-    const int lane = threadIdx.x;
-    const int M1 = M + 1, N1 = N + 1;
-    double* Z = smd;                 // [M1][N1]
-    double* u = Z + M1 * N1;         // [M1]
-    double* v = u + M1;              // [N1]
-    double* rmax = v + N1;           // [M] row maxima of the inner block, [N] column maxima
-    int* ridx = (int*)(rmax + M + N);   // [M] + [N]
+    const HeadLds s(smd, M, N, true);
     const int64_t b = blockIdx.x;
-    const float* m0 = md + set_row(0, b, B, M, N) * D;
-    const float* m1 = md + set_row(1, b, B, M, N) * D;
-    const double alpha = (double)alpha_f;
-    const double inv = 1.0 / sqrt((double)D);
-    for (int e = lane; e < M1 * N1; e += 64) {
-        const int i = e / N1, j = e % N1;
-        double a = alpha;
-        if (i < M && j < N) {
-            a = 0.0;
-            const float* x = m0 + i * (int64_t)D;
-            const float* y = m1 + j * (int64_t)D;
-            for (int k = 0; k < D; k++) a = fma((double)x[k], (double)y[k], a);
-            a *= inv;
-        }
-        Z[e] = a;
-    }
-    const double norm = -log((double)(M + N));
-    const double lmu_bin = log((double)N) + norm, lnu_bin = log((double)M) + norm;
-    if (lane < M1) u[lane] = 0.0;
-    if (lane < N1) v[lane] = 0.0;
-    __syncthreads();
-    for (int it = 0; it < iters; it++) {
-        if (lane < M1) {  // u = log_mu - logsumexp_j(Z + v)
-            double mx = -INFINITY;
-            for (int j = 0; j < N1; j++) mx = fmax(mx, Z[lane * N1 + j] + v[j]);
-            double s = 0.0;
-            for (int j = 0; j < N1; j++) s += exp(Z[lane * N1 + j] + v[j] - mx);
-            u[lane] = (lane < M ? norm : lmu_bin) - (mx + log(s));
-        }
-        __syncthreads();
-        if (lane < N1) {  // v = log_nu - logsumexp_i(Z + u)
-            double mx = -INFINITY;
-            for (int i = 0; i < M1; i++) mx = fmax(mx, Z[i * N1 + lane] + u[i]);
-            double s = 0.0;
-            for (int i = 0; i < M1; i++) s += exp(Z[i * N1 + lane] + u[i] - mx);
-            v[lane] = (lane < N ? norm : lnu_bin) - (mx + log(s));
-        }
-        __syncthreads();
-    }
-    for (int e = lane; e < M1 * N1; e += 64) {
-        const int i = e / N1, j = e % N1;
-        const double z = Z[e] + u[i] + v[j] - norm;
-        Z[e] = z;
-        P[b * M1 * N1 + e] = (float)exp(z);
-    }
-    __syncthreads();
-    // maxima over the inner (non-dustbin) block; ties -> first index
-    if (lane < M) {
-        double mx = -INFINITY;
-        int bi = 0;
-        for (int j = 0; j < N; j++)
-            if (Z[lane * N1 + j] > mx) { mx = Z[lane * N1 + j]; bi = j; }
-        rmax[lane] = mx;
-        ridx[lane] = bi;
-    }
-    if (lane < N) {
-        double mx = -INFINITY;
-        int bi = 0;
-        for (int i = 0; i < M; i++)
-            if (Z[i * N1 + lane] > mx) { mx = Z[i * N1 + lane]; bi = i; }
-        rmax[M + lane] = mx;
-        ridx[M + lane] = bi;
-    }
-    __syncthreads();
-    if (lane < M) {
-        const int j = ridx[lane];
-        const bool mutual = ridx[M + j] == lane;
-        const float s = mutual ? (float)exp(rmax[lane]) : 0.f;
-        ms0[b * M + lane] = s;
-        matches0[b * M + lane] = (mutual && s > thresh) ? j : -1;
-    }
-    if (lane < N) {
-        const int i = ridx[M + lane];
-        const bool mutual1 = ridx[i] == lane;
-        const bool mutual0 = ridx[M + ridx[i]] == i;                       // mutual0[i]
-        const float s0 = mutual0 ? (float)exp(rmax[i]) : 0.f;             // mscores0[i]
-        ms1[b * N + lane] = mutual1 ? s0 : 0.f;
-        matches1[b * N + lane] = (mutual1 && mutual0 && s0 > thresh) ? i : -1;
-    }
+    transport_scores(md + set_row(0, b, B, M, N) * D, md + set_row(1, b, B, M, N) * D, M, N, D, (double)alpha_f, s.Z);
+    const LogMarginals lm = sinkhorn_iterate(s.Z, s.u, s.v, M, N, iters, [](int, int, bool, double) {});
+    transport_decide(s, M, N, lm.norm, thresh, P + b * (M + 1) * (N + 1), matches0 + b * M, matches1 + b * N, ms0 + b * M, ms1 + b * N);
 }
 
 constexpr int kLossThreads = 256;
@@ -211,8 +102,7 @@ constexpr int kLossThreads = 256;
 // Sum of one value per thread of the workgroup, the same tree every time: butterflies inside a wavefront, then the wavefronts'
 // sums in order.  Every thread of the workgroup must call it; all of them receive the sum.
 __device__ __forceinline__ double block_sum(double x, double* part /*[kLossThreads / 64]*/) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
+    x = wave_sum(x);
     __syncthreads();                                         // (part may still be read from the previous call)
     if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = x;
     __syncthreads();
@@ -242,8 +132,7 @@ __global__ __launch_bounds__(kLossThreads) void k_matching_loss(const float* __r
                 else
                     s -= log((double)P[(b * M1 + i) * (int64_t)N1 + j]);
             }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+        s = wave_sum(s);
         const bool all_ok = __all(ok);
         if (lane == 0) sample_loss[b] = all_ok ? (float)(s / (double)(hi - lo)) : nan;
     }
@@ -301,27 +190,13 @@ __global__ __launch_bounds__(64) void k_attn_sets_bwd(const float* __restrict__ 
     if (t < nt) {
         float* p = Pm + t * LS;
         float* ds = dS + t * LS;
-        float mx = -INFINITY;
-        {   // S = scale q k^T and P = softmax(S): the forward's arithmetic
+        float den;
+        {   // p = exp(S - max) and den, S = scale q k^T: the forward's row
             float q[DH];
             const float* r = qkv + (t0 + t) * (int64_t)(3 * D) + h;
 #pragma unroll
             for (int d = 0; d < DH; d++) q[d] = r[d * kHeads];
-            for (int m = 0; m < ns; m++) {
-                const float* k = KQ + m * DH;
-                float a = 0.f;
-#pragma unroll
-                for (int d = 0; d < DH; d++) a = fmaf(q[d], k[d], a);
-                a *= scale;
-                p[m] = a;
-                mx = fmaxf(mx, a);
-            }
-        }
-        float den = 0.f;
-        for (int m = 0; m < ns; m++) {
-            const float e = expf(p[m] - mx);
-            p[m] = e;
-            den += e;
+            attention_row<DH>(q, KQ, DH, ns, scale, p, den);
         }
         float delta = 0.f;                                   // rowsum(P o dP)
         {
@@ -385,13 +260,6 @@ __global__ __launch_bounds__(64) void k_attn_sets_bwd(const float* __restrict__ 
     }
 }
 
-// Sum over the wavefront's 64 lanes, the same butterfly every time; every lane must call it, all receive the sum.
-__device__ __forceinline__ double wave_sum(double x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-    return x;
-}
-
 // One wavefront per sample.  ws: per sample iters (M + N + 2) doubles, the iterates u_t | v_t of t = 1 .. iters.  Lane j owns
 // column j of the gradient of Z0 throughout; a lane reads back from ws only what it stored itself.
 __global__ __launch_bounds__(64) void k_head_sets_bwd(const float* __restrict__ md, const float* __restrict__ dP, int64_t B, int M, int N,
@@ -400,64 +268,27 @@ __global__ __launch_bounds__(64) void k_head_sets_bwd(const float* __restrict__ 
     extern __shared__ double smd[];
     const int lane = threadIdx.x;
     const int M1 = M + 1, N1 = N + 1;
-    double* Z = smd;                 // [M1][N1] Z0
-    double* gZ = Z + M1 * N1;        // [M1][N1] its gradient
-    double* u = gZ + M1 * N1;        // [M1] u_t
-    double* v = u + M1;              // [N1] v_t
-    double* vp = v + N1;             // [N1] v_{t-1}
+    const HeadLds s(smd, M, N, false);
+    double *Z = s.Z, *u = s.u, *v = s.v;   // Z0, u_t, v_t
+    double* gZ = (double*)s.end;     // [M1][N1] the gradient of Z0
+    double* vp = gZ + M1 * N1;       // [N1] v_{t-1}
     double* gu = vp + N1;            // [M1]
     double* gv = gu + M1;            // [N1]
     const int64_t b = blockIdx.x;
     const float* m0 = md + set_row(0, b, B, M, N) * D;
     const float* m1 = md + set_row(1, b, B, M, N) * D;
     double* it = ws + b * (int64_t)iters * (M1 + N1);
-    const double alpha = (double)alpha_f;
     const double inv = 1.0 / sqrt((double)D);
-    // ---- the forward of k_head_sets, every iterate kept
-    for (int e = lane; e < M1 * N1; e += 64) {
-        const int i = e / N1, j = e % N1;
-        double a = alpha;
-        if (i < M && j < N) {
-            a = 0.0;
-            const float* x = m0 + i * (int64_t)D;
-            const float* y = m1 + j * (int64_t)D;
-            for (int k = 0; k < D; k++) a = fma((double)x[k], (double)y[k], a);
-            a *= inv;
-        }
-        Z[e] = a;
-    }
-    const double norm = -log((double)(M + N));
-    const double lmu_bin = log((double)N) + norm, lnu_bin = log((double)M) + norm;
-    if (lane < M1) u[lane] = 0.0;
-    if (lane < N1) v[lane] = 0.0;
-    __syncthreads();
-    for (int t = 0; t < iters; t++) {
-        if (lane < M1) {
-            double mx = -INFINITY;
-            for (int j = 0; j < N1; j++) mx = fmax(mx, Z[lane * N1 + j] + v[j]);
-            double s = 0.0;
-            for (int j = 0; j < N1; j++) s += exp(Z[lane * N1 + j] + v[j] - mx);
-            u[lane] = (lane < M ? norm : lmu_bin) - (mx + log(s));
-            it[t * (M1 + N1) + lane] = u[lane];
-        }
-        __syncthreads();
-        if (lane < N1) {
-            double mx = -INFINITY;
-            for (int i = 0; i < M1; i++) mx = fmax(mx, Z[i * N1 + lane] + u[i]);
-            double s = 0.0;
-            for (int i = 0; i < M1; i++) s += exp(Z[i * N1 + lane] + u[i] - mx);
-            v[lane] = (lane < N ? norm : lnu_bin) - (mx + log(s));
-            it[t * (M1 + N1) + M1 + lane] = v[lane];
-        }
-        __syncthreads();
-    }
+    // ---- the forward, every iterate kept
+    transport_scores(m0, m1, M, N, D, (double)alpha_f, Z);
+    const LogMarginals lm = sinkhorn_iterate(Z, u, v, M, N, iters, [=](int t, int i, bool is_v, double x) { it[t * (M1 + N1) + (is_v ? M1 : 0) + i] = x; });
     // ---- G = dP exp(Z) from the float64 log couplings; gZ0 = G, gu = rowsum(G), gv = colsum(G)
     {
         double cs = 0.0;
         for (int i = 0; i < M1; i++) {
             double g = 0.0;
             if (lane < N1) {
-                const double z = Z[i * N1 + lane] + u[i] + v[lane] - norm;
+                const double z = Z[i * N1 + lane] + u[i] + v[lane] - lm.norm;
                 g = (double)dP[(b * M1 + i) * (int64_t)N1 + lane] * exp(z);
                 gZ[i * N1 + lane] = g;
                 cs += g;
@@ -477,7 +308,7 @@ __global__ __launch_bounds__(64) void k_head_sets_bwd(const float* __restrict__ 
         }
         __syncthreads();
         {   // v_t = log_nu - logsumexp_i(Z0 + u_t): W[i, j] = exp(Z0 + u_t[i] + v_t[j] - log_nu[j]), columns sum to 1
-            const double lnu = lane < N ? norm : lnu_bin;
+            const double lnu = lane < N ? lm.norm : lm.nu_bin;
             const double gvj = lane < N1 ? gv[lane] : 0.0;
             for (int i = 0; i < M1; i++) {
                 double term = 0.0;
@@ -493,7 +324,7 @@ __global__ __launch_bounds__(64) void k_head_sets_bwd(const float* __restrict__ 
         if (lane < N1) {  // u_t = log_mu - logsumexp_j(Z0 + v_{t-1}): R[i, j] = exp(Z0 + v_{t-1}[j] + u_t[i] - log_mu[i]), rows sum to 1
             double acc = 0.0;
             for (int i = 0; i < M1; i++) {
-                const double r = exp(Z[i * N1 + lane] + vp[lane] + u[i] - (i < M ? norm : lmu_bin));
+                const double r = exp(Z[i * N1 + lane] + vp[lane] + u[i] - (i < M ? lm.norm : lm.mu_bin));
                 const double term = gu[i] * r;
                 gZ[i * N1 + lane] -= term;                   // gZ0 -= diag(gu) R
                 acc -= term;                                 // gv = -R^T gu
@@ -573,17 +404,6 @@ __global__ __launch_bounds__(kLossThreads) void k_colsum(const float* __restrict
     }
 }
 
-int check_sizes(const char* what, int64_t batch, int M, int N, int D) {
-    T2P_CHECK_ARG(batch >= 0 && M >= 1 && N >= 1 && M <= kMaxTokens && N <= kMaxTokens,
-                  "%s: need 1 <= n_obj, n_hints <= 63 (got %d, %d)", what, M, N);
-    if (D != 64 && D != 128 && D != 256) {
-        set_error("%s: embed_dim=%d not built (64, 128, 256)", what, D);
-        return T2P_E_UNSUPPORTED;
-    }
-    T2P_CHECK_ARG(batch * 2 * kHeads <= 0x7fffffff, "%s: batch %lld too large for one launch", what, (long long)batch);
-    return 0;
-}
-
 size_t head_bwd_ws_bytes(int64_t batch, int M, int N, int iters) {
     return (size_t)batch * (size_t)iters * (size_t)(M + N + 2) * sizeof(double);
 }
@@ -621,8 +441,7 @@ int t2p_match_head(const float* mdesc, int64_t batch, int32_t n_obj, int32_t n_h
     T2P_TRY(check_sizes("match_head", batch, M, N, D));
     T2P_CHECK_ARG(sinkhorn_iters >= 0, "match_head: sinkhorn_iters < 0");
     if (batch == 0) return 0;
-    // Z, u, v, the maxima (doubles) and their indices: <= 35.3 KiB at 63 + 63 tokens
-    const size_t lds = ((size_t)(M + 1) * (N + 1) + (M + 1) + (N + 1) + (M + N)) * sizeof(double) + (size_t)(M + N) * sizeof(int);
+    const size_t lds = head_lds_bytes(M, N, true);
     ProfScope ps_("match_train_head", st);
     hipLaunchKernelGGL(k_head_sets, dim3((unsigned)batch), dim3(64), lds, st, mdesc, batch, M, N, D, bin_score, sinkhorn_iters,
                        match_threshold, P, matches0, matches1, mscores0, mscores1);
@@ -691,7 +510,7 @@ int t2p_match_head_backward(const float* mdesc, const float* dP, int64_t batch, 
     }
     if (batch == 0) return 0;
     // Z0 and its gradient, u_t, v_t, v_{t-1}, gu, gv: <= 66.5 KiB at 63 + 63 tokens
-    const size_t lds = ((size_t)2 * (M + 1) * (N + 1) + (size_t)2 * (M + 1) + (size_t)3 * (N + 1)) * sizeof(double);
+    const size_t lds = head_lds_bytes(M, N, false) + ((size_t)(M + 1) * (N + 1) + (M + 1) + (size_t)2 * (N + 1)) * sizeof(double);
     if (lds > 64 * 1024) T2P_TRY(reserve_lds((const void*)k_head_sets_bwd, 80 * 1024, "match_head_backward"));
     ProfScope ps_("match_train_head_bwd", st);
     hipLaunchKernelGGL(k_head_sets_bwd, dim3((unsigned)batch), dim3(64), lds, st, mdesc, dP, batch, M, N, D, bin_score, sinkhorn_iters,

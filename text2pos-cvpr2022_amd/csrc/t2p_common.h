@@ -84,6 +84,14 @@ __device__ __forceinline__ uint32_t split_lo_pk(fp16x2 hi, float v0, float v1) {
 }
 // workgroup barrier that orders LDS traffic only (no vmcnt: loads and LDS-DMA pieces in flight survive it)
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+// Sum over the wavefront's 64 lanes by the xor butterfly 32, 16, ... 1: the same tree every time.  Every lane must call it, all
+// receive the sum.
+template <typename T>
+__device__ __forceinline__ T wave_sum(T x) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
+    return x;
+}
 typedef double f64x4 __attribute__((ext_vector_type(4)));
 
 int num_cus();  // cached multiProcessorCount of the current device

@@ -11,7 +11,7 @@ from .losses import CrossEntropyLoss, HardestRankingLoss, MatchingLoss, MSELoss,
 from .modules import LanguageEncoder, get_mlp  # noqa: F401
 from .object_encoder import ObjectEncoder  # noqa: F401
 from .pointnet2 import PointNet2  # noqa: F401
-from .retrieval import retrieve_topk  # noqa: F401
+from .retrieval import retrieve_topk, retrieve_topk_distinct  # noqa: F401
 from .superglue_matcher import SuperGlueMatch, get_pos_in_cell  # noqa: F401
 
 

@@ -1,4 +1,4 @@
-"""ctypes binding of libt2p_hip.so (C ABI: include/t2p.h and its extension include/t2p_serve.h).
+"""ctypes binding of libt2p_hip.so (C ABI: include/t2p.h and its extensions include/t2p_serve.h, include/t2p_select.h).
 
 The product path has no CPU fallback: if the HIP library is missing or fails a call, this raises.
 torch is imported first so that the library binds to the HIP runtime (libamdhip64.so.7) torch already loaded --
@@ -14,6 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("T2P_LIB") or os.path.join(_HERE, "libt2p_hip.so")  # T2P_LIB: A/B builds of the same ABI
 HEADER = os.path.join(_HERE, "..", "include", "t2p.h")   # the one statement of every signature, struct and limit
 SERVE_HEADER = os.path.join(_HERE, "..", "include", "t2p_serve.h")   # the serving extension: its own version and record
+SELECT_HEADER = os.path.join(_HERE, "..", "include", "t2p_select.h")   # distinct candidates: likewise
 
 
 class T2PError(RuntimeError):
@@ -22,8 +23,9 @@ class T2PError(RuntimeError):
 
 # The binding's type rule.  Scalars map to their ctypes twins; `const t2p_x*` to POINTER(X), so a call checks the struct it is
 # handed; `char*` to c_char_p; every other pointer and t2p_stream_t to c_void_p (device pointers travel as integers).
+# `double` by value is a parameter only (t2p_select.h's `sep`): no function returns one.
 _SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "uint32_t": C.c_uint32, "size_t": C.c_size_t,
-            "float": C.c_float}
+            "float": C.c_float, "double": C.c_double}
 _POINTEES = set(_SCALARS) | {"void", "char", "double", "uint8_t", "uint16_t", "uint64_t", "t2p_stream_t"}
 _DECLARATOR = re.compile(r"((?:\*\s*(?:const\b\s*)?)*)(?!const\b)(\w+)\s*(?:\[\s*(\d+)\s*\])?")
 
@@ -77,6 +79,8 @@ def parse_header(text):
         if not m:
             raise T2PError(f"include/t2p.h: cannot read the declaration `{stmt}`")
         base, stars, name, params = m.groups()
+        if (base, stars) == ("double", ""):
+            raise T2PError(f"include/t2p.h: unknown type in `{stmt}`")
         res = None if (base, stars) == ("void", "") else _ctype(base, len(stars), structs, stmt)
         args = [t for p in params.split(",") if params != "void" for _, t in _declare(p.strip(), structs)]
         if any(issubclass(t, C.Array) for t in args):
@@ -97,6 +101,12 @@ if _serve_structs or set(SERVE_SYMBOLS) & set(SYMBOLS):
     raise T2PError("include/t2p_serve.h: declares a struct or repeats a symbol of include/t2p.h")
 SERVE_ABI_VERSION = SERVE_DEFINES["T2P_SERVE_ABI_VERSION"]
 
+with open(SELECT_HEADER) as _f:
+    SELECT_DEFINES, _select_structs, SELECT_SYMBOLS = parse_header(_f.read())
+if _select_structs or set(SELECT_SYMBOLS) & (set(SYMBOLS) | set(SERVE_SYMBOLS)):
+    raise T2PError("include/t2p_select.h: declares a struct or repeats a symbol of include/t2p.h or include/t2p_serve.h")
+SELECT_ABI_VERSION = SELECT_DEFINES["T2P_SELECT_ABI_VERSION"]
+
 _lib = None
 
 
@@ -109,13 +119,15 @@ def lib() -> C.CDLL:
                 f"{LIB_PATH} is missing: build the HIP extension first "
                 "(python __graft_entry__.py build, or python text2pos-cvpr2022_amd/build.py)")
         handle = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SYMBOLS.items()) + list(SERVE_SYMBOLS.items()):
+        for name, (res, args) in list(SYMBOLS.items()) + list(SERVE_SYMBOLS.items()) + list(SELECT_SYMBOLS.items()):
             fn = getattr(handle, name)  # AttributeError if the export is missing
             fn.restype, fn.argtypes = res, args
         if handle.t2p_abi_version() != ABI_VERSION:
             raise T2PError(f"libt2p_hip.so ABI {handle.t2p_abi_version()} != binding ABI {ABI_VERSION}")
         if handle.t2p_serve_abi_version() != SERVE_ABI_VERSION:
             raise T2PError(f"libt2p_hip.so serve ABI {handle.t2p_serve_abi_version()} != binding serve ABI {SERVE_ABI_VERSION}")
+        if handle.t2p_select_abi_version() != SELECT_ABI_VERSION:
+            raise T2PError(f"libt2p_hip.so select ABI {handle.t2p_select_abi_version()} != binding select ABI {SELECT_ABI_VERSION}")
         _lib = handle
     return _lib
 

@@ -1,4 +1,4 @@
-"""Builds libt2p_hip.so (the gfx950 kernels + C ABI of include/t2p.h) in-tree with hipcc.
+"""Builds libt2p_hip.so (the gfx950 kernels + C ABI of include/t2p.h and its extensions) in-tree with hipcc.
 
     python -m text2pos_amd.build            # or: python text2pos-cvpr2022_amd/build.py
 
@@ -13,9 +13,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libt2p_hip.so")
-SOURCES = ["api.hip", "cell_encoder.hip", "sample_group.hip", "small_kernels.hip", "tg_gemm.hip", "tg_gemm_tn.hip", "tg_gemm_x3.hip", "train_gemm.hip", "ws_gemm.hip", "ga2.hip", "ws_sa.hip", "sa_rows.hip", "sa3.hip", "sa_points.hip", "lstm.hip", "train_ops.hip", "sim_topk.hip", "match.hip", "match_train.hip", "classify.hip", "fine_stats.hip", "localize.hip"]
+SOURCES = ["api.hip", "cell_encoder.hip", "sample_group.hip", "small_kernels.hip", "tg_gemm.hip", "tg_gemm_tn.hip", "tg_gemm_x3.hip", "train_gemm.hip", "ws_gemm.hip", "ga2.hip", "ws_sa.hip", "sa_rows.hip", "sa3.hip", "sa_points.hip", "lstm.hip", "train_ops.hip", "sim_topk.hip", "match.hip", "match_train.hip", "classify.hip", "fine_stats.hip", "localize.hip", "distinct.hip"]
 HEADERS = [os.path.join(CSRC, "t2p_common.h"), os.path.join(CSRC, "match_common.h"), os.path.join(HERE, "..", "include", "t2p.h"),
-           os.path.join(HERE, "..", "include", "t2p_serve.h")]
+           os.path.join(HERE, "..", "include", "t2p_serve.h"), os.path.join(HERE, "..", "include", "t2p_select.h")]
 # -ffp-contract=off: the index-producing kernels (FPS, ball query, kNN) pin their fp32 distance arithmetic to the
 # oracle's un-contracted form; fused multiply-adds are written explicitly (fmaf / MFMA) where they are wanted.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-Wno-unused-function"]

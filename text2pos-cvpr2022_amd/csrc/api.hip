@@ -11,6 +11,7 @@
 
 #include "../../include/t2p.h"
 #include "../../include/t2p_serve.h"
+#include "../../include/t2p_select.h"
 #include "t2p_common.h"
 
 namespace t2p {
@@ -117,6 +118,7 @@ extern "C" {
 
 int t2p_abi_version(void) { return T2P_ABI_VERSION; }
 int t2p_serve_abi_version(void) { return T2P_SERVE_ABI_VERSION; }
+int t2p_select_abi_version(void) { return T2P_SELECT_ABI_VERSION; }
 
 void t2p_profile_enable(int on) {
     std::lock_guard<std::mutex> lock(g_prof_mu);

@@ -5,6 +5,7 @@
     python -m text2pos_amd.localize query --db db.pt --path_coarse ./checkpoints/coarse.pth --path_fine ./checkpoints/fine.pth \\
         --hints "The pose is north of a gray road." "The pose is east of a green tree."
     python -m text2pos_amd.localize query ... --hints "..." --prior 1042.5 3310.0 --radius 60 --scene 2013_05_28_drive_0010_sync
+    python -m text2pos_amd.localize query ... --hints "..." --distinct 30
 
 The reference has no such path: the only code that chains text encoding, top-k, the fine matcher and the pose estimate is its
 evaluation (evaluation/pipeline.py:60-137, :172-279), which needs ground-truth poses and the raw scene, and re-encodes every
@@ -22,6 +23,9 @@ are fixed, so here they are encoded ONCE:
                  (t2p_sim_topk_prior, include/t2p_serve.h): a cell qualifies when the prior point lies within the radius of the
                  cell's square and the cell belongs to the named scene.  Applied after an unrestricted top-k the prior would
                  return nothing whenever the k best cells of the whole database lie elsewhere.
+                 With distinct_radius the top_k candidates are k different places: overlapping cells (30 m on a 10 m stride) have
+                 near-duplicate embeddings, so the ranking returns a pool of cells and t2p_topk_distinct (include/t2p_select.h)
+                 keeps the best top_k no two of which lie within the radius of each other in x and in y, scene by scene.
 
 The deliberate difference from the evaluation: a database cell has ONE T.FixedPoints draw, `transform.keys(row, slot)` of its
 database row, where run_fine draws once per (query, candidate) sample as the reference's dataloader does.
@@ -37,7 +41,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .retrieval import check_top_k, retrieve_topk
+from .retrieval import MAX_TOP_K, check_distinct, check_top_k, default_distinct_pool, retrieve_topk
 from .superglue_matcher import MATCH_THRESHOLD
 
 FORMAT = 1
@@ -114,6 +118,11 @@ class CellDatabase:
         """float64 [Nc, 4] on the database's device: x0, y0, x0 + cell_size, y0 + cell_size (one rounding each), the closed square
         a prior position is measured against."""
         return torch.cat([self.bbox_xy, self.bbox_xy + self.cell_size[:, None]], dim=1).contiguous()
+
+    def cell_centers(self) -> torch.Tensor:
+        """float64 [Nc, 2] on the database's device: x0 + cell_size / 2, y0 + cell_size / 2 (one rounding each), the position two
+        candidates are told apart by (distinct_radius)."""
+        return (self.bbox_xy + 0.5 * self.cell_size[:, None]).contiguous()
 
     def scene_index(self):
         """(sorted unique scene names, int32 [Nc] on the database's device: every cell's index into them)."""
@@ -207,7 +216,10 @@ class Localization(SimpleNamespace):
     best_world_xy float64 [Q, 2] = world_xy[q, best[q]]; n_valid int32 [Q] and restricted (bool).
     A call with a prior (restricted) may find fewer than K cells that qualify: n_valid[q] candidates are valid, always the first
     ones; the columns behind them read cell_rows -1, cell_ids None, scores -inf, NaN positions and matched 0; best is taken over
-    the valid columns only and is -1, with a NaN best_world_xy, where n_valid is 0.  Without a prior n_valid is K."""
+    the valid columns only and is -1, with a NaN best_world_xy, where n_valid is 0.  Without a prior n_valid is K.
+    A call with distinct_radius (distinct, restricted both set) has the same states for the candidates the selection did not find,
+    and exhausted bool [Q]: True where fewer than K were found only because the pool of ranked cells ran out (ask again with a
+    larger distinct_pool); where it is False the candidates are those of the whole database.  Otherwise exhausted is all False."""
 
     def to_json(self, q: int) -> dict:
         """One query as plain values.  Unrestricted: the fields of _RESULT_FIELDS.  Restricted: n_valid besides, every per-candidate
@@ -222,6 +234,8 @@ class Localization(SimpleNamespace):
         if n == 0:
             out["best"] = out["best_world_xy"] = None
         out["n_valid"] = n
+        if getattr(self, "distinct", False):
+            out["exhausted"] = bool(self.exhausted[q])
         return out
 
 
@@ -280,13 +294,41 @@ def check_prior(n_queries: int, prior_xy, prior_radius, scenes, known_scenes: Se
     return xy, rad, grp
 
 
-def unpack_result(res: np.ndarray, k: int, cell_ids: Sequence[str], restricted: bool, what: str = "Localizer.localize") -> Localization:
+def check_distinct_args(distinct_radius, distinct_pool, top_k: int, n_cells: int):
+    """The distinct-candidates arguments of Localizer.localize, checked on the host before anything is encoded -> None without a
+    radius, else (radius float, pool int).  radius: one number >= 0, inf allowed; pool: None (retrieval.default_distinct_pool) or a
+    whole number in [top_k, min(n_cells, MAX_TOP_K)]; a pool without a radius is refused."""
+    if distinct_radius is None:
+        if distinct_pool is not None:
+            raise ValueError("localize: distinct_pool needs distinct_radius")
+        return None
+    if isinstance(distinct_radius, bool) or np.ndim(distinct_radius) != 0:
+        raise ValueError(f"localize: distinct_radius must be one number >= 0 (got {distinct_radius!r})")
+    radius = check_distinct(distinct_radius, "localize: distinct_radius")
+    hi = min(int(n_cells), MAX_TOP_K)
+    if distinct_pool is None:
+        return radius, default_distinct_pool(n_cells, top_k)
+    if isinstance(distinct_pool, bool) or np.ndim(distinct_pool) != 0 or int(distinct_pool) != distinct_pool or \
+            not top_k <= int(distinct_pool) <= hi:
+        raise ValueError(f"localize: distinct_pool={distinct_pool!r} outside [top_k, min(len(db), {MAX_TOP_K})] = [{top_k}, {hi}]")
+    return radius, int(distinct_pool)
+
+
+def unpack_result(res: np.ndarray, k: int, cell_ids: Sequence[str], restricted: bool, what: str = "Localizer.localize",
+                  distinct: bool = False) -> Localization:
     """The packed float64 [Q, 11 K + 1] rows of Localizer._run_chunk (in the caller's order, on the host) -> Localization.
+    distinct: the rows come from a call with distinct_radius and carry two more columns, the selection's n_valid (-1: a pool index
+    outside the database, IndexError naming the query) and its exhausted flag; the columns it did not fill are at -inf, so the
+    rest is the restricted handling.
     restricted: candidate j of a query is valid iff its score is above -inf (the masked pairs of t2p_sim_topk_prior are exactly
     -inf and come last); the invalid columns, whose rows are real cells the matcher ran on, are overwritten as Localization
     states, and best is recomputed over the valid columns (most matched objects, the first on ties, -1 without any)."""
     nq = res.shape[0]
     cut = lambda i, n=1: res[:, i * k: (i + n) * k]
+    exhausted = np.zeros(nq, dtype=bool)
+    if distinct:
+        ops.distinct_check(res[:, 11 * k + 1], what)
+        exhausted, restricted = res[:, 11 * k + 2] != 0, True
     matched = cut(10).astype(np.int32)
     ops.localize_check(matched, what)
     rows = cut(0).astype(np.int64)
@@ -311,7 +353,8 @@ def unpack_result(res: np.ndarray, k: int, cell_ids: Sequence[str], restricted: 
     if restricted and nq:
         best_xy[best < 0] = np.nan           # (a copy: fancy indexing)
     return Localization(cell_rows=rows, cell_ids=ids, scores=scores, pos_in_cell_mean=pos[0], pos_in_cell=pos[1], world_xy_mean=pos[2],
-                        world_xy=world, matched=matched, best=best, best_world_xy=best_xy, n_valid=n_valid, restricted=bool(restricted))
+                        world_xy=world, matched=matched, best=best, best_world_xy=best_xy, n_valid=n_valid, restricted=bool(restricted),
+                        exhausted=exhausted, distinct=bool(distinct))
 
 
 def group_by_hint_count(hints: List[List[str]]) -> Dict[int, List[int]]:
@@ -331,12 +374,19 @@ class Localizer:
         check_models(database.meta, model_coarse, model_fine, "Localizer")
         self.model_coarse, self.model_fine, self.database = model_coarse, model_fine, database
         self._tables = None      # (len(database), cell boxes, scene names, scene index): what a prior is checked against
+        self._centers = None     # (len(database), cell centres): what distinct candidates are told apart by
 
     def prior_tables(self):
         """(cell_boxes, scene names, scene index) of the database, computed once and again after the database grew (extend)."""
         if self._tables is None or self._tables[0] != len(self.database):
             self._tables = (len(self.database), self.database.cell_boxes(), *self.database.scene_index())
         return self._tables[1:]
+
+    def distinct_tables(self):
+        """(cell centres float64 [Nc, 2], scene index int32 [Nc]) of the database, computed once and again after it grew."""
+        if self._centers is None or self._centers[0] != len(self.database):
+            self._centers = (len(self.database), self.database.cell_centers())
+        return self._centers[1], self.prior_tables()[2]
 
     def _require_device(self):
         db = self.database
@@ -346,13 +396,16 @@ class Localizer:
         if not (torch.device(db.device) == torch.device(self.model_coarse.device) == torch.device(self.model_fine.device)):
             raise RuntimeError("Localizer.localize: database and models are on different devices")
 
-    def _run_chunk(self, hints: List[List[str]], top_k: int, prior=None) -> torch.Tensor:
+    def _run_chunk(self, hints: List[List[str]], top_k: int, prior=None, distinct=None) -> torch.Tensor:
         """Queries with the same number of hints -> float64 [Q, 11 K + 1] on the device: cell rows | scores | pos_mean | pos_offset |
         world_mean | world_offset (K x 2 each) | matched | best.  (Rows and counts are small integers: exact in float64.)
         prior: None, or (xy [Q, 2], radius [Q], group [Q] or None) of these queries, already on the device (localize uploads the
         whole call's prior once, before the first launch: an upload between the chunks would wait for the work in flight) - the
         ranking then runs on t2p_sim_topk_prior; a masked candidate's row is still a real cell, so the matcher and the pose
-        estimate run on it as on any other."""
+        estimate run on it as on any other.
+        distinct: None, or (radius, pool): the ranking (either family) returns `pool` cells per query and t2p_topk_distinct keeps the
+        best K no two of which conflict; the rows then carry two more columns, the selection's n_valid and exhausted.  A column
+        it did not fill holds the query's first pool row at -inf: a real cell, as a masked candidate of the prior path is."""
         db, mc, mf = self.database, self.model_coarse, self.model_fine
         nq, k = len(hints), int(top_k)
         for m in (mc, mf):
@@ -360,13 +413,21 @@ class Localizer:
                 raise NotImplementedError("Localizer.localize: a model was put into train() mode; call .eval()")
         with torch.no_grad():
             text = mc.encode_text([" ".join(h) for h in hints])                      # io.Scenes.texts (cells.py:82)
+            n_rank = k if distinct is None else int(distinct[1])
             if prior is None:
-                rows, scores = retrieve_topk(db.coarse, text, k)
+                rows, scores = retrieve_topk(db.coarse, text, n_rank)
             else:
                 xy, rad, grp = prior
                 boxes, _, scene_idx = self.prior_tables()
                 groups = {} if grp is None else dict(cell_groups=scene_idx, query_groups=grp)
-                rows, scores = retrieve_topk(db.coarse, text, k, cell_boxes=boxes, query_xy=xy, query_radius=rad, validate=False, **groups)
+                rows, scores = retrieve_topk(db.coarse, text, n_rank, cell_boxes=boxes, query_xy=xy, query_radius=rad, validate=False,
+                                             **groups)
+            extra = []
+            if distinct is not None:
+                centers, scene_idx = self.distinct_tables()
+                rows, scores, n_valid, exhausted = ops.topk_distinct(rows, scores, centers, float(distinct[0]), k, cell_group=scene_idx,
+                                                                     check=False)
+                extra = [n_valid, exhausted]
             hint_enc = mf.encode_hints(hints).contiguous()                           # once per query, not per candidate
             obj_row = rows.reshape(-1).to(torch.int32)
             hint_row = torch.arange(nq, dtype=torch.int32, device=rows.device).repeat_interleave(k)
@@ -375,10 +436,10 @@ class Localizer:
                                       check=False)
         flat = lambda t: t.reshape(nq, -1).to(torch.float64)
         return torch.cat([flat(rows), flat(scores), flat(pose["pos_mean"]), flat(pose["pos_offset"]), flat(pose["world_mean"]),
-                          flat(pose["world_offset"]), flat(pose["matched"]), flat(pose["best"])], dim=1)
+                          flat(pose["world_offset"]), flat(pose["matched"]), flat(pose["best"])] + [flat(t) for t in extra], dim=1)
 
     def localize(self, hints: List[List[str]], top_k: int = 10, queries_per_call: Optional[int] = None, *, prior_xy=None,
-                 prior_radius=None, scenes=None) -> Localization:
+                 prior_radius=None, scenes=None, distinct_radius=None, distinct_pool=None) -> Localization:
         """hints: one list of hint sentences per query (1 to 63 each; the coarse text of a query is " ".join(hints)).  Queries are
         grouped by their number of hints, run in calls of queries_per_call (None = min(256, 4096 // top_k), evaluation.run_fine's
         device default) and returned in the caller's order.  One device-to-host copy at the end; a sample either kernel refused to
@@ -386,13 +447,20 @@ class Localizer:
         prior_xy (one (x, y) or [Q, 2], world metres) with prior_radius (one number or [Q], >= 0; inf = no geometric restriction)
         and / or scenes (one name, or Q entries each a name or None = any scene) restrict the ranking to the cells within the
         radius of the position (distance to the cell's closed square: 0 keeps the cells that contain the point) and of the named
-        scene; see Localization for a query with fewer than top_k such cells.  Without them: the unrestricted call, bit for bit."""
+        scene; see Localization for a query with fewer than top_k such cells.  Without them: the unrestricted call, bit for bit.
+        distinct_radius (metres, >= 0, inf allowed): the candidates are top_k DIFFERENT places - walking the ranking (restricted or
+        not) from the best cell, a cell is taken iff no cell taken before it lies within distinct_radius of it in x and in y
+        (cell centres, strictly) in the same scene.  The cell size asks for non-overlapping cells; 0 is the plain ranking; inf one
+        cell per scene.  The walk sees the distinct_pool best cells (None: min(len(db), 1024, max(64, 32 top_k)); any value in
+        [top_k, min(len(db), 1024)]): Localization.exhausted marks the queries it was too short for.  Without distinct_radius the
+        call is the one above, bit for bit."""
         hints = check_hints(hints)
         k = check_top_k(top_k)
         if np.ndim(top_k) != 0:
             raise ValueError("localize: top_k is one number (the candidates per query)")
         if k > len(self.database):
             raise ValueError(f"localize: top_k={k} exceeds the {len(self.database)} cells of the database")
+        distinct = check_distinct_args(distinct_radius, distinct_pool, k, len(self.database))
         per_call = min(256, 4096 // k) if queries_per_call is None else int(queries_per_call)
         per_call = max(1, per_call)
         nq = len(hints)
@@ -409,23 +477,27 @@ class Localizer:
             prior = tuple(None if t is None else torch.from_numpy(np.ascontiguousarray(t[sel])).to(dev) for t in (xy, rad, grp))
         parts, at = [], 0
         for chunk in chunks:
+            more = {} if distinct is None else dict(distinct=distinct)
             if restricted:
-                parts.append(self._run_chunk([hints[q] for q in chunk], k, tuple(None if t is None else t[at: at + len(chunk)] for t in prior)))
+                parts.append(self._run_chunk([hints[q] for q in chunk], k, tuple(None if t is None else t[at: at + len(chunk)] for t in prior),
+                                             **more))
             else:
-                parts.append(self._run_chunk([hints[q] for q in chunk], k))
+                parts.append(self._run_chunk([hints[q] for q in chunk], k, **more))
             at += len(chunk)
-        width = 11 * k + 1
+        width = 11 * k + (1 if distinct is None else 3)
         packed = torch.cat(parts).cpu().numpy() if parts else np.zeros((0, width))       # the call's one device-to-host copy
         res = np.empty((nq, width), dtype=np.float64)
         res[np.asarray(order, dtype=np.int64)] = packed
-        return unpack_result(res, k, self.database.cell_ids, restricted)
+        if distinct is None:
+            return unpack_result(res, k, self.database.cell_ids, restricted)
+        return unpack_result(res, k, self.database.cell_ids, restricted, distinct=True)
 
     def localize_poses(self, poses, top_k: int = 10, queries_per_call: Optional[int] = None, *, prior_xy=None, prior_radius=None,
-                       scenes=None) -> Localization:
+                       scenes=None, distinct_radius=None, distinct_pool=None) -> Localization:
         """localize() on the hint sentences of data.Pose objects (evaluation.create_hint_description)."""
         from .evaluation import create_hint_description
         return self.localize([create_hint_description(p) for p in poses], top_k, queries_per_call, prior_xy=prior_xy,
-                             prior_radius=prior_radius, scenes=scenes)
+                             prior_radius=prior_radius, scenes=scenes, distinct_radius=distinct_radius, distinct_pool=distinct_pool)
 
 
 # ---- command line ---------------------------------------------------------------------------------------------------------------
@@ -490,11 +562,17 @@ def parse_args(argv: Optional[List[str]] = None):
                            help="prior position in world metres (with --radius); applies to every query of the invocation")
             p.add_argument("--radius", type=float, default=None, help="radius of --prior in metres (0: the cells that contain it)")
             p.add_argument("--scene", default=None, help="rank only the cells of this scene; applies to every query")
+            p.add_argument("--distinct", type=float, default=None, metavar="METRES",
+                           help="return top_k different places: no two candidates of a scene within METRES of each other in x and in y")
+            p.add_argument("--distinct_pool", type=int, default=None, metavar="N",
+                           help="ranked cells per query the distinct selection walks (with --distinct; default max(64, 32 top_k))")
             p.add_argument("--vocab_base_path", default=None, help="dataset the models' vocabulary comes from (with --vocab_scenes)")
             p.add_argument("--vocab_scenes", nargs="*", default=SCENE_NAMES_VAL)
     a = ap.parse_args(argv)
     if a.command == "query" and (a.prior is None) != (a.radius is None):
         ap.error("--prior X Y and --radius R go together")
+    if a.command == "query" and a.distinct_pool is not None and a.distinct is None:
+        ap.error("--distinct_pool N needs --distinct METRES")
     return a
 
 
@@ -514,6 +592,7 @@ def main(argv: Optional[List[str]] = None):
     queries = check_hints(read_queries(a.hints, a.queries_file))
     db = CellDatabase.load(a.db)
     check_prior(len(queries), a.prior, a.radius, a.scene, sorted(set(db.scene_names)))   # before the checkpoints are read
+    check_distinct_args(a.distinct, a.distinct_pool, int(a.top_k), len(db))
     if a.vocab_base_path:
         words = IO.load_scenes(a.vocab_base_path, a.vocab_scenes).get_known_words()
     elif "known_words" in db.meta:
@@ -521,7 +600,8 @@ def main(argv: Optional[List[str]] = None):
     else:
         raise ValueError("query: the database carries no vocabulary; give --vocab_base_path")
     coarse, fine, _ = _load_models(a, words=words, classes=list(D.KNOWN_CLASSES))
-    res = Localizer(coarse, fine, db.to(coarse.device)).localize(queries, a.top_k, prior_xy=a.prior, prior_radius=a.radius, scenes=a.scene)
+    res = Localizer(coarse, fine, db.to(coarse.device)).localize(queries, a.top_k, prior_xy=a.prior, prior_radius=a.radius, scenes=a.scene,
+                                                                distinct_radius=a.distinct, distinct_pool=a.distinct_pool)
     for q in range(len(queries)):
         print(json.dumps(res.to_json(q)))
     return res

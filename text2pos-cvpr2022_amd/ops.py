@@ -1373,6 +1373,53 @@ def localize_poses(matches0: torch.Tensor, offsets: torch.Tensor, cell_row: torc
     return out
 
 
+def distinct_check(n_valid: np.ndarray, what: str = "topk_distinct", query_offset: int = 0):
+    """IndexError naming the first query the selection kernel marked with n_valid = -1 (host array [Q])."""
+    bad = np.flatnonzero(np.asarray(n_valid) < 0)
+    if len(bad):
+        raise IndexError(f"{what}: query {int(bad[0]) + query_offset}: a pool index outside the cell table ({len(bad)} such queries; the "
+                         "kernel marks them instead of reading through the index)")
+
+
+def topk_distinct(pool_idx: torch.Tensor, pool_score: torch.Tensor, cell_xy: torch.Tensor, sep: float, k: int, cell_group=None,
+                  index_offset: int = 0, check: bool = True):
+    """Greedy non-overlap selection over a ranked pool (t2p_topk_distinct, include/t2p_select.h).  pool_idx int64 / pool_score
+    float64 [nq, pool]: a query's cells as sim_topk* return them (score descending, ties to the lower index, -inf last, indices
+    index_offset + row); cell_xy float64 [n_cells, 2]: the cells' centres; cell_group int32 [n_cells] or None.  Walks each pool from
+    the front to its first -inf entry and accepts a cell iff no accepted one lies within sep of it in x AND in y (strictly, float64)
+    in the same group, up to k.  sep = 0: the first k entries; inf: one cell per group; negative or NaN: refused.
+    Returns (idx int64 [nq, k], scores float64 [nq, k], n_valid int32 [nq], exhausted int32 [nq]) on the GPU: the accepted entries
+    first, then the first pool entry's index at -inf; exhausted = 1 where fewer than k were found only because the pool ran out
+    (no -inf entry in it and pool < n_cells) - where it is 0 the result is that of the full ranking.
+    check (default): read n_valid back and raise IndexError naming the first query with a pool index outside the table
+    (distinct_check); a caller that copies the results anyway passes check=False and calls distinct_check itself."""
+    _need(pool_idx, "pool_idx", torch.int64, 2)
+    dev = pool_idx.device
+    _need(pool_score, "pool_score", torch.float64, 2, dev)
+    _need(cell_xy, "cell_xy", torch.float64, 2, dev)
+    if cell_group is not None:
+        _need(cell_group, "cell_group", torch.int32, 1, dev)
+    nq, pool = pool_idx.shape
+    n_cells = cell_xy.shape[0]
+    if tuple(pool_score.shape) != (nq, pool) or cell_xy.shape[1] != 2 or (cell_group is not None and cell_group.shape[0] != n_cells):
+        raise RuntimeError(f"topk_distinct: pool_idx {tuple(pool_idx.shape)}, pool_score {tuple(pool_score.shape)}, cell_xy "
+                           f"{tuple(cell_xy.shape)}, cell_group {None if cell_group is None else tuple(cell_group.shape)}: expected "
+                           f"[nq, pool] twice, [n_cells, 2] and [n_cells]")
+    k = int(k)
+    idx = torch.empty((nq, max(k, 0)), dtype=torch.int64, device=dev)
+    score = torch.empty((nq, max(k, 0)), dtype=torch.float64, device=dev)
+    n_valid = torch.empty((nq,), dtype=torch.int32, device=dev)
+    exhausted = torch.empty((nq,), dtype=torch.int32, device=dev)
+    if nq == 0 and 1 <= k <= pool:       # (empty tensors have no address to hand over; the entry point launches nothing for nq 0 either)
+        return idx, score, n_valid, exhausted
+    L.check(L.lib().t2p_topk_distinct(_ptr(pool_idx), _ptr(pool_score), nq, pool, n_cells, int(index_offset), _ptr(cell_xy),
+                                      _ptr(cell_group), float(sep), k, _ptr(idx), _ptr(score), _ptr(n_valid), _ptr(exhausted),
+                                      _stream(dev)), "t2p_topk_distinct")
+    if check:
+        distinct_check(n_valid.cpu().numpy())
+    return idx, score, n_valid, exhausted
+
+
 # ---------------------------------------------------------------------------------------------------------------
 def profile_enable(on: bool):
     """Bracket every kernel launch with hipEvents on its launch stream (bench.py's live per-kernel timing)."""

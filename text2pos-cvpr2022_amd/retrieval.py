@@ -137,6 +137,54 @@ def retrieve_topk(cell_encodings, text_encodings, k: int, device=None, index_off
     return ops.sim_topk(q, c, int(k), index_offset)
 
 
+def check_distinct(sep, what: str = "retrieve_topk_distinct") -> float:
+    """The separation of a distinct-candidates call as a float, or a ValueError: a number >= 0, inf allowed (one cell per group)."""
+    try:
+        s = float(sep)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: the separation must be one number >= 0 (got {sep!r})") from None
+    if not s >= 0:
+        raise ValueError(f"{what}: the separation is {s}: it must be >= 0 (0: nothing conflicts, inf: one cell per group)")
+    return s
+
+
+def default_distinct_pool(n_cells: int, k: int) -> int:
+    """min(Nc, MAX_TOP_K, max(64, 32 k)): at a separation of the cell size, 30 m cells on a 10 m stride conflict with 24 neighbours
+    each, rounded up to 32.  A default, not a guarantee: `exhausted` reports the queries it was too small for."""
+    return min(int(n_cells), MAX_TOP_K, max(64, 32 * int(k)))
+
+
+def retrieve_topk_distinct(cell_encodings, text_encodings, k: int, cell_xy, sep: float, pool=None, device=None, index_offset: int = 0,
+                           cell_groups=None, query_groups=None, cell_boxes=None, query_xy=None, query_radius=None,
+                           validate: bool = True):
+    """The k best cells of every query no two of which overlap: retrieve_topk with k = pool (same restriction arguments), then the
+    greedy selection of ops.topk_distinct over that ordered list - a cell is accepted iff no accepted one of its group lies within
+    `sep` of it in x and in y (cell_xy float64 [Nc, 2], the cells' centres).  cell_groups, when given, are the conflict groups too:
+    cells of different groups never suppress each other.  pool: None = default_distinct_pool(Nc, k), or any value in
+    [k, min(Nc, MAX_TOP_K)].  Returns (indices int64 [Nq, k], scores f64 [Nq, k], n_valid int32 [Nq], exhausted int32 [Nq]) on the
+    GPU: n_valid accepted cells first, the columns behind them at -inf; exhausted = 1 where the pool, not the database, cut the
+    list short (ask again with a larger pool).  NaN centres are refused by name (validate=False skips that host read and the
+    one of the selection's marks, for a caller that has checked its table and reads n_valid itself)."""
+    k, sep = check_top_k(k), check_distinct(sep)
+    nc = int(cell_encodings.shape[0])
+    if k > nc:
+        raise ValueError(f"retrieve_topk_distinct: k={k} exceeds the {nc} cells")
+    pool = default_distinct_pool(nc, k) if pool is None else int(pool)
+    if not k <= pool <= min(nc, MAX_TOP_K):
+        raise ValueError(f"retrieve_topk_distinct: pool={pool} outside [k, min(Nc, {MAX_TOP_K})] = [{k}, {min(nc, MAX_TOP_K)}]")
+    idx, score = retrieve_topk(cell_encodings, text_encodings, pool, device=device, index_offset=index_offset, cell_groups=cell_groups,
+                               query_groups=query_groups, cell_boxes=cell_boxes, query_xy=query_xy, query_radius=query_radius,
+                               validate=validate)
+    dev = idx.device
+    xy = _as_device_f64(cell_xy, (nc, 2), "cell_xy", dev)
+    if validate:
+        c = _first_offender(torch.isnan(xy))
+        if c is not None:
+            raise ValueError(f"retrieve_topk_distinct: cell_xy[{c}] = {xy[c].tolist()} holds a NaN")
+    cg = None if cell_groups is None else _as_device_groups(cell_groups, nc, "cell_groups", dev)
+    return ops.topk_distinct(idx, score, xy, sep, k, cell_group=cg, index_offset=index_offset, check=validate)
+
+
 def top_retrievals(cell_encodings, text_encodings, db_cell_ids, top_k):
     """{query_idx: retrieved cell ids} exactly as eval_epoch builds it (training/coarse.py:133-147)."""
     idx, _ = retrieve_topk(cell_encodings, text_encodings, int(np.max(top_k)))
